@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: complex64 IQ Msamples/s through Hann-windowed 4096-point
 FFT + log-PSD (BASELINE.json configs[1]: 2^20 synthetic frames per GPU), with the
-dominant kernel's achieved HBM GB/s against the 8 TB/s roofline and the numpy
-oracle timed on the host cores of the same box.
+dominant kernel's achieved HBM GB/s against the 8 TB/s roofline and (with --full) the
+numpy oracle timed on the host cores of the same box.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the resident batch (placement included), warms up, times the K steps and prints the line:
+metric, value, unit, higher_is_better, dtype, ms_per_step and what the K steps' own events give (launch_ms, the
+roofline fraction of the timed launches).  `--dump-outputs DIR` also writes what the last timed step computed
+(DIR/power_db.npy: see dump_rows).  Everything else the benchmark measures or checks runs only with `--full`.
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
@@ -14,15 +19,16 @@ is the barrier and the max-reduce of the elapsed time; if RCCL does not come up 
 every rank alike, those move to gloo and config.rendezvous_note says so).
 
 A "step" is one pass of the hot path over the rank's device-resident batch.  Rank 0
-prints ONE JSON line.  At N = 1 the same line also carries:
-  launch_ms            min / median / max of the K timed launches (HIP events between launches)
+prints ONE JSON line, with launch_ms: min / median / max of the K timed launches (HIP events between
+launches).  With `--full`, at N = 1 the same line also carries:
   roofline.measured_copy_GBps / frac_of_measured_copy
                        a no-arithmetic streaming kernel with the same bytes, same buffers, same process
   telemetry            shader/memory clocks and socket power sampled around and during the timed region
   cpu_baseline         the oracle on one core, plus `all_cores` (one worker per CPU this process may use)
   secondary            BASELINE configs 3 and 5 (device resident), the numpy boundary (PCIe inclusive) and
                        the per-row feature reductions — each with its own algorithmic-bytes formula
-`--no-secondary` skips those extra legs.  At N > 1 the only extra leg is `secondary.config5_channels`: one continuous
+  parity_max_rel_err   the timed output against the oracle on sampled frames
+`--no-secondary` skips the secondary legs.  At N > 1 the only extra leg is `secondary.config5_channels`: one continuous
 N = 2^20 channel per GPU (BASELINE.json configs[4]), all ranks at the same time, a few tens of milliseconds.
 """
 from __future__ import annotations
@@ -41,6 +47,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 NFFT = 4096
+MAX_LAUNCHES_PER_CALL = 4096        # sdrk_exec_device_timed_each refuses more in one call
+DUMP_ROWS = 2048                    # --dump-outputs: at most 2048 rows x 4096 float32 = 32 MiB
 ALGO_BYTES_PER_SAMPLE = 12          # 8 B complex64 read + 4 B float32 written
 HBM_PEAK_GBPS = 8000.0              # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 METRIC = "complex64 IQ Msamples/s through windowed FFT+log-PSD, N=4096; % HBM3E peak"
@@ -66,12 +74,32 @@ def parse_args():
                     help="random frames of the timed output checked against the oracle (SURVEY.md §8d: >= 1024)")
     ap.add_argument("--placement-candidates", type=int, default=6,
                     help="output-buffer placements probed for the resident pair (1 = plain allocation).  The level a pair runs at is a "
-                         "lottery (DESIGN.md 4.1): of the 144 pairings probed in rounds 3-5, 3 % (one box) to 22 % (another) were on the "
+                         "lottery (DESIGN.md 4.1): of the 144 pairings probed in rounds 3-5, 3 %% (one box) to 22 %% (another) were on the "
                          "fast level.  Six since round 6 (round 5 drew ten: +15 s of wall time, and the driver's series 0.714 / 0.693 / "
                          "0.706 could not see a gain — the box-to-box spread is larger)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip configs 3/5, the numpy boundary and the feature-reduction legs")
-    return ap.parse_args()
+                    help="with --full: skip configs 3/5, the numpy boundary and the feature-reduction legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: CPU baselines, telemetry, parity against the oracle, the copy "
+                         "probes, the other window and the secondary legs (the --cpu-*, --parity-frames and --no-secondary "
+                         "options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last step computed to DIR/power_db.npy (float32, rank 0's "
+                         "frames; a fixed sample of at most 2048 rows, see dump_rows)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_rows(frames: int):
+    """Frame indices (ascending) whose rows --dump-outputs writes: every frame up to DUMP_ROWS, else the first, the last
+    and a fixed seeded sample between them, so that two builds run with the same arguments dump the same rows."""
+    import numpy as np
+    if frames <= DUMP_ROWS:
+        return np.arange(frames, dtype=np.int64)
+    mid = np.random.default_rng(4096).choice(frames - 2, DUMP_ROWS - 2, replace=False) + 1
+    return np.concatenate([[0], np.sort(mid), [frames - 1]]).astype(np.int64)
 
 
 # ---- CPU baseline (oracle = checker; a reported number, not the target) -----------------------
@@ -722,6 +750,10 @@ def child_command(args, port):
            "--placement-candidates", str(args.placement_candidates), "--cpu-seconds", "0"]
     if args.no_secondary:
         cmd.append("--no-secondary")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd
 
 
@@ -736,7 +768,7 @@ def self_launch(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     tmp = None
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         cpu = cpu_baseline(args.window, args.cpu_seconds)
         if args.cpu_all_cores_seconds > 0:
             cpu["all_cores"] = cpu_baseline_all_cores(args.window, args.cpu_all_cores_seconds)
@@ -784,12 +816,12 @@ def main():
             cpu = json.load(open(handed))
         except Exception:
             cpu = None
-    elif rank == 0 and args.cpu_seconds > 0:
+    elif rank == 0 and args.full and args.cpu_seconds > 0:
         cpu = cpu_baseline(args.window, args.cpu_seconds if solo else min(args.cpu_seconds, 5.0))
         if solo and args.cpu_all_cores_seconds > 0:
             cpu["all_cores"] = cpu_baseline_all_cores(args.window, args.cpu_all_cores_seconds)
     cpu_large = None
-    if solo and not args.no_secondary and args.cpu_seconds > 0 and args.cpu_large_seconds > 0:
+    if solo and args.full and not args.no_secondary and args.cpu_seconds > 0 and args.cpu_large_seconds > 0:
         cpu_large = cpu_baselines_secondary(args.cpu_large_seconds, args.cpu_large_seconds)
 
     import torch  # before libsdrk: one shared HIP runtime in the process (see _ffi.py)
@@ -845,7 +877,7 @@ def main():
     lib = _ffi.lib()
     _ffi.require_device(dev)
     info = _ffi.device_info(dev)
-    tel = Telemetry(info) if rank == 0 else None
+    tel = Telemetry(info) if rank == 0 and args.full else None
 
     frames = args.frames
     first_frame = args.first_frame + rank * frames  # config 4: GPU g owns [g*F, (g+1)*F)
@@ -881,13 +913,27 @@ def main():
         tel.start()
     t0 = time.perf_counter()
     # K steps; HIP events on the stream the kernel runs on, one between every two launches
-    each_ms = plan.exec_device_timed_each(d_in.value, frames, d_out.value, launches=args.steps)
+    each_ms, left = [], args.steps
+    while left:
+        n = min(left, MAX_LAUNCHES_PER_CALL)
+        each_ms += plan.exec_device_timed_each(d_in.value, frames, d_out.value, launches=n)
+        left -= n
     barrier()
     elapsed = time.perf_counter() - t0
     if tel:
         tel.stop()
     after = tel.snapshot() if tel else None
     kernel_ms = float(sum(each_ms))
+
+    # what the last timed step computed, before anything below reuses the row buffer
+    if rank == 0 and args.dump_outputs:
+        picks = dump_rows(frames)
+        rows = np.empty((picks.size, NFFT), dtype=np.float32)
+        for i, f in enumerate(picks):
+            _ffi.check(lib.sdrk_memcpy_d2h(dev, rows[i].ctypes.data_as(ctypes.c_void_p),
+                                           ctypes.c_void_p(d_out.value + int(f) * NFFT * 4), rows[i].nbytes))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "power_db.npy"), rows)
     per_rank = None
     if dist is not None:
         # every rank's own median launch and wall time, so that a straggler (placement level, clocks) shows in the line
@@ -912,7 +958,7 @@ def main():
 
     # parity on this rank's output of the timed launches (oracle = checker only)
     parity, n_checked = 0.0, 0
-    if args.parity_frames > 0:
+    if args.full and args.parity_frames > 0:
         rng = np.random.default_rng(rank)
         picks = np.unique(np.concatenate([[0, frames - 1], rng.integers(0, frames, args.parity_frames)]))
         w = np.hanning(NFFT) if args.window == "hann" else None
@@ -928,14 +974,15 @@ def main():
         mine = torch.tensor([parity, float(first_frame), float(first_frame + frames)], device=red_dev, dtype=torch.float64)
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(everyone, mine, group=grp)
-        per_rank["parity_max_rel_err"] = [float(v[0]) for v in everyone]
         per_rank["frame_range"] = [[int(v[1]), int(v[2])] for v in everyone]     # rank g: [first + g F, first + (g + 1) F)
         per_rank["first_sample_index"] = [int(v[1]) * NFFT for v in everyone]     # >= 2^32 from config 4's rank 1 on: 64-bit frame numbers in the generator
-        parity = max(per_rank["parity_max_rel_err"])
+        if args.full:
+            per_rank["parity_max_rel_err"] = [float(v[0]) for v in everyone]
+            parity = max(per_rank["parity_max_rel_err"])
 
     # the same bytes with no arithmetic, same buffers, same process: the measured-copy ceiling (rank 0)
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             ms = (ctypes.c_float * 10)()
             _ffi.check(lib.sdrk_stream_ceiling_probe(dev, d_in, d_out, frames, 10, ms))
@@ -947,7 +994,7 @@ def main():
     # ... and the guide's reference shape, a 1:1 float4 copy (MI355X_MICROARCH.md: 6.29 TB/s), between the same
     # two buffers: the first 16 GiB of the IQ buffer into the row buffer
     copy11_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             ms = (ctypes.c_float * 10)()
             nbytes = frames * NFFT * 4
@@ -959,7 +1006,7 @@ def main():
     # ... and the same 1:1 copy on a small pair (4 + 2 GiB) allocated beside the resident one, same process: the footprint
     # dependence of the copy ceiling on record (the guide's 6.29 TB/s is a small-footprint figure)
     copy11_small = None
-    if solo and not args.no_secondary and frames * NFFT * 8 >= (8 << 30):
+    if solo and args.full and not args.no_secondary and frames * NFFT * 8 >= (8 << 30):
         try:
             a_s, b_s = ctypes.c_void_p(), ctypes.c_void_p()
             _ffi.check(lib.sdrk_dev_alloc(dev, 4 << 30, ctypes.byref(a_s)))
@@ -980,7 +1027,7 @@ def main():
 
     # the other window of configs[1] on the same buffers (SURVEY.md §8d names Hann and rect); rank 0, N = 1 only
     other_window = None
-    if solo and not args.no_secondary:
+    if solo and args.full and not args.no_secondary:
         try:
             ow = None if args.window != "rect" else "hann"
             with SpectrumPlan(NFFT, window=ow, device=dev) as p2:
@@ -1001,7 +1048,7 @@ def main():
     lib.sdrk_dev_free(dev, d_out)
 
     secondary = None
-    if solo and not args.no_secondary:
+    if solo and args.full and not args.no_secondary:
         secondary = {"config2_other_window": other_window}
         try:
             L = 614_400_000                                       # 10 s @ 61.44 Msps
@@ -1032,7 +1079,7 @@ def main():
             secondary["row_features"] = feature_reductions(lib, _ffi, SpectrumPlan, features, dev)
         except Exception as e:
             secondary["error"] = f"{type(e).__name__}: {e}"
-    elif dist is not None and not args.no_secondary:
+    elif dist is not None and args.full and not args.no_secondary:
         # N > 1: BASELINE.json configs[4] as it is worded — one continuous N = 2^20 channel PER GPU, all at the same
         # time: 256 back-to-back Hann frames from a resident stream -> the device waterfall ring -> max-hold to 4096
         # bins and a host gather every 16 rows (channel seed = 1234 + device).  Every rank runs its channel between
@@ -1122,6 +1169,14 @@ def main():
                 "kernel": "sdrk::fft4096_kernel",
                 "kernel_ms_per_launch": round(launch_ms, 4),
                 "algorithmic_bytes_per_launch": ALGO_BYTES_PER_SAMPLE * frames * NFFT,
+            },
+            "launch_ms": {"min": round(min(each_ms), 4), "median": round(_median(each_ms), 4),
+                          "max": round(max(each_ms), 4), "mean": round(sum(each_ms) / len(each_ms), 4),
+                          "n": len(each_ms), "scope": "rank 0", "series": [round(float(v), 3) for v in each_ms]},
+            "placement": placement,
+        }
+        if args.full:
+            line["roofline"].update({
                 "measured_copy_GBps": None if copy_gbps is None else round(copy_gbps, 1),
                 "frac_of_measured_copy": None if not copy_gbps else round(achieved / copy_gbps, 4),
                 "measured_copy_what": "sdrk_stream_ceiling_probe: 32 KiB read + 16 KiB written per frame, no arithmetic, "
@@ -1131,14 +1186,9 @@ def main():
                 "copy_1to1_what": "sdrk_copy_probe: plain 1:1 copy, 16 B per lane each way, first half of the IQ buffer into "
                                   "the row buffer (read + written bytes / time); MI355X_MICROARCH.md quotes 6.29 TB/s for this shape",
                 "copy_1to1_small_footprint": copy11_small,
-            },
-            "launch_ms": {"min": round(min(each_ms), 4), "median": round(_median(each_ms), 4),
-                          "max": round(max(each_ms), 4), "mean": round(sum(each_ms) / len(each_ms), 4),
-                          "n": len(each_ms), "scope": "rank 0", "series": [round(float(v), 3) for v in each_ms]},
-            "parity_max_rel_err": parity,
-            "parity_frames_checked": n_checked,
-            "placement": placement,
-        }
+            })
+            line["parity_max_rel_err"] = parity
+            line["parity_frames_checked"] = n_checked
         if per_rank is not None:
             line["per_rank"] = per_rank
             line["aggregate_frac_of_n_gpu_peak"] = round(ALGO_BYTES_PER_SAMPLE * value * 1e6 / 1e9 / (world * HBM_PEAK_GBPS), 4)

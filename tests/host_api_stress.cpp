@@ -227,7 +227,10 @@ static void placement_and_misc() {
     CHECK(d_in && d_out && chosen >= 0 && chosen < 3);
     float warm = 0, first = 0, again = 0, kept = 0;
     int launches = 0;
-    CHECK(sdrk_placement_report(&warm, &launches, &first, &again, &kept) == 3 && warm >= 55.0f && launches >= 2 && again > 0 && kept > 0);
+    // the warm-up ends after 60 ms or at its cap of 4000 launches, whichever comes first (the stand-in runtime's launches
+    // are quick enough that a fast host reaches the cap first)
+    CHECK(sdrk_placement_report(&warm, &launches, &first, &again, &kept) == 3 && (warm >= 55.0f || launches == 4000) &&
+          launches >= 2 && again > 0 && kept > 0);
     CHECK(sdrk_dev_free(0, d_in) == SDRK_OK && sdrk_dev_free(0, d_out) == SDRK_OK);
     sdrk_plan* p = nullptr;
     CHECK(sdrk_plan_create(0, 65536, 8, SDRK_WINDOW_HANN, nullptr, 1e-12f, 1, &p) == SDRK_OK);

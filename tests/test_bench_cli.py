@@ -21,7 +21,7 @@ def _args(argv):
 
 def test_child_command_is_the_drivers_launch_line():
     a = _args(["--gpus", "4", "--steps", "7", "--warmup", "2", "--frames", "4096", "--window", "rect", "--no-secondary",
-               "--first-frame", "3145728"])
+               "--first-frame", "3145728", "--full", "--dump-outputs", "out"])
     cmd = bench.child_command(a, 29511)
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in cmd and "--nproc-per-node=4" in cmd
@@ -33,7 +33,9 @@ def test_child_command_is_the_drivers_launch_line():
                       ("--first-frame", "3145728")):                       # the ranks' frame ranges start where the parent was told
         assert tail[tail.index(flag) + 1] == val
     assert tail[tail.index("--cpu-seconds") + 1] == "0"        # the parent owns the CPU baseline
-    assert "--no-secondary" in tail
+    assert "--no-secondary" in tail and "--full" in tail
+    assert tail[tail.index("--dump-outputs") + 1] == os.path.abspath("out")    # the ranks' working directory may differ
+    assert "--full" not in bench.child_command(_args(["--gpus", "4"]), 29511)
 
 
 def test_self_launch_spawns_a_child_and_relays_its_code(monkeypatch):
@@ -49,7 +51,7 @@ def test_self_launch_spawns_a_child_and_relays_its_code(monkeypatch):
     monkeypatch.setattr(subprocess, "call", fake_call)
     monkeypatch.setattr(bench, "cpu_baseline", lambda window, seconds: {"value": 1.0, "cores": 1, "kind": "port"})
     monkeypatch.setattr(bench, "cpu_baseline_all_cores", lambda window, seconds: {"value": 2.0, "cores": 2})
-    a = _args(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    a = _args(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     with pytest.raises(SystemExit) as ex:
         bench.self_launch(a)
     assert ex.value.code == 3
@@ -57,6 +59,30 @@ def test_self_launch_spawns_a_child_and_relays_its_code(monkeypatch):
     assert seen["cpu"] == {"value": 1.0, "cores": 1, "kind": "port", "all_cores": {"value": 2.0, "cores": 2}}
     assert not os.path.exists(seen["env"]["SDRK_BENCH_CPU_BASELINE"])      # removed after the child ended
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_plain_run_has_no_cpu_legs(monkeypatch):
+    """Without --full the parent times no CPU baseline and hands none over."""
+    import subprocess
+    seen = {}
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env=None: seen.update(cmd=cmd, env=env) or 0)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda window, seconds: pytest.fail("CPU baseline in a plain run"))
+    with pytest.raises(SystemExit) as ex:
+        bench.self_launch(_args(["--gpus", "2"]))
+    assert ex.value.code == 0 and "SDRK_BENCH_CPU_BASELINE" not in seen["env"] and "--full" not in seen["cmd"]
+
+
+def test_steps_and_dump_rows():
+    assert _args([]).full is False and _args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        _args(["--steps", "0"])
+    small = bench.dump_rows(100)
+    assert small.tolist() == list(range(100))
+    rows = bench.dump_rows(1 << 20)
+    assert rows.size == bench.DUMP_ROWS and rows[0] == 0 and rows[-1] == (1 << 20) - 1
+    assert (rows[1:] > rows[:-1]).all()                                      # distinct, ascending
+    assert rows.size * bench.NFFT * 4 <= 64 << 20                            # the dump stays within 64 MB
+    assert bench.dump_rows(1 << 20).tolist() == rows.tolist()                # the same rows from run to run
 
 
 def test_self_launch_parent_never_imports_torch():
@@ -68,7 +94,7 @@ def test_self_launch_parent_never_imports_torch():
         "subprocess.call = lambda cmd, env=None: 0\n"
         "bench.cpu_baseline = lambda w, s: {'value': 1.0}\n"
         "bench.cpu_baseline_all_cores = lambda w, s: {'value': 2.0}\n"
-        "sys.argv = ['bench.py', '--gpus', '2']\n"
+        "sys.argv = ['bench.py', '--gpus', '2', '--full']\n"
         "try:\n"
         "    bench.main()\n"
         "except SystemExit as e:\n"

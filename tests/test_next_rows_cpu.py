@@ -196,40 +196,24 @@ def test_streamer_shim_failure_behaviour_matches_reference_traces():
 
 
 def test_streamer_shim_equals_reference_loop_on_random_failure_scripts():
-    """Where the reference is present (the build container): 300 random scripts — good frames, generic exceptions,
-    OSErrors of every errno class the loop distinguishes (9, 10054, 110, 113, others, none), frames the transform
-    rejects, reconnects that succeed on the k-th try or never, starting connected or not — through the reference's
-    own `_stream_data` (driven as oracle/make_golden_streamer.py drives it) and through SpectrumStreamer: the same
-    waits, reconnects and frames in the same order, and the same final state."""
+    """300 random scripts (oracle/make_golden_random.random_scripts) — good frames, generic exceptions, OSErrors of every
+    errno class the loop distinguishes (9, 10054, 110, 113, others, none), frames the transform rejects, reconnects that
+    succeed on the k-th try or never, starting connected or not — through SpectrumStreamer, against what the reference's
+    own `_stream_data` (driven as oracle/make_golden_streamer.py drives it) did with them
+    (tests/golden/ref_streamer_random_scripts.json): the same waits, reconnects and frames in the same order, and the
+    same final state."""
+    import json
     import logging
     import os
-    import sys
-    from unittest.mock import MagicMock
-    ref_root = os.environ.get("SDRK_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_root, "app", "sdr")):
-        pytest.skip("the reference is not present on this machine")
-    from oracle import make_golden_streamer as G
-    sys.modules.setdefault("adi", MagicMock())
-    sys.path.insert(0, ref_root)
-    try:
-        import app.sdr.streamer as module
-    finally:
-        while ref_root in sys.path:
-            sys.path.remove(ref_root)
-    rng = np.random.default_rng(83)
-    steps = ["ok", {"raise": "Exception"}, {"raise": "ValueError"}, {"raise": "RuntimeError"}, {"raise": "OSError"},
-             {"raise": "OSError", "errno": 9}, {"raise": "OSError", "errno": 10054}, {"raise": "OSError", "errno": 110},
-             {"raise": "OSError", "errno": 113}, {"raise": "OSError", "errno": 5}, {"return": "garbage"}]
-    weights = np.array([6, 2, 1, 1, 1, 1, 1, 2, 1, 1, 1], dtype=float)
+    from oracle import make_golden_random as R
+    from tests.conftest import GOLDEN
+    want = json.load(open(os.path.join(GOLDEN, "ref_streamer_random_scripts.json")))["traces"]
+    scripts = R.random_scripts()
+    assert len(want) == len(scripts) == 300
     logging.disable(logging.CRITICAL)
     try:
-        for c in range(300):
-            sc = {"name": f"random_{c}",
-                  "rx": [steps[i] for i in rng.choice(len(steps), size=int(rng.integers(1, 14)), p=weights / weights.sum())],
-                  "reconnect": [bool(b) for b in rng.random(int(rng.integers(0, 6))) < 0.4],
-                  "start_connected": bool(rng.random() < 0.85)}
-            want = G.run_scenario(module, module.SDRDataStreamer, sc)
-            assert _replay(sc) == want, sc
+        for sc, trace in zip(scripts, want):
+            assert _replay(sc) == trace, sc
     finally:
         logging.disable(logging.NOTSET)
 
@@ -280,62 +264,28 @@ def test_oracle_row_features_match_reference_on_corner_rows(golden):
         assert np.array_equal(f["peak_idx"], g[f"{k}/peak_idx"]), k
 
 
-def test_oracle_equals_reference_helpers_on_random_rows():
-    """Where the reference is present (the build container; it never travels), the oracle's row_features is run next to
-    the reference's own helpers on 400 random rows of the kinds tools/stress_features.py and stress_fused.py use
+def test_oracle_equals_reference_helpers_on_random_rows(golden):
+    """The oracle's row_features on 400 random rows of the kinds tools/stress_features.py and stress_fused.py use
     (noise, ties, tones, cliffs, far-off percentiles, -inf bins, constant tails, ramps, values past 385 dB; lengths
-    16 ... 20000): every scalar and every peak list identical.  This is what lets the GPU stress tools use the oracle
-    as their checker for thousands of rows."""
-    import os
-    import sys
+    16 ... 20000: oracle/make_golden_random.random_rows), against what the reference's own helpers returned for them
+    (tests/golden/ref_classifier_random_rows.npz): every scalar and every peak list identical.  This is what lets the
+    GPU stress tools use the oracle as their checker for thousands of rows."""
     import warnings
-    ref_root = os.environ.get("SDRK_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_root, "app", "processing")):
-        pytest.skip("the reference is not present on this machine")
-    sys.path.insert(0, ref_root)
-    try:
-        from app.processing import classifier as C
-    finally:
-        sys.path.remove(ref_root)
-    rng = np.random.default_rng(400)
-    kinds = ["noise", "quantised", "tone", "steps", "wide", "holes", "const_tail", "ramp", "huge", "nans"]
-    for c in range(400):
-        n = int(rng.choice([16, 64, 100, 257, 1000, 2048, 4096, 4097, 8192, 20000]))
-        kind = kinds[c % len(kinds)]
-        x = (rng.standard_normal(n) * rng.uniform(1, 9) + rng.uniform(-120, 60)).astype(np.float32)
-        if kind == "quantised":
-            x = (np.round(x * 2) / 2).astype(np.float32)
-        elif kind == "tone":
-            x[rng.integers(0, n, 3)] += np.float32(90)
-        elif kind == "steps":
-            x[: max(1, n // 5 + int(rng.integers(-3, 4)))] -= np.float32(150)
-        elif kind == "wide":
-            x[rng.random(n) < 0.8] += np.float32(70)
-        elif kind == "holes":
-            x[rng.random(n) < 0.05] = -np.inf
-        elif kind == "const_tail":
-            x[n // 2:] = x[0]
-        elif kind == "ramp":
-            x = np.linspace(-80, 5, n).astype(np.float32) + (rng.standard_normal(n) * 0.01).astype(np.float32)
-        elif kind == "huge":
-            x[rng.random(n) < 0.3] += np.float32(rng.uniform(400, 3000))
-        elif kind == "nans":
-            x[rng.integers(0, n, int(rng.integers(1, 4)))] = np.nan
-        freqs = cpu_ref.freq_axis(n, 20e6, 2.4e9)
+    from oracle import make_golden_random as R
+    g = golden["ref_classifier_random_rows"]
+    scalars, peaks, off = g["scalars"], g["peaks_concat"], g["peaks_off"]
+    rows = R.random_rows()
+    assert scalars.shape == (len(rows), 9) and off.size == len(rows) + 1
+    for c, (kind, x) in enumerate(rows):
+        n = x.shape[0]
+        freqs = cpu_ref.freq_axis(n, *R.ROW_FS_FC)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            nf = C._estimate_noise_floor(x)
-            snr = float(np.max(x) - nf)
-            thr = max(nf + 5.0, np.max(x) - 0.9 * snr + 5.0)
-            pk = C._find_peaks(x, threshold_db=thr, min_distance_bins=max(3, len(x) // 300))
-            ref = np.array([nf, snr, C._occupied_bandwidth(freqs, x, 3), C._occupied_bandwidth(freqs, x, 10),
-                            C._occupied_bandwidth(freqs, x, 20), C._spectral_flatness(x), C._spectral_kurtosis(x), float(thr),
-                            C._peak_spacing_std(freqs, pk)])
             f = cpu_ref.row_features(freqs, x)
         got = np.array([f["noise_floor_db"], f["snr_db"], f["bandwidth_hz_3db"], f["bandwidth_hz_10db"], f["bandwidth_hz_20db"],
                         f["spectral_flatness"], f["spectral_kurtosis"], f["adaptive_threshold_db"], f["peak_spacing_std_hz"]])
-        assert np.array_equal(got, ref, equal_nan=True), (c, kind, n, got, ref)
-        assert np.array_equal(f["peak_idx"], np.array(pk, dtype=np.int64)), (c, kind, n)
+        assert np.array_equal(got, scalars[c], equal_nan=True), (c, kind, n, got, scalars[c])
+        assert np.array_equal(f["peak_idx"], peaks[off[c]:off[c + 1]]), (c, kind, n)
 
 
 def test_oracle_welch_equals_mlab_psd_for_random_segmentations():

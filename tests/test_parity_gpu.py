@@ -2047,7 +2047,7 @@ def test_bench_self_launches_four_ranks_on_the_one_gpu():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
            "--frames", str(F), "--first-frame", str(first), "--cpu-seconds", "0", "--parity-frames", "24",
-           "--placement-candidates", "1"]
+           "--placement-candidates", "1", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -2091,7 +2091,7 @@ def test_bench_prints_exactly_one_json_line(launcher):
     from tests.conftest import REPO
     bench = os.path.join(REPO, "bench.py")
     tail = ["--steps", "2", "--warmup", "1", "--frames", "8192", "--no-secondary", "--cpu-seconds", "0",
-            "--parity-frames", "16", "--placement-candidates", "1"]
+            "--parity-frames", "16", "--placement-candidates", "1", "--full"]
     env = dict(os.environ)
     env.pop("RANK", None)
     if launcher == "plain":
@@ -2114,3 +2114,44 @@ def test_bench_prints_exactly_one_json_line(launcher):
         assert backend == "nccl" and "rendezvous_note" not in line["config"]
     else:
         assert backend == "gloo" and "did not come up on any rank" in line["config"]["rendezvous_note"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps launches, more than one timing call takes (4096) included, prints
+    the headline line without the --full legs, and --dump-outputs writes the sampled rows of the last timed step: the
+    oracle's rows on the generator's frames, and the same file from a second run with other step counts."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from tests.conftest import REPO
+    from sdr_iq_visualizer_amd import synth
+    frames = 8192
+    env = dict(os.environ)
+    env.pop("RANK", None)
+    dumps = []
+    for steps, warmup in ((4100, 1), (2, 0)):
+        out_dir = tmp_path / f"steps{steps}"
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--frames", str(frames), "--placement-candidates", "1", "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout[:400]
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["launch_ms"]["n"] == steps and line["higher_is_better"] is True
+        assert line["unit"] == "Msamples/s" and line["dtype"] == "f32" and line["metric"] == bench.METRIC
+        assert line["value"] == pytest.approx(frames * 4096 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+        for key in ("cpu_baseline", "secondary", "telemetry", "parity_max_rel_err"):
+            assert key not in line, key
+        assert "measured_copy_GBps" not in line["roofline"]
+        assert sorted(os.listdir(out_dir)) == ["power_db.npy"]
+        assert os.path.getsize(out_dir / "power_db.npy") <= 64 << 20
+        dumps.append(np.load(out_dir / "power_db.npy"))
+    rows = bench.dump_rows(frames)
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (rows.size, 4096)
+    assert np.array_equal(dumps[0], dumps[1])
+    x = synth.synth_iq(1234, 0, frames, 4096)[rows]
+    ref = cpu_ref.spectrum_db(x, window=np.hanning(4096))
+    assert float(peak_rel_err(dumps[0], ref).max()) <= 1e-5

@@ -15,7 +15,7 @@ cd "$ROOT"
 # (One gpurun call is limited to 20 minutes; the two parts are two calls.  Unset: both.)
 PART=${SDRK_COLLECT_PART:-AB}
 case $PART in *A*)
-echo "== bench (full line)"; python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+echo "== bench (full line)"; python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 echo "== profiles"; bash tools/profile_round.sh $TAG > "$OUT/profile_round.log" 2>&1; cp gpurun_out/prof_$TAG/summary.json "$OUT/rocprof_summary.json"; cp gpurun_out/prof_$TAG/pmc_fetch_write_rows.csv "$OUT/" 2>/dev/null
 for t in bench cfg3 cfg3tiled cfg5 n16384 n2p21 n2p22 feat; do cp gpurun_out/prof_$TAG/${t}_trace/*/*kernel_stats.csv "$OUT/${t}_kernel_stats.csv" 2>/dev/null; done
 cp gpurun_out/prof_$TAG/cfg3_trace_vs_events.json gpurun_out/prof_$TAG/cfg3tiled_trace_vs_events.json gpurun_out/prof_$TAG/cfg5_trace_vs_events.json gpurun_out/prof_$TAG/cfg3_steady.json gpurun_out/prof_$TAG/cfg3tiled_steady.json gpurun_out/prof_$TAG/cfg5_steady.json "$OUT/" 2>/dev/null
@@ -37,11 +37,11 @@ summ() { python3 -c "
 import json,sys
 l=json.loads(sys.stdin.read()); t=l['telemetry']
 print('%.4f  %.4f  %.4f  %.4f  %7.1f  %.4f  sclk_after %s  probe_ms %s chosen %d' % (l['launch_ms']['median'], l['launch_ms']['min'], l['launch_ms']['max'], l['roofline']['frac'], l['roofline']['measured_copy_GBps'], l['roofline']['frac_of_measured_copy'], t['after']['sclk_mhz'], l['placement']['probe_ms'], l['placement']['chosen']))"; }
-{ echo "# python bench.py --no-secondary --cpu-seconds 0 --parity-frames 0   ($NP processes; placement: 6 candidates)";
+{ echo "# python bench.py --full --no-secondary --cpu-seconds 0 --parity-frames 0   ($NP processes; placement: 6 candidates)";
   echo "# launch_ms median  min  max  frac_of_8TB/s  copy_GB/s  kernel/copy";
-  for i in $(seq $NP); do python3 bench.py --no-secondary --cpu-seconds 0 --parity-frames 0 2>/dev/null | tail -1 | summ; done; } > "$OUT/placement_runs.txt"
+  for i in $(seq $NP); do python3 bench.py --full --no-secondary --cpu-seconds 0 --parity-frames 0 2>/dev/null | tail -1 | summ; done; } > "$OUT/placement_runs.txt"
 { echo "# the same with --placement-candidates 1 (plain alloc(in); alloc(out)), $NQ processes";
-  for i in $(seq $NQ); do python3 bench.py --no-secondary --cpu-seconds 0 --parity-frames 0 --placement-candidates 1 2>/dev/null | tail -1 | summ; done; } > "$OUT/plain_alloc_runs.txt"
+  for i in $(seq $NQ); do python3 bench.py --full --no-secondary --cpu-seconds 0 --parity-frames 0 --placement-candidates 1 2>/dev/null | tail -1 | summ; done; } > "$OUT/plain_alloc_runs.txt"
 echo "== N=65536: the persistent launch against the two tiled launches (4096 packed frames, then config 3; Hann), and their crossover"
 { python3 tools/fused_probe.py 4096 65536 hann; python3 tools/fused_probe.py 18749 32768 hann; } > "$OUT/fused64k_vs_tiled.log" 2>&1
 { python3 experiments/fused64k_policy/crossover.py 32768; python3 experiments/fused64k_policy/crossover.py 65536; } > "$OUT/fused64k_crossover.log" 2>&1
@@ -78,14 +78,14 @@ hipcc --offload-arch=gfx950 -O3 -o sdr-iq-visualizer_amd/build_tools/pcie_probe 
 fi
 echo "== per-row measurements at the numpy boundary"; python3 tools/feat_host_probe.py > "$OUT/feat_host_probe.log" 2>&1; tail -2 "$OUT/feat_host_probe.log"
 echo "== bench.py under torch.distributed.run, one rank (the nccl group formed and proven)"
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29641 bench.py --gpus 1 --steps 5 --warmup 1 --no-secondary --cpu-seconds 0 > "$OUT/bench_torchrun1_nccl.json" 2> "$OUT/bench_torchrun1_nccl.err"; echo "rc=$? $(wc -l < "$OUT/bench_torchrun1_nccl.json") line(s)"
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29641 bench.py --gpus 1 --steps 5 --warmup 1 --full --no-secondary --cpu-seconds 0 > "$OUT/bench_torchrun1_nccl.json" 2> "$OUT/bench_torchrun1_nccl.err"; echo "rc=$? $(wc -l < "$OUT/bench_torchrun1_nccl.json") line(s)"
 echo "== bench.py --gpus 2, self-launched (rehearsal on one GPU: gloo rendezvous, ranks share the device)"
-python3 bench.py --gpus 2 --steps 3 --warmup 1 --frames 262144 --cpu-seconds 3 --cpu-all-cores-seconds 2 2> "$OUT/bench_gpus2_rehearsal.err" | grep '^{' > "$OUT/bench_gpus2_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus2_rehearsal.json") bytes"
+python3 bench.py --gpus 2 --steps 3 --warmup 1 --full --frames 262144 --cpu-seconds 3 --cpu-all-cores-seconds 2 2> "$OUT/bench_gpus2_rehearsal.err" | grep '^{' > "$OUT/bench_gpus2_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus2_rehearsal.json") bytes"
 echo "== bench.py --gpus 4, self-launched on the one GPU (the control path of configs[3] / [4]; the -m gpu suite runs the same)"
-python3 bench.py --gpus 4 --steps 3 --warmup 1 --frames 65536 --first-frame 3145728 --cpu-seconds 0 --placement-candidates 1 2> "$OUT/bench_gpus4_rehearsal.err" | grep '^{' > "$OUT/bench_gpus4_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus4_rehearsal.json") bytes"
+python3 bench.py --gpus 4 --steps 3 --warmup 1 --full --frames 65536 --first-frame 3145728 --cpu-seconds 0 --placement-candidates 1 2> "$OUT/bench_gpus4_rehearsal.err" | grep '^{' > "$OUT/bench_gpus4_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus4_rehearsal.json") bytes"
 echo "== bench.py --gpus 5, self-launched on the one GPU: the most ranks this pool's process guard admits beside the launcher (6 processes on"
 echo "   the card; a 6-rank rehearsal was killed by it in round 6: profiles/r06/bench_gpus7_refused.txt).  frames 4096 per rank as the driver's"
 echo "   8-GPU command line would be rehearsed; first frame 3 x 2^20 so that every rank's samples lie past index 2^32"
-python3 bench.py --gpus 5 --frames 4096 --first-frame 3145728 --steps 3 --warmup 1 --cpu-seconds 0 --placement-candidates 1 2> "$OUT/bench_gpus5_rehearsal.err" | grep '^{' > "$OUT/bench_gpus5_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus5_rehearsal.json") bytes"
+python3 bench.py --gpus 5 --full --frames 4096 --first-frame 3145728 --steps 3 --warmup 1 --cpu-seconds 0 --placement-candidates 1 2> "$OUT/bench_gpus5_rehearsal.err" | grep '^{' > "$OUT/bench_gpus5_rehearsal.json"; echo "rc=$? $(wc -c < "$OUT/bench_gpus5_rehearsal.json") bytes"
 echo "== one-frame host call"; python3 tools/small_call_probe.py > "$OUT/small_call_probe.log" 2>&1; cat "$OUT/small_call_probe.log"
 echo "== gpu tests"; python3 -m pytest tests -m gpu -q > "$OUT/pytest_gpu.log" 2>&1; tail -2 "$OUT/pytest_gpu.log"

@@ -16,8 +16,8 @@ run() {  # name, rocprof args..., -- program args
     echo "== $name" >&2
     rocprofv3 "$@" > "$OUT/$name.stdout" 2> "$OUT/$name.stderr" || echo "rocprofv3 $name failed rc=$?" >&2
 }
-BENCH_SHORT="--steps 3 --warmup 1 --cpu-seconds 0 --parity-frames 0 --no-secondary"
-run bench_trace --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$ROOT/bench.py" --no-secondary --cpu-seconds 0
+BENCH_SHORT="--full --steps 3 --warmup 1 --cpu-seconds 0 --parity-frames 0 --no-secondary"
+run bench_trace --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$ROOT/bench.py" --full --no-secondary --cpu-seconds 0
 run bench_fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/bench_fetch" -- python3 "$ROOT/bench.py" $BENCH_SHORT
 run bench_write --pmc WRITE_SIZE --output-format csv -d "$OUT/bench_write" -- python3 "$ROOT/bench.py" $BENCH_SHORT
 # BASELINE configs 3 and 5, and the frame lengths DESIGN.md names as the slowest passes left (not BASELINE configs)

@@ -91,7 +91,7 @@ def main(root):
                 rec["WRITE_SIZE_KB_mean"] = round(wr[k]["mean_KB"], 3)
                 rec["write_bytes_per_dispatch"] = round(wr[k]["mean_KB"] * 1024)
             kernels[k] = rec
-        if tag == "bench":       # python3 bench.py --no-secondary --cpu-seconds 0: 20 timed steps (the default --steps)
+        if tag == "bench":       # python3 bench.py --full --no-secondary --cpu-seconds 0: 20 timed steps (the default --steps)
             for k in kernels:
                 if k.startswith("fft4096_kernel"):
                     tl = timed_launches(f"{root}/{tag}_trace", "fft4096_kernel", 20)
