@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define SDRK_VERSION 500 /* 0.5.0: every addition to this ABI bumps it; _ffi.py refuses a library of another version */
+#define SDRK_VERSION 500 /* 0.5.0: _ffi.py refuses a library of another version.  A change to an existing entry point bumps it;
+                           * additions (new symbols) do not: _ffi.py checks that every symbol it declares is present. */
 
 typedef enum sdrk_status {
     SDRK_OK = 0,
@@ -221,6 +222,32 @@ int sdrk_exec_device_timed(sdrk_plan* plan, const void* d_iq_c64, size_t n_frame
  * (events between consecutive launches; each_ms holds `launches` floats). */
 int sdrk_exec_device_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_frames,
                                 size_t frame_stride, float* d_out_db, int launches, float* each_ms);
+
+/* ---- double precision: the reference's own dtypes ----------------------------
+ * app/sdr/streamer.py:119-121 computes in float64 on the complex128 samples pyadi-iio delivers:
+ *     out_db[k] = 20*log10( | fftshift( fft( w * x ) ) |[k] + eps )     (float64, complex128 in)
+ * in that order (abs, + eps, log10, * 20), with library hypot / log10 / sincospi in double on the device.
+ * An f64 plan is an ordinary sdrk_plan: sdrk_plan_destroy, _sync, _nfft and _device take it.  It serves ONLY the
+ * _f64 entry points below; every float32 entry point (exec, Welch, features, waterfall) given an f64 plan returns
+ * SDRK_ERR_INVALID, and so does an _f64 entry point given a float32 plan.
+ * nfft: powers of two 2 ... 2^SDRK_MAX_LOG2_NFFT (other lengths: SDRK_ERR_UNSUPPORTED).  window: nfft doubles for
+ * SDRK_WINDOW_CUSTOM; SDRK_WINDOW_HANN is numpy.hanning(nfft) in float64.  eps >= 0 (0: exact zeros give -inf).
+ * Layout rules as sdrk_exec_host / sdrk_exec_device, with 16-byte samples (interleaved float64 I,Q) and 8-byte rows. */
+/* streamer.py:119-121 */
+int sdrk_plan_create_f64(int device, int nfft, size_t max_batch, int window_kind,
+                         const double* window, double eps, int shift, sdrk_plan** out);
+/* streamer.py:119-121 (which arithmetic a plan does): 32 (sdrk_plan_create*) or 64 (sdrk_plan_create_f64) */
+int sdrk_plan_precision(const sdrk_plan* plan);
+/* streamer.py:119-121, host in / host out, any batch in bounded device memory (pageable or pinned caller arrays) */
+int sdrk_exec_host_f64(sdrk_plan* plan, const void* iq_c128, size_t n_frames, size_t frame_stride, double* out_db);
+/* streamer.py:119 alone: complex128 fft(w*x), fftshifted if the plan shifts */
+int sdrk_exec_fft_host_f64(sdrk_plan* plan, const void* iq_c128, size_t n_frames, size_t frame_stride, void* out_c128);
+/* streamer.py:119-121, device in / device out, asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_f64(sdrk_plan* plan, const void* d_iq_c128, size_t n_frames, size_t frame_stride,
+                         double* d_out_db, void* stream);
+/* streamer.py:119-121, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_f64_timed_each(sdrk_plan* plan, const void* d_iq_c128, size_t n_frames, size_t frame_stride,
+                                    double* d_out_db, int launches, float* each_ms);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

@@ -124,6 +124,13 @@ SYMBOLS = [
     ("sdrk_waterfall_read_decimated", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_size_t)]),
     ("sdrk_waterfall_maxhold16_rows", c_int, [c_void_p]),
     ("sdrk_waterfall_clear", c_int, [c_void_p]),
+    # double precision (the reference's complex128 -> float64, streamer.py:119-121)
+    ("sdrk_plan_create_f64", c_int, [c_int, c_int, c_size_t, c_int, c_void_p, c_double, c_int, POINTER(c_void_p)]),
+    ("sdrk_plan_precision", c_int, [c_void_p]),
+    ("sdrk_exec_host_f64", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_f64", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_f64", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrk_exec_device_f64_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
 ]
 
 _lib = None

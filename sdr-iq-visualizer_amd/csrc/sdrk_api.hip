@@ -2,7 +2,8 @@
 // device staging, the pinned host pipeline, the waterfall ring, error reporting.
 // All compute is in the gfx950 kernels (fft4096.hip, fft_lds.hip, fft_tiled2.hip,
 // fft_small.hip, bluestein.hip, fft_fused64k.hip, row_features.hip, aux_kernels.hip);
-// there is no host fallback anywhere in this file.
+// there is no host fallback anywhere in this file.  The double-precision entry points are in sdrk_f64.hip; they reach the
+// plan object and the numpy-boundary pipeline here through plan_internal.h.
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
@@ -23,6 +24,11 @@
 
 #include "host_pool.h"
 #include "kernels.h"
+#include "plan_internal.h"
+
+using sdrk_host::HOST_SLOTS;
+using sdrk_host::HostSlot;
+using sdrk_host::HostIo;
 
 namespace {
 
@@ -90,74 +96,6 @@ float2 twiddle(double m, double n) {
 
 }  // namespace
 
-namespace {
-constexpr int HOST_SLOTS = 3;
-struct HostSlot {
-    void *h_in = nullptr, *h_out = nullptr;   // pinned
-    void *d_in = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
-    hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_done = nullptr;
-    // the chunk in flight in this slot (busy == true): where its rows go once ev_done has fired
-    // (user_out == nullptr: the rows were DMA'd straight into the caller's pinned array)
-    bool busy = false;
-    void* user_out = nullptr;
-    size_t out_bytes = 0;
-};
-}  // namespace
-
-struct sdrk_plan {
-    int device = 0;
-    int nfft = 0;
-    size_t max_batch = 0;
-    float eps = 1e-12f;
-    int shift = 1;
-    int num_cus = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float* d_window = nullptr;     // nfft floats, or nullptr for rectangular
-    float2* d_twiddle = nullptr;   // W_min(nfft,4096)^m
-    float2* d_scratch = nullptr;   // large plans
-    size_t scratch_frames = 0;
-    void* d_in = nullptr;          // whole-stream staging (Welch PSD, waterfall append from host IQ); only grows
-    size_t in_cap = 0;
-    void* d_out = nullptr;
-    size_t out_cap = 0;
-    void* d_feat = nullptr;          // per-row feature results of sdrk_frame_features_host (only grows)
-    size_t feat_cap = 0;
-    float2* d_tw_2p = nullptr;       // two-pass tiled plans (fft_tiled2.hip)
-    bool tiled2 = false;
-    // overlapped form of the two-pass plans: row pass of chunk i on stream2 beside the col pass of chunk i + 1
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_col[2] = {nullptr, nullptr}, ev_row[2] = {nullptr, nullptr}, ev_fork = nullptr;
-    int col_cus = 0, row_cus = 0;    // 0: serial form
-    // sdrk_exec_host pipeline: HOST_SLOTS chunks in flight, each with pinned host and device staging
-    HostSlot slot[HOST_SLOTS];
-    float staging_probe_ms[HOST_SLOTS * 3] = {};   // SDRK_PLAN_TUNE_STAGING: the transform over each candidate pairing
-    int staging_probe_n = 0;
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    // non-power-of-two lengths (bluestein.hip): inner power-of-two plan of size blu_m
-    sdrk_plan* blu_inner = nullptr;
-    int blu_m = 0;
-    float2* d_blu_chirp = nullptr;   // c[n] = exp(+i pi n^2 / N), n < N
-    float2* d_blu_bspec = nullptr;   // FFT_M(b)
-    float2* d_blu_a = nullptr;       // work buffers: blu_frames * M complex64 each
-    float2* d_blu_b = nullptr;
-    size_t blu_frames = 0;
-    // small-call fast path of sdrk_exec_host: pinned, device-mapped staging the kernel reads and
-    // writes directly over PCIe (no DMA-engine copies for a 32 KiB frame)
-    void* h_small_in = nullptr;
-    void* h_small_out = nullptr;
-    uint32_t* h_small_flag = nullptr;   // completion word the stream writes behind a small call
-    void* d_small_flag = nullptr;
-    uint32_t small_seq = 0;
-    // N = 65536 fused path (fft_fused64k.hip).  fused64k: every launch (SDRK_PLAN_FUSED64K); fused_auto: launches of at least
-    // FUSED_AUTO_MIN_FRAMES frames (the default for nfft = 65536), until one reports a failed hand-over (fused_broken, latched).
-    bool fused64k = false, fused_auto = false, fused_broken = false;
-    void* d_fused_ring = nullptr;
-    unsigned* d_fused_ctrl = nullptr;
-    unsigned* h_fused_err = nullptr;   // pinned mailbox: error word of the last launches
-    unsigned fused_launches = 0, fused_pending = 0;
-};
 constexpr size_t SMALL_IN_BYTES = 256 << 10;   // calls up to this much input take the zero-copy path
 constexpr size_t HOST_CHUNK_BYTES = 16 << 20;  // target input bytes per pipelined chunk of sdrk_exec_host
 constexpr size_t ZERO_COPY_MAX_BYTES = 32 << 20;  // calls up to this much input skip the DMA engines (see exec_host_common)
@@ -278,6 +216,7 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
 // d_mip / mip_written: see LaunchArgs (kernels.h) — *mip_written tells whether the launch wrote the by-16 companion rows.
 int plan_launch(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
                 int epilogue, hipStream_t stream, float* d_mip = nullptr, bool* mip_written = nullptr, const EpiArgs* epi = nullptr) {
+    if (p->precision != 32) return fail(SDRK_ERR_INVALID, "float32 transform requested of a float64 plan");
     RoctxRange range(p, n_frames, frame_stride, epilogue);
     if (mip_written) *mip_written = false;
     return plan_launch_impl(p, d_iq, n_frames, frame_stride, d_out, epilogue, stream, d_mip, mip_written, epi);
@@ -431,9 +370,18 @@ int fused_check(sdrk_plan* p) {
     return SDRK_OK;
 }
 
+// A plan serves the entry points of its own precision only (sdrk_plan_create: float32; sdrk_plan_create_f64: float64).
+int check_precision(const sdrk_plan* p, int precision) {
+    if (p->precision == precision) return SDRK_OK;
+    return fail(SDRK_ERR_INVALID, "this is a float%d plan (sdrk_plan_create%s) and the call is a float%d entry point%s",
+                p->precision, p->precision == 64 ? "_f64" : "", precision,
+                precision == 64 ? " (sdrk_*_f64)" : ": use the sdrk_*_f64 entry points");
+}
+
 int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride,
-                    const void* out) {
+                    const void* out, int precision = 32) {
     if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
+    if (int st = check_precision(p, precision); st != SDRK_OK) return st;
     if (n_frames == 0) return SDRK_OK;
     if (!in || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
     if (frame_stride == 0 && n_frames > 1)
@@ -625,9 +573,9 @@ int tune_staging(sdrk_plan* p) {
 // memory into a pinned slot, then H2D (copy stream) -> transform (plan stream) -> D2H (copy stream) run
 // asynchronously, chained by events, while the host stages the next chunk and drains finished ones.
 // H2D of chunk c+1 overlaps D2H of chunk c (PCIe is full duplex) and both overlap the staging memcpys.
-int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out,
-                     int epilogue) {
-    int st = check_exec_args(p, iq, n_frames, frame_stride, out);
+// Element sizes, the launch and the kernels that may read host memory themselves come from `io` (float32 and float64 plans).
+int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io) {
+    int st = check_exec_args(p, iq, n_frames, frame_stride, out, io.precision);
     if (st != SDRK_OK || n_frames == 0) return st;
     if (n_frames > p->max_batch)
         return fail(SDRK_ERR_INVALID, "n_frames %zu exceeds the plan's max_batch %zu", n_frames,
@@ -635,8 +583,9 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
     HIP_TRY(hipSetDevice(p->device));
     const size_t nfft = (size_t)p->nfft;
     const size_t in_samples = (n_frames - 1) * frame_stride + nfft;
-    const size_t in_bytes = in_samples * sizeof(float2);
-    const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+    const size_t in_elem = io.in_elem, out_elem = io.out_elem;
+    const int epilogue = io.epilogue;
+    const size_t in_bytes = in_samples * in_elem;
     const size_t out_bytes = n_frames * nfft * out_elem;
     if (in_bytes <= SMALL_IN_BYTES && out_bytes <= SMALL_IN_BYTES && p->nfft <= 4096 && !p->blu_inner) {
         if (!p->h_small_in) {
@@ -657,7 +606,7 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
         HIP_TRY(hipHostGetDevicePointer(&d_si, p->h_small_in, 0));
         HIP_TRY(hipHostGetDevicePointer(&d_so, p->h_small_out, 0));
         memcpy(p->h_small_in, iq, in_bytes);
-        st = plan_launch(p, d_si, n_frames, frame_stride, d_so, epilogue, p->stream);
+        st = io.launch(p, d_si, n_frames, frame_stride, d_so, epilogue, p->stream);
         if (st != SDRK_OK) return st;
         // Completion: the stream writes a sequence number into mapped host memory behind the kernel and the caller
         // polls it — for a 10 us job the wake-up path of hipStreamSynchronize costs as much as the job.  Falls back
@@ -686,14 +635,14 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
     }
     // frames per chunk: ~HOST_CHUNK_BYTES of input, but at least 4 chunks per call when the call is big
     // enough for the overlap to matter, and never less than one frame
-    const size_t stride_bytes = (frame_stride ? frame_stride : 1) * sizeof(float2);
+    const size_t stride_bytes = (frame_stride ? frame_stride : 1) * in_elem;
     size_t target = HOST_CHUNK_BYTES;
     if (in_bytes / 4 < target) target = in_bytes / 4 > ((size_t)1 << 20) ? in_bytes / 4 : ((size_t)1 << 20);
     size_t per = target / stride_bytes;
     if (per > target / (nfft * out_elem)) per = target / (nfft * out_elem);   // heavily overlapped frames: bound the rows too
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
-    const size_t chunk_in = ((per - 1) * frame_stride + nfft) * sizeof(float2);
+    const size_t chunk_in = ((per - 1) * frame_stride + nfft) * in_elem;
     const size_t chunk_out = per * nfft * out_elem;
     sdrk::CopyPool& pool = sdrk::CopyPool::get();
     HostTrace tr;
@@ -706,15 +655,16 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
     // Caller arrays in pinned memory (sdrk_host_alloc / sdrk_host_register) are not staged: the copy engines read
     // and write them directly.  Decided per side.
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
-    const bool zero_copy = p->nfft <= 16384 && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES &&
+    const bool zero_copy = p->nfft <= io.zero_copy_max_nfft && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES &&
                            !in_pinned && !out_pinned;
-    if (in_pinned && out_pinned && p->nfft <= 16384 && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES) {
+    if (in_pinned && out_pinned && p->nfft <= io.zero_copy_max_nfft && !p->blu_inner && frame_stride >= nfft &&
+        in_bytes <= ZERO_COPY_MAX_BYTES) {
         // both arrays pinned, a call small enough that the link's latency matters more than its last 10 %: ONE launch
         // that reads the caller's frames and writes the caller's rows over PCIe — no staging, no copy engine, no chunks
         void *d_src = nullptr, *d_dst = nullptr;
         if (hipHostGetDevicePointer(&d_src, const_cast<void*>(iq), 0) == hipSuccess &&
             hipHostGetDevicePointer(&d_dst, out, 0) == hipSuccess) {
-            st = plan_launch(p, d_src, n_frames, frame_stride, d_dst, epilogue, p->stream);
+            st = io.launch(p, d_src, n_frames, frame_stride, d_dst, epilogue, p->stream);
             if (st != SDRK_OK) return st;
             HIP_TRY(hipStreamSynchronize(p->stream));
             return fused_check(p);
@@ -726,13 +676,13 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
     for (size_t f0 = 0; f0 < n_frames; f0 += per, ++c) {
         HostSlot& s = p->slot[c % HOST_SLOTS];
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
-        const size_t cin = ((nf - 1) * frame_stride + nfft) * sizeof(float2);
+        const size_t cin = ((nf - 1) * frame_stride + nfft) * in_elem;
         const size_t cout = nf * nfft * out_elem;
         st = slot_retire(s, tr);                               // chunk c - HOST_SLOTS: rows out, slot free
         if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);
         if (st != SDRK_OK) { slots_abandon(p); return st; }
         const double t0 = tr.on ? HostTrace::now() : 0;
-        const void* src = static_cast<const float2*>(iq) + f0 * frame_stride;
+        const void* src = static_cast<const char*>(iq) + f0 * frame_stride * in_elem;
         if (!in_pinned) {
             pool.copy(s.h_in, src, cin);
             src = s.h_in;
@@ -743,7 +693,7 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
         if (zero_copy) {
             // the transform reads the pinned chunk and writes the pinned rows itself, over PCIe: no DMA-engine
             // copies, two API calls per chunk
-            st = plan_launch(p, s.h_in, nf, frame_stride, s.h_out, epilogue, p->stream);
+            st = io.launch(p, s.h_in, nf, frame_stride, s.h_out, epilogue, p->stream);
             if (st != SDRK_OK) { slots_abandon(p); return st; }
             e = hipEventRecord(s.ev_done, p->stream);
         } else {
@@ -751,7 +701,7 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
             if (e == hipSuccess) e = hipEventRecord(s.ev_in, p->s_h2d);
             if (e == hipSuccess) e = hipStreamWaitEvent(p->stream, s.ev_in, 0);
             if (e == hipSuccess) {
-                st = plan_launch(p, s.d_in, nf, frame_stride, s.d_out, epilogue, p->stream);
+                st = io.launch(p, s.d_in, nf, frame_stride, s.d_out, epilogue, p->stream);
                 if (st != SDRK_OK) { slots_abandon(p); return st; }
                 e = hipEventRecord(s.ev_k, p->stream);
             }
@@ -781,7 +731,35 @@ int exec_host_common(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame
     return fused_check(p);
 }
 
+int launch_f32(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t s) {
+    return plan_launch(p, d_in, n_frames, stride, d_out, epilogue, s);
+}
+
+// the float32 numpy boundary: complex64 in; float32 rows or complex64 out; the single-pass kernels (nfft <= 16384) may read and
+// write pinned host memory themselves
+HostIo f32_io(int epilogue) {
+    HostIo io;
+    io.in_elem = sizeof(float2);
+    io.out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+    io.epilogue = epilogue;
+    io.precision = 32;
+    io.zero_copy_max_nfft = 16384;
+    io.launch = launch_f32;
+    return io;
+}
+
 }  // namespace
+
+namespace sdrk_host {
+int fail_text(int status, const char* msg) { return fail(status, "%s", msg); }
+int check_device(int device) { return ::check_device(device); }
+int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out, int precision) {
+    return ::check_exec_args(p, in, n_frames, frame_stride, out, precision);
+}
+int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io) {
+    return exec_host_common(p, iq, n_frames, frame_stride, out, io);
+}
+}  // namespace sdrk_host
 
 namespace {
 // `launches` timed launches (after two untimed ones) of a probe kernel on a private stream
@@ -875,6 +853,7 @@ int sdrk_dev_alloc_stream_pair(int device, size_t in_bytes, size_t out_bytes, in
     size_t plan_frames = 0;
     if (plan) {
         if (plan->device != device) return fail(SDRK_ERR_INVALID, "plan is on device %d, not %d", plan->device, device);
+        if (int st = check_precision(plan, 32); st != SDRK_OK) return st;
         plan_frames = in_bytes / ((size_t)plan->nfft * sizeof(float2));
         if (plan_frames == 0 || out_bytes < plan_frames * (size_t)plan->nfft * sizeof(float))
             return fail(SDRK_ERR_INVALID, "buffers do not hold whole frames of the plan's length");
@@ -1257,6 +1236,9 @@ int sdrk_plan_destroy(sdrk_plan* p) {
         if (p->ev_row[h]) (void)hipEventDestroy(p->ev_row[h]);
     }
     if (p->d_window) (void)hipFree(p->d_window);
+    if (p->d_window64) (void)hipFree(p->d_window64);
+    if (p->d_tw64) (void)hipFree(p->d_tw64);
+    if (p->d_scratch64) (void)hipFree(p->d_scratch64);
     if (p->d_twiddle) (void)hipFree(p->d_twiddle);
     if (p->d_tw_2p) (void)hipFree(p->d_tw_2p);
     if (p->d_scratch) (void)hipFree(p->d_scratch);
@@ -1298,12 +1280,12 @@ int sdrk_plan_nfft(const sdrk_plan* p) { return p ? p->nfft : fail(SDRK_ERR_INVA
 int sdrk_plan_device(const sdrk_plan* p) { return p ? p->device : fail(SDRK_ERR_INVALID, "plan is NULL"); }
 
 int sdrk_exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, float* out_db) {
-    return exec_host_common(p, iq, n_frames, frame_stride, out_db, sdrk::EPI_LOGPSD);
+    return exec_host_common(p, iq, n_frames, frame_stride, out_db, f32_io(sdrk::EPI_LOGPSD));
 }
 
 int sdrk_exec_fft_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride,
                        void* out_c64) {
-    return exec_host_common(p, iq, n_frames, frame_stride, out_c64, sdrk::EPI_COMPLEX);
+    return exec_host_common(p, iq, n_frames, frame_stride, out_c64, f32_io(sdrk::EPI_COMPLEX));
 }
 
 int sdrk_welch_psd_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride,
@@ -1748,6 +1730,7 @@ int sdrk_frame_features_device(sdrk_plan* p, const void* d_iq, size_t n_frames, 
                                float* d_out_db, int rank, float gamma, int min_distance, int max_peaks,
                                double* d_stats, double* d_thr, int32_t* d_idx, int32_t* d_count, void* stream) {
     if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
+    if (int st = check_precision(p, 32); st != SDRK_OK) return st;
     if (n_frames == 0) return SDRK_OK;
     if (!d_iq || !d_stats) return fail(SDRK_ERR_INVALID, "d_iq or d_stats is NULL");
     const bool peaks = d_idx != nullptr || d_count != nullptr;
@@ -2056,6 +2039,7 @@ int sdrk_waterfall_append_rows(sdrk_waterfall* wf, const float* rows, size_t n_r
 int sdrk_waterfall_append_iq_device_async(sdrk_waterfall* wf, sdrk_plan* p, const void* d_iq,
                                           size_t n_frames, size_t frame_stride) {
     if (!wf || !p) return fail(SDRK_ERR_INVALID, "waterfall or plan is NULL");
+    if (int st = check_precision(p, 32); st != SDRK_OK) return st;
     if (p->nfft != wf->nfft || p->device != wf->device)
         return fail(SDRK_ERR_INVALID, "plan (nfft %d, device %d) does not match waterfall (nfft %d, device %d)",
                     p->nfft, p->device, wf->nfft, wf->device);
@@ -2103,6 +2087,7 @@ int sdrk_waterfall_append_iq_device(sdrk_waterfall* wf, sdrk_plan* p, const void
 int sdrk_waterfall_append_iq(sdrk_waterfall* wf, sdrk_plan* p, const void* iq, size_t n_frames,
                              size_t frame_stride) {
     if (!wf || !p) return fail(SDRK_ERR_INVALID, "waterfall or plan is NULL");
+    if (int st = check_precision(p, 32); st != SDRK_OK) return st;
     if (n_frames == 0) return SDRK_OK;
     if (!iq) return fail(SDRK_ERR_INVALID, "iq is NULL");
     if (frame_stride == 0 && n_frames > 1) return fail(SDRK_ERR_INVALID, "frame_stride must be >= 1");

@@ -12,8 +12,15 @@ call from those lines:
 
 Defaults reproduce the reference exactly: rectangular window, un-normalised
 forward DFT, fftshift, additive floor 1e-12 on |X|.  Contract: complex64 in,
-float32 out (complex128 input is down-cast; the reference would then compute in
-float64 — documented difference, well inside the 1e-5 parity bar).
+float32 out by default (complex128 input is down-cast; the reference would then
+compute in float64 — documented difference, well inside the 1e-5 parity bar).
+
+``precision="double"`` (a plan option and a keyword of the module functions) is
+the reference's own arithmetic: complex128 in, float64 ``power_db`` out (complex128
+from ``fft_c128``), powers of two 2 ... 2^22, on the float64 kernels of
+csrc/fft_f64.hip.  ``precision="auto"`` picks by the input's dtype as numpy's FFT
+does — complex64 / float32 / float16 single, everything else (complex128, float64,
+integers) double — so the reference's complex128 samples get float64 rows.
 
 All arithmetic on samples happens on the GPU through ``libsdrk.so``; nothing in
 this module computes a spectrum with numpy, and every entry point raises if the
@@ -33,8 +40,29 @@ from ._ffi import byref, c_float, c_int, c_size_t, c_void_p, check, lib
 WindowArg = Union[None, str, np.ndarray, Sequence[float]]
 
 
-def _window_spec(window: WindowArg, nfft: int):
-    """-> (kind, float32 array or None, cache key)."""
+PRECISIONS = ("single", "double")
+
+
+def resolve_precision(precision: str, samples=None) -> str:
+    """``"single"`` / ``"double"`` as given; ``"auto"``: what numpy's FFT computes in for the input's dtype (complex64 for
+    complex64, float32 and float16 input; complex128 for everything else, integers included)."""
+    if precision in PRECISIONS:
+        return precision
+    if precision != "auto":
+        raise ValueError(f"precision must be 'single', 'double' or 'auto', got {precision!r}")
+    dt = np.asarray(samples).dtype if not hasattr(samples, "dtype") else np.dtype(samples.dtype)
+    single = dt == np.complex64 or (dt.kind == "f" and dt.itemsize <= 4)
+    return "single" if single else "double"
+
+
+def _check_double_nfft(nfft: int) -> None:
+    """float64 plans: powers of two 2 ... 2^22 (no chirp-z in double), checked before any device call."""
+    if nfft < 2 or nfft > (1 << _ffi.MAX_LOG2_NFFT) or nfft & (nfft - 1):
+        raise ValueError(f"nfft={nfft}: precision='double' supports powers of two 2..2^{_ffi.MAX_LOG2_NFFT} only")
+
+
+def _window_spec(window: WindowArg, nfft: int, dtype=np.float32):
+    """-> (kind, array of `dtype` or None, cache key)."""
     if window is None:
         return _ffi.WINDOW_RECT, None, "rect"
     if isinstance(window, str):
@@ -44,10 +72,10 @@ def _window_spec(window: WindowArg, nfft: int):
         if name in ("hann", "hanning"):
             return _ffi.WINDOW_HANN, None, "hann"
         raise ValueError(f"unknown window {window!r} (use None, 'hann' or an array of nfft floats)")
-    w = np.ascontiguousarray(np.asarray(window, dtype=np.float32))
+    w = np.ascontiguousarray(np.asarray(window, dtype=dtype))
     if w.ndim != 1 or w.shape[0] != nfft:
         raise ValueError(f"window must have shape ({nfft},), got {w.shape}")
-    return _ffi.WINDOW_CUSTOM, w, ("custom", w.tobytes())
+    return _ffi.WINDOW_CUSTOM, w, ("custom" if w.dtype == np.float32 else "custom64", w.tobytes())
 
 
 def _as_c64(a) -> np.ndarray:
@@ -58,24 +86,43 @@ def _as_c64(a) -> np.ndarray:
     return np.ascontiguousarray(arr)
 
 
+def _as_c128(a) -> np.ndarray:
+    """complex128, C-contiguous view or copy of `a`."""
+    arr = np.asarray(a)
+    if arr.dtype != np.complex128:
+        arr = arr.astype(np.complex128)
+    return np.ascontiguousarray(arr)
+
+
 class SpectrumPlan:
-    """A compiled plan for one (nfft, window, eps, shift, device) combination.
+    """A compiled plan for one (nfft, window, eps, shift, device, precision) combination.
 
     Thin owner of an ``sdrk_plan``; methods take and return numpy arrays.  A plan
     is used by one thread at a time (an internal lock enforces it); create one
     plan per device to drive several GPUs from several threads.
+
+    ``precision="double"``: complex128 in, float64 rows (complex128 from ``fft``) out, powers of two only; Welch and the
+    ``fused64k`` / ``overlap_passes`` / ``tune_staging`` options are float32-only.
     """
 
     def __init__(self, nfft: int, *, window: WindowArg = None, eps: float = 1e-12,
                  shift: bool = True, device: int = 0, max_batch: int = 1 << 30, fused64k: Optional[bool] = None,
-                 overlap_passes: bool = False, tune_staging: bool = False):
+                 overlap_passes: bool = False, tune_staging: bool = False, precision: str = "single"):
         nfft = int(nfft)
+        if precision not in PRECISIONS:
+            raise ValueError(f"plan precision must be 'single' or 'double', got {precision!r}")
+        self.precision = precision
+        self._double = precision == "double"
+        if self._double:
+            _check_double_nfft(nfft)
+            if fused64k is not None or overlap_passes or tune_staging:
+                raise ValueError("fused64k, overlap_passes and tune_staging are options of float32 plans only")
         pow2 = nfft >= 2 and not (nfft & (nfft - 1))
         if nfft < 2 or nfft > (1 << _ffi.MAX_LOG2_NFFT) or (not pow2 and nfft > (1 << (_ffi.MAX_LOG2_NFFT - 1))):
             raise ValueError(
                 f"nfft={nfft}: frames must have 2..2^{_ffi.MAX_LOG2_NFFT} samples (powers of two) or "
                 f"2..2^{_ffi.MAX_LOG2_NFFT - 1} (other lengths, via Bluestein)")
-        kind, warr, self._wkey = _window_spec(window, nfft)
+        kind, warr, self._wkey = _window_spec(window, nfft, np.float64 if self._double else np.float32)
         _ffi.require_device(device)
         self.nfft = nfft
         self.eps = float(eps)
@@ -94,6 +141,10 @@ class SpectrumPlan:
         # tune_staging: the numpy boundary's device staging placed at creation (sdrk.h SDRK_PLAN_TUNE_STAGING; measured:
         # no effect at the shipped chunk size)
         self.tune_staging = bool(tune_staging)
+        if self._double:
+            check(lib().sdrk_plan_create_f64(self.device, nfft, c_size_t(int(max_batch)), kind, wptr,
+                                             _ffi.c_double(self.eps), int(self.shift), byref(self._handle)))
+            return
         flags = ((_ffi.PLAN_FUSED64K if self.fused64k else 0) |
                  (_ffi.PLAN_TILED64K if self.fused64k is False and nfft == 65536 else 0) |
                  (_ffi.PLAN_OVERLAP_PASSES if self.overlap_passes else 0) |
@@ -132,8 +183,15 @@ class SpectrumPlan:
             check(fn(self.handle, iq.ctypes.data_as(c_void_p), c_size_t(n_frames), c_size_t(stride),
                      out.ctypes.data_as(c_void_p)))
 
+    def _float32_only(self, what: str) -> None:
+        if self._double:
+            raise ValueError(f"{what} is not available on a precision='double' plan")
+
+    def _as_input(self, a) -> np.ndarray:
+        return _as_c128(a) if self._double else _as_c64(a)
+
     def _frames(self, samples):
-        x = _as_c64(samples)
+        x = self._as_input(samples)
         if x.ndim == 1:
             if x.shape[0] != self.nfft:
                 raise ValueError(f"frame has {x.shape[0]} samples, plan nfft is {self.nfft}")
@@ -152,21 +210,29 @@ class SpectrumPlan:
             raise ValueError(f"out must be a C-contiguous {np.dtype(dtype).name} array of shape {tuple(shape)}")
         return out
 
+    @property
+    def _row_dtype(self):
+        return np.float64 if self._double else np.float32
+
+    def _exec_host_fn(self):
+        return lib().sdrk_exec_host_f64 if self._double else lib().sdrk_exec_host
+
     def spectrum_db(self, samples, out: Optional[np.ndarray] = None) -> np.ndarray:
-        """float32 ``20*log10(|fftshift(fft(w*x))| + eps)`` for one frame or a batch; ``out`` (same shape as
-        ``samples``, float32) receives the rows in place when given."""
+        """float32 (float64 on a double plan) ``20*log10(|fftshift(fft(w*x))| + eps)`` for one frame or a batch; ``out``
+        (same shape as ``samples``, of the row dtype) receives the rows in place when given."""
         x, one = self._frames(samples)
-        res = self._out_array(out, x.shape[1:] if one else x.shape, np.float32)
+        res = self._out_array(out, x.shape[1:] if one else x.shape, self._row_dtype)
         if x.shape[0]:
-            self._run_host(lib().sdrk_exec_host, x, x.shape[0], self.nfft, res)
+            self._run_host(self._exec_host_fn(), x, x.shape[0], self.nfft, res)
         return res
 
     def fft(self, samples) -> np.ndarray:
-        """complex64 spectrum ``fft(w*x)`` (fftshifted if the plan shifts), no log."""
+        """complex64 (complex128 on a double plan) spectrum ``fft(w*x)`` (fftshifted if the plan shifts), no log."""
         x, one = self._frames(samples)
-        out = np.empty(x.shape, dtype=np.complex64)
+        out = np.empty(x.shape, dtype=np.complex128 if self._double else np.complex64)
         if x.shape[0]:
-            self._run_host(lib().sdrk_exec_fft_host, x, x.shape[0], self.nfft, out)
+            self._run_host(lib().sdrk_exec_fft_host_f64 if self._double else lib().sdrk_exec_fft_host, x, x.shape[0],
+                           self.nfft, out)
         return out[0] if one else out
 
     def stft_db(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -174,14 +240,14 @@ class SpectrumPlan:
         ``[r*hop, r*hop + nfft)``; ``rows = 1 + (len(iq) - nfft) // hop`` (0 if the
         stream is shorter than one frame).  Frames are cut on the device from the
         single uploaded stream; overlapped samples are not duplicated on the host."""
-        x = _as_c64(iq).reshape(-1)
+        x = self._as_input(iq).reshape(-1)
         hop = self.nfft if hop is None else int(hop)
         if hop < 1:
             raise ValueError("hop must be >= 1")
         rows = 0 if x.shape[0] < self.nfft else 1 + (x.shape[0] - self.nfft) // hop
-        out = self._out_array(out, (rows, self.nfft), np.float32)
+        out = self._out_array(out, (rows, self.nfft), self._row_dtype)
         if rows:
-            self._run_host(lib().sdrk_exec_host, x, rows, hop, out)
+            self._run_host(self._exec_host_fn(), x, rows, hop, out)
         return out
 
     def welch_psd(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
@@ -191,6 +257,7 @@ class SpectrumPlan:
         two-sided; in fftshift order when the plan shifts), which is what the reference's
         offline script plots (scripts/process_sigmf_data.py:188-189).  The per-segment
         transforms and the averaging both run on the GPU."""
+        self._float32_only("welch_psd")
         x = _as_c64(iq).reshape(-1)
         hop = self.nfft if hop is None else int(hop)
         if hop < 1:
@@ -214,15 +281,19 @@ class SpectrumPlan:
     # -- device pointers (bench / pipelines that keep data resident) -------------
     def exec_device(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                     stream: int = 0) -> None:
+        """Device pointers: complex64 in / float32 rows out (complex128 / float64 on a double plan), asynchronous on
+        ``stream`` (0: the plan's stream)."""
         stride = self.nfft if frame_stride is None else int(frame_stride)
+        fn = lib().sdrk_exec_device_f64 if self._double else lib().sdrk_exec_device
         with self._lock:
-            check(lib().sdrk_exec_device(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+            check(fn(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
                                          c_void_p(d_out), c_void_p(stream) if stream else None))
 
     def tune_scratch(self, d_iq: int, n_frames: int, d_out: int, candidates: int = 6, *,
                      frame_stride: Optional[int] = None):
         """Large-frame plans: try ``candidates`` placements of the two-pass scratch on this workload and keep the
         fastest (``sdrk_plan_tune_scratch``).  Returns ``(probe_ms, chosen)``; ``d_out`` is overwritten."""
+        self._float32_only("tune_scratch")
         stride = self.nfft if frame_stride is None else int(frame_stride)
         ms, chosen = (c_float * int(candidates))(), c_int(0)
         with self._lock:
@@ -237,8 +308,9 @@ class SpectrumPlan:
         consecutive launches on the plan's stream)."""
         stride = self.nfft if frame_stride is None else int(frame_stride)
         ms = (c_float * int(launches))()
+        fn = lib().sdrk_exec_device_f64_timed_each if self._double else lib().sdrk_exec_device_timed_each
         with self._lock:
-            check(lib().sdrk_exec_device_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames),
+            check(fn(self.handle, c_void_p(d_iq), c_size_t(n_frames),
                                                     c_size_t(stride), c_void_p(d_out), int(launches), ms))
         return [float(v) for v in ms]
 
@@ -246,6 +318,7 @@ class SpectrumPlan:
                           frame_stride: Optional[int] = None) -> float:
         """Run `launches` back-to-back transforms on the plan's stream; milliseconds
         between HIP events recorded on that stream (all launches together)."""
+        self._float32_only("exec_device_timed (use exec_device_timed_each)")
         stride = self.nfft if frame_stride is None else int(frame_stride)
         ms = c_float(0.0)
         with self._lock:
@@ -290,16 +363,19 @@ _plans: dict = {}
 _plans_lock = threading.Lock()
 
 
-def _cached_plan(nfft: int, window: WindowArg, eps: float, shift: bool, device: int) -> SpectrumPlan:
-    _, _, wkey = _window_spec(window, nfft)
-    key = (int(device), int(nfft), wkey, float(eps), bool(shift))
+def _cached_plan(nfft: int, window: WindowArg, eps: float, shift: bool, device: int,
+                 precision: str = "single") -> SpectrumPlan:
+    if precision == "double":
+        _check_double_nfft(int(nfft))
+    _, _, wkey = _window_spec(window, nfft, np.float64 if precision == "double" else np.float32)
+    key = (int(device), int(nfft), wkey, float(eps), bool(shift), precision)
     plan = _plans.get(key)                      # (dict.get is atomic; the lock is only for creation)
     if plan is not None:
         return plan
     with _plans_lock:
         plan = _plans.get(key)
         if plan is None:
-            plan = SpectrumPlan(nfft, window=window, eps=eps, shift=shift, device=device)
+            plan = SpectrumPlan(nfft, window=window, eps=eps, shift=shift, device=device, precision=precision)
             _plans[key] = plan
         return plan
 
@@ -318,9 +394,14 @@ def _nfft_of(samples) -> int:
     return int(shape[-1])
 
 
+def _no_sharding(precision: str, devices) -> None:
+    if precision == "double" and devices is not None:
+        raise ValueError("devices=[...] (multi-GPU sharding) is float32 only; use device= with precision='double'")
+
+
 def spectrum_db(samples, *, window: WindowArg = None, eps: float = 1e-12, shift: bool = True,
                 device: int = 0, devices: Optional[Sequence[int]] = None,
-                out: Optional[np.ndarray] = None, pin="auto") -> np.ndarray:
+                out: Optional[np.ndarray] = None, pin="auto", precision: str = "single") -> np.ndarray:
     """Power spectrum in dB of one frame ``(N,)`` or a batch ``(B, N)`` of complex IQ.
 
     Equivalent to ``20*np.log10(np.abs(np.fft.fftshift(np.fft.fft(samples*window, axis=-1),
@@ -331,8 +412,14 @@ def spectrum_db(samples, *, window: WindowArg = None, eps: float = 1e-12, shift:
     allocating (large batches: reusing it saves the page faults and the munmap of a
     fresh result per call).  ``pin`` (with ``devices``): how pageable arrays reach several GPUs — ``"auto"`` stages
     them until reuse has paid for page-locking them (sharding.spectrum_db_sharded, hostmem.plan_pinning).
+    ``precision``: ``"single"`` (complex64 -> float32), ``"double"`` (complex128 -> float64, the reference's dtypes) or
+    ``"auto"`` (by the input's dtype, as numpy's FFT decides).
     """
     nfft = _nfft_of(samples)
+    precision = resolve_precision(precision, samples)
+    _no_sharding(precision, devices)
+    if precision == "double":
+        return _cached_plan(nfft, window, eps, shift, device, "double").spectrum_db(samples, out=out)
     if devices is not None and len(devices) > 1 and np.ndim(samples) == 2:
         from .sharding import spectrum_db_sharded
         return spectrum_db_sharded(samples, devices, window=window, eps=eps, shift=shift, out=out, pin=pin)
@@ -346,6 +433,13 @@ def fft_c64(samples, *, window: WindowArg = None, shift: bool = False, device: i
     log), optionally fftshifted."""
     nfft = _nfft_of(samples)
     return _cached_plan(nfft, window, 1e-12, shift, device).fft(samples)
+
+
+def fft_c128(samples, *, window: WindowArg = None, shift: bool = False, device: int = 0) -> np.ndarray:
+    """complex128 ``np.fft.fft(samples*window, axis=-1)`` computed in double (streamer.py:119 in the reference's own
+    dtype), optionally fftshifted; powers of two 2 ... 2^22."""
+    nfft = _nfft_of(samples)
+    return _cached_plan(nfft, window, 1e-12, shift, device, "double").fft(samples)
 
 
 def freq_axis(n: int, sample_rate: float, center_freq: float = 0.0) -> np.ndarray:
@@ -375,13 +469,14 @@ _freq_cache: dict = {}
 
 
 def process_frame(samples, sample_rate: float, center_freq: float, *, window: WindowArg = None,
-                  eps: float = 1e-12, device: int = 0) -> dict:
+                  eps: float = 1e-12, device: int = 0, precision: str = "single") -> dict:
     """One reader-loop iteration of the reference (app/sdr/streamer.py:119-130):
     returns the ``plot_data`` dict with exactly its keys — ``time``, ``samples``
     (the caller's array, same object), ``freqs``, ``power_db``, ``sample_rate``,
     ``center_freq`` — which is what ``update_graphs`` reads
-    (app/dashboard/callbacks.py:110-115)."""
-    power_db = spectrum_db(samples, window=window, eps=eps, shift=True, device=device)
+    (app/dashboard/callbacks.py:110-115).  ``precision="auto"`` gives the reference's float64 ``power_db`` for its
+    complex128 samples."""
+    power_db = spectrum_db(samples, window=window, eps=eps, shift=True, device=device, precision=precision)
     freqs = freq_axis(len(samples), sample_rate, center_freq)
     return {
         "time": time.time(),
@@ -402,10 +497,16 @@ def welch_psd(iq, nfft: int, sample_rate: float, hop: Optional[int] = None, wind
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,
-            shift: bool = True, device: int = 0, devices: Optional[Sequence[int]] = None) -> np.ndarray:
+            shift: bool = True, device: int = 0, devices: Optional[Sequence[int]] = None,
+            precision: str = "single") -> np.ndarray:
     """Spectrogram rows ``(rows, nfft)`` float32 over one contiguous IQ stream (the
     waterfall of BASELINE.json config 3: nfft=65536, hop=nfft//2).  ``devices=[...]`` splits the
-    rows into contiguous ranges, one per GPU, each reading its samples plus an ``nfft-hop`` halo."""
+    rows into contiguous ranges, one per GPU, each reading its samples plus an ``nfft-hop`` halo.
+    ``precision="double"`` (or ``"auto"`` on complex128 input): float64 rows from complex128 samples, one device."""
+    precision = resolve_precision(precision, iq)
+    _no_sharding(precision, devices)
+    if precision == "double":
+        return _cached_plan(int(nfft), window, eps, shift, device, "double").stft_db(iq, hop)
     if devices is not None and len(devices) > 1:
         from .sharding import stft_db_sharded
         return stft_db_sharded(iq, int(nfft), int(nfft if hop is None else hop), devices, window=window, eps=eps,

@@ -19,6 +19,7 @@ __path__.append(_SRC_DIR)
 from .spectrum import (  # noqa: E402
     SpectrumPlan,
     fft_c64,
+    fft_c128,
     freq_axis,
     process_frame,
     spectrum_db,
@@ -36,6 +37,7 @@ __all__ = [
     "device_count",
     "device_info",
     "fft_c64",
+    "fft_c128",
     "freq_axis",
     "is_pinned",
     "library_path",
