@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where does the persistent N = 65536 launch start to pay?  Forced fused against forced tiled for calls of 1 ... 4096 frames,
-device resident, warm, median of 15 launches (events between consecutive launches).  Sets FUSED_AUTO_MIN_FRAMES (sdrk_api.hip).
+device resident, warm, median of 15 launches (events between consecutive launches).  Sets FUSED_AUTO_MIN_FRAMES (plan_internal.h).
     crossover.py [hop]"""
 import ctypes
 import os

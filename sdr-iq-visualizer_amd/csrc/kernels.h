@@ -1,4 +1,4 @@
-// kernels.h — internal interface between the C ABI (sdrk_api.hip) and the
+// kernels.h — internal interface between the C ABI (the host files sdrk_*.hip) and the
 // gfx950 kernels.  Nothing here is exported from the shared library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -63,7 +63,7 @@ struct LaunchArgs {
     size_t in_valid = 0;
 };
 
-#ifdef __HIPCC__   // device helpers (the host-only sanitizer build of sdrk_api.hip, tests/fake_hip, compiles this header with g++)
+#ifdef __HIPCC__   // device helpers (the host-only sanitizer build of the host files, tests/fake_hip, compiles this header with g++)
 // 20*log10(sqrt(re^2+im^2) + eps), the expression order of streamer.py:121:
 // |X| first, then the additive floor, then the log.  v_sqrt_f32 / v_log_f32 are
 // 1-ulp approximations; the result is within ~2e-5 dB of numpy's float32 path

@@ -1,10 +1,14 @@
-// plan_internal.h — what the host translation units of the C ABI share: the plan object behind the opaque sdrk_plan and the
-// entry points of sdrk_api.hip that the double-precision entry points (sdrk_f64.hip) build on.  Not installed; host code only.
+// plan_internal.h — what the host translation units of the C ABI (sdrk_*.hip) share: the plan object behind the opaque
+// sdrk_plan, error reporting, the argument checks, the launch dispatcher and the staging slots of the numpy boundary.  Each
+// function is defined in exactly one .hip, named beside its declaration.  Not installed; host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "../../include/sdrk.h"
 
@@ -86,6 +90,63 @@ struct sdrk_plan {
 
 namespace sdrk_host {
 
+constexpr size_t SMALL_IN_BYTES = 256 << 10;   // calls up to this much input take the zero-copy path
+constexpr size_t HOST_CHUNK_BYTES = 16 << 20;  // target input bytes per pipelined chunk of sdrk_exec_host
+constexpr size_t ZERO_COPY_MAX_BYTES = 32 << 20;  // calls up to this much input skip the DMA engines (see exec_host)
+constexpr unsigned FUSED_MAILBOX = 64;   // entries of 8 words: error flag + debug record
+// Below this many frames a launch of an auto plan takes the two tiled launches: the persistent launch costs about 30 us before
+// its first row (control-block memset, role formation, the ramp of a set's pipeline, the mailbox copy) against 11-18 us, and
+// the two forms cross between 384 and 512 frames, packed or half-overlapped (profiles/r06/fused64k_crossover.log).
+constexpr size_t FUSED_AUTO_MIN_FRAMES = 512;
+
+// ---- sdrk_api.hip: error text, devices, pinned ranges, growing device buffers ----
+int fail(int status, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets sdrk_last_error(), returns status
+
+#define HIP_TRY(expr)                                                                                                   \
+    do {                                                                                                                \
+        hipError_t e__ = (expr);                                                                                        \
+        if (e__ != hipSuccess)                                                                                          \
+            return ::sdrk_host::fail(e__ == hipErrorOutOfMemory ? SDRK_ERR_NOMEM : SDRK_ERR_HIP,                        \
+                                     "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);       \
+    } while (0)
+
+int check_device(int device);
+bool is_pow2(long long v);
+
+// Pinned host ranges the library knows about (sdrk_host_alloc / sdrk_host_register): start -> (bytes, owned)
+struct PinnedRanges {
+    std::mutex m;
+    std::map<uintptr_t, std::pair<size_t, bool>> r;
+    bool covers(const void* p, size_t bytes) {
+        if (!p || bytes == 0) return false;
+        std::lock_guard<std::mutex> g(m);
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+        auto it = r.upper_bound(a);
+        if (it == r.begin()) return false;
+        --it;
+        return a >= it->first && a + bytes <= it->first + it->second.first;
+    }
+};
+PinnedRanges& pinned_ranges();
+
+int grow(int device, void** buf, size_t* cap, size_t need);   // device staging that only ever grows
+
+// ---- sdrk_plan.hip: argument checks, the launch dispatcher, the fused N = 65536 gate ----
+int check_precision(const sdrk_plan* p, int precision);
+// NULL plan, plan of another precision, NULL buffers, zero stride
+int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out, int precision = 32);
+bool takes_fused(const sdrk_plan* p, size_t n_frames);   // the persistent N = 65536 kernel for this many frames?
+struct EpiArgs;   // chirp-z epilogues riding on an inner plan's row pass (sdrk_plan.hip)
+// One float32 transform of the plan.  d_mip / mip_written: see LaunchArgs (kernels.h) — *mip_written tells whether the launch
+// wrote the by-16 companion rows.
+int plan_launch(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out, int epilogue,
+                hipStream_t stream, float* d_mip = nullptr, bool* mip_written = nullptr, const EpiArgs* epi = nullptr);
+int fused_check(sdrk_plan* p);   // after a stream sync: the fused launches since the last check
+
+// ---- sdrk_probes.hip ----
+int tune_staging(sdrk_plan* p);   // SDRK_PLAN_TUNE_STAGING, at plan creation
+
+// ---- sdrk_host_pipeline.hip: the staging slots and the numpy boundary ----
 // One transform of the plan: (plan, device input, frames, frame stride, device output, epilogue, stream) -> sdrk_status.
 using LaunchFn = int (*)(sdrk_plan*, const void*, size_t, size_t, void*, int, hipStream_t);
 
@@ -99,10 +160,14 @@ struct HostIo {
     LaunchFn launch = nullptr;
 };
 
-int fail_text(int status, const char* msg);    // sets sdrk_last_error(), returns status
-int check_device(int device);
-// NULL plan, plan of another precision, NULL buffers, zero stride
-int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out, int precision);
+int slot_reserve(sdrk_plan* p, HostSlot& s, size_t in_bytes, size_t out_bytes);   // events and staging of at least these sizes
+void slots_abandon(sdrk_plan* p);   // error path: nothing may still be writing into the staging buffers
+int ensure_copy_streams(sdrk_plan* p);   // s_h2d / s_d2h, created at the first chunked call
+// Where a copy engine (or, on the zero-copy branch, the kernel) reads a chunk of the caller's input: the caller's own array
+// if it is pinned, else the slot's pinned h_in, filled by the helper threads.
+const void* chunk_pinned_src(HostSlot& s, const void* src, size_t bytes, bool in_pinned);
+// The pinned chunk -> the slot's d_in on s_h2d; ev_in behind it, and the plan's stream waits for that.
+hipError_t stage_chunk_in(sdrk_plan* p, HostSlot& s, const void* pinned_src, size_t bytes);
 // the small mapped call, the zero-copy chunks and the three-slot pipeline of sdrk_exec_host, for any element sizes
 int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io);
 

@@ -1,14 +1,12 @@
 // sdrk_f64.hip — host side of the double-precision entry points of include/sdrk.h (sdrk_plan_create_f64, sdrk_exec_*_f64):
 // the reference's own arithmetic, complex128 samples in and float64 power_db out (app/sdr/streamer.py:119-121).  An f64 plan
-// is an ordinary sdrk_plan with precision 64; the numpy boundary is sdrk_api.hip's pipeline (sdrk_host::exec_host) with
+// is an ordinary sdrk_plan with precision 64; the numpy boundary is sdrk_host_pipeline.hip's (sdrk_host::exec_host) with
 // 16-byte samples, and the transforms are fft_f64.hip's.  Host code only.
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -17,26 +15,9 @@
 #include "kernels_f64.h"
 #include "plan_internal.h"
 
+using namespace sdrk_host;
+
 namespace {
-
-int fail(int status, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int status, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return sdrk_host::fail_text(status, buf);
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e__ = (expr);                                                           \
-        if (e__ != hipSuccess)                                                             \
-            return fail(e__ == hipErrorOutOfMemory ? SDRK_ERR_NOMEM : SDRK_ERR_HIP,        \
-                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__,  \
-                        __LINE__);                                                         \
-    } while (0)
 
 // Scratch between the two passes of nfft > 4096: up to 192 MiB of complex128 frames (at least one frame: 64 MiB at 2^22).
 constexpr size_t SCRATCH64_BYTES = (size_t)192 << 20;
@@ -74,8 +55,6 @@ sdrk_host::HostIo f64_io(int epilogue) {
     io.launch = launch64;
     return io;
 }
-
-bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // tests/fake_hip/fake_kernels.cpp — stand-ins for the gfx950 kernels behind csrc/kernels.h, for the host-only sanitizer
-// build of csrc/sdrk_api.hip (see hip/hip_runtime.h beside this file).  Each "launch" enqueues a host function on the
+// build of the host files csrc/sdrk_*.hip (see hip/hip_runtime.h beside this file).  Each "launch" enqueues a host function on the
 // stream it was given, so it runs asynchronously on that stream's thread like a kernel would.  The "transform" is NOT a
 // spectrum: row[f][k] = 3 re(x[f][k]) - im(x[f][k]) + k (log epilogue) or (re + 1, im - 1) (complex epilogue) — a function of
 // the input that lets the driver check, element by element, that the host pipeline moved the right bytes to the right place.

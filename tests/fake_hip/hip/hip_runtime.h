@@ -1,4 +1,4 @@
-// tests/fake_hip/hip/hip_runtime.h — a HOST-ONLY stand-in for the HIP runtime calls that csrc/sdrk_api.hip makes, so that
+// tests/fake_hip/hip/hip_runtime.h — a HOST-ONLY stand-in for the HIP runtime calls that the host files csrc/sdrk_*.hip make, so that
 // the library's host side (plans, the four-slot pinned pipeline of sdrk_exec_host, the pinned-range table, the waterfall
 // ring's two-stream read-out, the placement probes) can be built with g++ and run under ThreadSanitizer and
 // AddressSanitizer + UBSan in the CPU suite (tests/test_host_sanitizers.py; GPU-side sanitizers do not exist on this pool).

@@ -1,6 +1,6 @@
 // tests/host_api_f64_stress.cpp — drives the host side of the double-precision entry points (csrc/sdrk_f64.hip on top of
-// csrc/sdrk_api.hip's numpy-boundary pipeline, built with g++ against the stand-in runtime of tests/fake_hip and the stand-in
-// launcher of tests/fake_f64_kernels.cpp) for the sanitizer legs of tests/test_host_sanitizers_f64.py.
+// csrc/sdrk_host_pipeline.hip's numpy boundary; all host files csrc/sdrk_*.hip built with g++ against the stand-in runtime
+// of tests/fake_hip and the stand-in launcher of tests/fake_f64_kernels.cpp) for the sanitizer legs of tests/test_host_sanitizers_f64.py.
 //
 // Every path of sdrk_exec_host_f64 with 16-byte samples — the mapped small call, the zero-copy chunks, the three-slot DMA
 // pipeline from pageable and from pinned caller arrays, overlapped frames, ragged last chunks, the two-pass lengths' scratch —

@@ -1,5 +1,5 @@
-// tests/host_api_stress.cpp — drives the HOST side of the library (csrc/sdrk_api.hip built with g++ against the stand-in
-// runtime of tests/fake_hip) through its C ABI from several threads at once, for the sanitizer legs of the CPU suite
+// tests/host_api_stress.cpp — drives the HOST side of the library (the float32 host files csrc/sdrk_*.hip built with g++
+// against the stand-in runtime of tests/fake_hip) through its C ABI from several threads at once, for the sanitizer legs of the CPU suite
 // (tests/test_host_sanitizers.py: -fsanitize=thread, and -fsanitize=address,undefined with leak checking).
 //
 // The stand-in "transform" is row[f][k] = 3 re - im + (k & 1023) (fake_kernels.cpp): every path of sdrk_exec_host — the

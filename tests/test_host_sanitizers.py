@@ -14,6 +14,8 @@ import threading
 import numpy as np
 import pytest
 
+from tests.host_sources import host_sources
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -49,15 +51,14 @@ def test_copy_pool_under_sanitizers(stress_binaries, san, helpers):
 
 @pytest.fixture(scope="module")
 def host_api_binaries(tmp_path_factory):
-    """csrc/sdrk_api.hip — the 1 900 lines of host C++ behind the C ABI — compiled with g++ against the stand-in runtime of
-    tests/fake_hip (streams are threads, events are tickets, device memory is malloc: asynchrony and bounds are real, the
-    spectrum is not) and linked with the driver tests/host_api_stress.cpp, once per sanitizer."""
+    """csrc/sdrk_*.hip without sdrk_f64.hip — the 2 000 lines of host C++ behind the float32 C ABI — compiled with g++ against
+    the stand-in runtime of tests/fake_hip (streams are threads, events are tickets, device memory is malloc: asynchrony and
+    bounds are real, the spectrum is not) and linked with the driver tests/host_api_stress.cpp, once per sanitizer."""
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("g++ not available")
     out = tmp_path_factory.mktemp("san_api")
-    repo = os.path.dirname(HERE)
-    srcs = [("-x c++", os.path.join(repo, "sdr-iq-visualizer_amd", "csrc", "sdrk_api.hip")),
+    srcs = [*(("-x c++", src) for src in host_sources(f64=False)),
             ("", os.path.join(HERE, "fake_hip", "fake_kernels.cpp")), ("", os.path.join(HERE, "host_api_stress.cpp"))]
     built = {}
     for name, flags in (("tsan", ["-fsanitize=thread"]),

@@ -1,6 +1,7 @@
 """Sanitizer legs for the host side of the double-precision entry points (CPU).
 
-csrc/sdrk_f64.hip and csrc/sdrk_api.hip (whose numpy-boundary pipeline the f64 calls share, with 16-byte samples) compiled with
+csrc/sdrk_f64.hip and the other host files csrc/sdrk_*.hip (whose numpy-boundary pipeline the f64 calls share, with 16-byte
+samples) compiled with
 g++ against the stand-in runtime of tests/fake_hip and the stand-in f64 launcher of tests/fake_f64_kernels.cpp, driven by
 tests/host_api_f64_stress.cpp under ThreadSanitizer and under AddressSanitizer + UBSan with leak checking: the small call,
 chunked calls from pageable and from pinned arrays, two threads on their own plans, and the refusals across precisions."""
@@ -10,8 +11,9 @@ import subprocess
 
 import pytest
 
+from tests.host_sources import host_sources
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
@@ -20,8 +22,7 @@ def f64_binaries(tmp_path_factory):
     if not gxx:
         pytest.skip("g++ not available")
     out = tmp_path_factory.mktemp("san_f64")
-    csrc = os.path.join(REPO, "sdr-iq-visualizer_amd", "csrc")
-    srcs = [("-x c++", os.path.join(csrc, "sdrk_api.hip")), ("-x c++", os.path.join(csrc, "sdrk_f64.hip")),
+    srcs = [*(("-x c++", src) for src in host_sources(f64=True)),
             ("", os.path.join(HERE, "fake_hip", "fake_kernels.cpp")), ("", os.path.join(HERE, "fake_f64_kernels.cpp")),
             ("", os.path.join(HERE, "host_api_f64_stress.cpp"))]
     built = {}

@@ -1623,7 +1623,7 @@ def test_config3_full_size_sampled_rows(pkg, form):
     (fft_fused64k.hip): 24 sets of 32 workgroups, set g owns the contiguous run of 782 rows from 782 g (the last set 763) —
     sampled on both sides of the first, second and last run boundary (781 / 782, 1563 / 1564, 17985 / 17986).  The two tiled
     launches walk the stream in chunks of 384 frames (192 MiB of scratch,
-    sdrk_api.hip: plan creation; fft_tiled2.hip: round_chunk) = 48 full chunks + a last one of 317; inside a chunk the
+    sdrk_plan.hip: plan creation; fft_tiled2.hip: round_chunk) = 48 full chunks + a last one of 317; inside a chunk the
     col pass gives each of its 48 workgroups per tile position a run of 8 consecutive frames (7 in the last chunk, whose
     46th run has 2 frames left and whose 47th and 48th have none).  Sampled: both ends, both sides of the first, second
     and last chunk boundary, both sides of a run boundary in a full chunk and in the last chunk, the last run's rows."""
