@@ -249,6 +249,32 @@ int sdrk_exec_device_f64(sdrk_plan* plan, const void* d_iq_c128, size_t n_frames
 int sdrk_exec_device_f64_timed_each(sdrk_plan* plan, const void* d_iq_c128, size_t n_frames, size_t frame_stride,
                                     double* d_out_db, int launches, float* each_ms);
 
+/* ---- int16 input: what the radio delivers -----------------------------------------
+ * The AD936x behind app/sdr/streamer.py:114 (self.sdr.rx()) produces 12-bit integers in int16 pairs; pyadi-iio widens them to
+ * complex128 only because numpy needs it, and "ci16_le" is the most common SigMF datatype.  These entry points take that
+ * format as it is: interleaved little-endian int16 I,Q, 4 bytes per sample, frame f at sample f*frame_stride (layout rules as
+ * sdrk_exec_host / sdrk_exec_device; the buffer need only be 4-byte aligned).  Semantics:
+ *     x[n] = float32(I[n]) + i*float32(Q[n])          (exact)
+ * then exactly what the plan's complex64 entry point computes — the same bits, not the same values within a tolerance.  No
+ * scale is applied: a caller who wants full-scale normalisation folds 1/32768 (1/2048 for 12-bit data) into a custom window or
+ * adds the constant 20*log10(scale) to the dB rows.  Served by ordinary float32 plans of any nfft; an f64 plan returns
+ * SDRK_ERR_INVALID.  nfft = 256 ... 16384 are read as int16 by the transform itself (half the input bytes of the complex64
+ * call); other lengths are widened on the device in chunks of at most 64 MiB first.  Welch, the feature entry points and the
+ * waterfall appends have no int16 form. */
+/* streamer.py:114-121, host in / host out: the numpy boundary of sdrk_exec_host with 4-byte samples */
+int sdrk_exec_host_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_frames, size_t frame_stride, float* out_db);
+/* streamer.py:114-119: complex64 fft(w*x) of int16 samples, fftshifted if the plan shifts */
+int sdrk_exec_fft_host_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_frames, size_t frame_stride, void* out_c64);
+/* streamer.py:114-121, device in / device out, asynchronous on `stream` (NULL: the plan's stream); any number of frames */
+int sdrk_exec_device_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_frames, size_t frame_stride, float* d_out_db,
+                          void* stream);
+/* streamer.py:114-121, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_frames, size_t frame_stride,
+                                     float* d_out_db, int launches, float* each_ms);
+/* streamer.py:114: sdrk_synth_fill's values (below) as int16 pairs, n_frames*nfft*4 bytes; equal to synth.py's int16 form */
+int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,
+                         void* stream);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

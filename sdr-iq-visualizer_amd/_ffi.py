@@ -131,6 +131,12 @@ SYMBOLS = [
     ("sdrk_exec_fft_host_f64", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     ("sdrk_exec_device_f64", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     ("sdrk_exec_device_f64_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
+    # int16 I,Q input (what the radio delivers, streamer.py:114; SigMF ci16_le) on float32 plans
+    ("sdrk_exec_host_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrk_exec_device_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_synth_fill_ci16", c_int, [c_int, c_uint32, c_uint64, c_size_t, c_int, c_void_p, c_void_p]),
 ]
 
 _lib = None

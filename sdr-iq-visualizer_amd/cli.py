@@ -44,19 +44,28 @@ def main(argv=None) -> int:
         return 0
 
     from . import spectrum
-    samples, meta = sigmf_io.read_sigmf(args.path)
-    if samples.size < args.nfft:
-        print(f"recording has {samples.size} samples, need {args.nfft}", file=sys.stderr)
+    # one read; an int16 recording stays int16 (the spectrum row is computed from the int16 samples themselves: the same
+    # bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
+    samples, meta = sigmf_io.read_sigmf(args.path, native=True)
+    raw16 = samples if samples.dtype == np.int16 else None
+    n_samples = int(samples.shape[0])
+    if n_samples < args.nfft:
+        print(f"recording has {n_samples} samples, need {args.nfft}", file=sys.stderr)
         return 2
     fs, fc = meta["sample_rate"], meta["center_freq"]
-    power_db = spectrum.spectrum_db(samples[: args.nfft], window=args.window, device=args.device)
+    if raw16 is not None:
+        power_db = spectrum.spectrum_db_ci16(np.ascontiguousarray(raw16[: args.nfft]), window=args.window, device=args.device)
+    else:
+        power_db = spectrum.spectrum_db(samples[: args.nfft], window=args.window, device=args.device)
     freqs = spectrum.freq_axis(args.nfft, fs, fc)
     k = int(np.argmax(power_db))
-    report = {"samples": int(samples.size), "sample_rate": fs, "center_freq": fc, "nfft": args.nfft,
+    report = {"samples": n_samples, "sample_rate": fs, "center_freq": fc, "nfft": args.nfft,
               "peak_db": float(power_db[k]), "peak_freq_hz": float(freqs[k]),
               "median_db": float(np.median(power_db))}
     results = {"power_db": power_db, "freqs": freqs}
     if args.welch:
+        if raw16 is not None:
+            samples = raw16.astype(np.float32).view(np.complex64).reshape(-1)
         pxx = spectrum.welch_psd(samples, args.welch, fs, device=args.device)
         results["welch_pxx"] = pxx
         results["welch_freqs"] = spectrum.freq_axis(args.welch, fs, fc)

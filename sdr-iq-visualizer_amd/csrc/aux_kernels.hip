@@ -6,17 +6,9 @@
 // integer hash so that the numpy mirror in the host package (synth.py) produces
 // the same float32 bits with no device round trip.
 #include "kernels.h"
+#include "synth_hash.h"
 
 namespace sdrk {
-
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
 
 // One thread -> two consecutive samples (one 16-byte store).
 __global__ __launch_bounds__(256) void synth_fill_kernel(uint32_t seed, uint64_t first_frame,
@@ -29,13 +21,15 @@ __global__ __launch_bounds__(256) void synth_fill_kernel(uint32_t seed, uint64_t
         const size_t f = i / pairs_per_frame;
         const uint32_t n = (uint32_t)(i - f * pairs_per_frame) * 2u;
         const uint64_t F = first_frame + f;
-        const uint32_t base = fmix32(seed ^ (uint32_t)F) ^ fmix32((uint32_t)(F >> 32) + 0x9E3779B1u);
-        const uint32_t h0 = fmix32(base ^ n), h1 = fmix32(base ^ (n + 1u));
+        const uint32_t base = synth_frame_base(seed, F);
+        int i0, q0, i1, q1;
+        synth_codes(base, n, i0, q0);
+        synth_codes(base, n + 1u, i1, q1);
         float4 v;
-        v.x = (float)((int)(h0 & 0xFFFu) - 2048);
-        v.y = (float)((int)((h0 >> 12) & 0xFFFu) - 2048);
-        v.z = (float)((int)(h1 & 0xFFFu) - 2048);
-        v.w = (float)((int)((h1 >> 12) & 0xFFFu) - 2048);
+        v.x = (float)i0;
+        v.y = (float)q0;
+        v.z = (float)i1;
+        v.w = (float)q1;
         out[i] = v;
     }
 }

@@ -1,0 +1,170 @@
+// fft4096_ci16.hip — the flagship N = 4096 transform (fft4096.hip) reading interleaved little-endian int16 I,Q: what the
+// AD936x behind the reference's self.sdr.rx() delivers (app/sdr/streamer.py:114) before pyadi-iio widens it, and SigMF's
+// ci16_le.  One HBM read of 4 B/sample and one HBM write of 4 B/sample per frame (the complex64 kernel: 8 + 4).
+//
+//   x[n] = float32(I[n]) + i float32(Q[n])     (exact)
+// then fft4096.hip's arithmetic through the same f4k_transform and epilogues, so the rows and spectra are bit-identical to
+// the complex64 kernel's on the widened samples.
+//
+// Two load forms, the same 16 KiB per workgroup in flight as the one-frame prefetch:
+//   direct  x[tid + 256 j] as one dword per lane, 16 per thread: every wave instruction reads 64 consecutive samples (256 B),
+//           the shape of the kernel's own row stores.  Frame starts need 4-byte alignment only (frame_stride is arbitrary).
+//   WIDE    4 consecutive samples (16 B) per lane, 4 loads per thread (1 KiB per wave instruction); the dwords then go through
+//           the exchange LDS (ds_write_b128 at their sample index, ds_read_b32 at tid + 256 j: both conflict free) to the lanes
+//           that own them, at the price of two more workgroup barriers per frame.  Needs 16-byte aligned frame starts.
+// launch_fft4096_ci16 says which one runs, and what each measured.
+#include "fft4096_core.h"
+#include "kernels_ci16.h"
+
+#ifndef F4K_WINREG
+#define F4K_WINREG 0   // as fft4096.hip
+#endif
+#ifndef F4K_NT
+#define F4K_NT 2       // cache-policy bits of the streaming loads/stores (2 = nt)
+#endif
+
+#include <cstdlib>
+
+namespace sdrk {
+
+constexpr bool CI16_WIDE_DEFAULT = false;
+
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+template <bool HAS_WINDOW, int EPILOGUE, bool WIDE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ci16_kernel(
+    const unsigned* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift) {
+    __shared__ __attribute__((aligned(16))) float2 lds[F4K_XCH_ELEMS + F4K_TW_ELEMS + ((HAS_WINDOW && !F4K_WINREG) ? F4K_N / 2 : 0)];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid, A);
+#if F4K_WINREG
+    float win[16];
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) win[j] = window[tid + 256 * j];
+    }
+#else
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+#endif
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    const int voff_in = tid * 4;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+
+    const size_t first = blockIdx.x;
+    const size_t step = gridDim.x;
+
+    // nxt: the next frame's raw dwords — direct: nxt[j] = x[tid + 256 j]; WIDE: dwords 4 i .. 4 i + 3 = x[1024 i + 4 tid + 0..3]
+    auto issue = [&](unsigned (&x)[16], size_t fr) {
+        if (fr >= n_frames) fr = first;  // harmless re-read past the end
+        __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + fr * frame_stride, F4K_N * 4);
+        if constexpr (WIDE) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const v4u q = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, i * 4096, F4K_NT));
+                x[4 * i] = q.x, x[4 * i + 1] = q.y, x[4 * i + 2] = q.z, x[4 * i + 3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b32(r, voff_in, j * 1024, F4K_NT);
+        }
+    };
+    auto process = [&](unsigned (&x)[16], size_t f) {
+        if constexpr (WIDE) {
+            unsigned* __restrict__ raw = reinterpret_cast<unsigned*>(lds);   // the exchange buffer, 16 KiB of it
+            __syncthreads();   // the previous frame's pass-3 reads of the exchange buffer are done
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const v4u q = {x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
+                *reinterpret_cast<v4u*>(raw + 1024 * i + 4 * tid) = q;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 16; ++j) x[j] = raw[tid + 256 * j];
+            // (f4k_transform's first barrier stands between these reads and its exchange-1 writes)
+        }
+        cf v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            float re, im;
+            ci16_unpack(x[j], re, im);
+            v[j] = cf{re, im};
+        }
+        issue(x, f + step);
+        if (HAS_WINDOW) {
+#if !F4K_WINREG
+            float win[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
+#endif
+            f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
+        } else {
+            f4k_transform(v, lds, tw256, tw1, A, tid);
+        }
+        // ---- epilogue + store: bin k = tid + 256 k2 -> index tid + 256 (k2 ^ xor) ----
+        __amdgpu_buffer_rsrc_t w = frame_rsrc(
+            static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM);
+        if (EPILOGUE == EPI_LOGPSD) {
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                cf z = v[rev16(k2)];
+                float db = logpsd_db(z.x, z.y, eps);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, voff_out,
+                                                      (k2 ^ xor_k2) * 1024, F4K_NT);
+            }
+        } else {
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                cf z = v[rev16(k2)];
+                v2f o = {z.x, z.y};
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), w, voff_out,
+                                                      (k2 ^ xor_k2) * 2048, 0);
+            }
+        }
+    };
+    unsigned nxt[16];
+    issue(nxt, first);
+    for (size_t f = first; f < n_frames; f += step) process(nxt, f);
+}
+
+hipError_t launch_fft4096_ci16(const LaunchArgs& a) {
+    if (a.n_frames == 0) return hipSuccess;
+    // Persistent grid: F4K_WAVES workgroups per CU.
+    size_t max_blocks = (size_t)a.num_cus * F4K_WAVES;
+    unsigned grid = (unsigned)(a.n_frames < max_blocks ? a.n_frames : max_blocks);
+    dim3 g(grid), b(F4K_THREADS);
+    const unsigned* iq = static_cast<const unsigned*>(a.d_iq);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+    // Which load form: measured in one process on 2^20 Hann frames, alternating (tools/bench_ci16.py, profiles/ci16/SUMMARY.md),
+    // direct 7.18 ms, wide 7.38 ms per launch — the two extra barriers per frame cost more than twelve load instructions save.
+    // The direct form is the default; the wide one is kept for A/B work and applies to 16-byte aligned frame starts only.
+    bool wide = CI16_WIDE_DEFAULT;
+    if (const char* env = getenv("SDRK_CI16_FORM")) wide = env[0] == 'w';   // "wide" / "direct": A/B work (tools/bench_ci16.py)
+    if (a.frame_stride % 4 != 0 || reinterpret_cast<uintptr_t>(a.d_iq) % 16 != 0) wide = false;
+#define SDRK_LAUNCH_F(W, E, F)                                                                       \
+    hipLaunchKernelGGL((fft4096_ci16_kernel<W, E, F>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,   \
+                       a.n_frames, a.d_window, tw, a.eps, a.shift)
+#define SDRK_LAUNCH(W, E) do { if (wide) SDRK_LAUNCH_F(W, E, true); else SDRK_LAUNCH_F(W, E, false); } while (0)
+    if (a.epilogue == EPI_LOGPSD) {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
+    } else {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_COMPLEX); else SDRK_LAUNCH(false, EPI_COMPLEX);
+    }
+#undef SDRK_LAUNCH
+#undef SDRK_LAUNCH_F
+    return hipGetLastError();
+}
+
+}  // namespace sdrk

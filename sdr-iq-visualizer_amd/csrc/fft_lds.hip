@@ -18,6 +18,7 @@
 // depth<=4 product tree for its powers.  Persistent grid; the next group's loads are prefetched
 // into registers while the current one is transformed (except at 1024 threads, for VGPRs).
 #include "fft_lds_core.h"
+#include "kernels_ci16.h"
 
 namespace sdrk {
 
@@ -25,7 +26,12 @@ namespace sdrk {
 // x[tau + T q] touches 64 different 128-byte lines per wave instruction, so the group's 4096 contiguous
 // samples are loaded lane-contiguously, parked in LDS (padded by one element per 16) and picked up from
 // there; the rows take the same route out.
-template <int LOG2N, bool HAS_WINDOW, int EPILOGUE, bool STAGED>
+// CI16 (not STAGED; N >= 256): `iq` holds interleaved int16 I,Q instead of complex64 — one dword per sample and load, widened
+// exactly where nxt[] becomes v[] (kernels_ci16.h); everything after that is the complex64 kernel's arithmetic.
+template <bool CI16> struct InWord { typedef v2u type; };        // what one load of a sample delivers
+template <> struct InWord<true> { typedef unsigned type; };
+
+template <int LOG2N, bool HAS_WINDOW, int EPILOGUE, bool STAGED, bool CI16>
 __global__ __launch_bounds__(LdsCfg<LOG2N>::WG, LdsCfg<LOG2N>::WAVES) void fft_lds_kernel(
     const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw, size_t n_frames,
     const float* __restrict__ window, const float2* __restrict__ twN /* W_N^m, m < N */, float eps, int shift) {
@@ -47,22 +53,32 @@ __global__ __launch_bounds__(LdsCfg<LOG2N>::WG, LdsCfg<LOG2N>::WAVES) void fft_l
     // Buffer addressing: a wave-uniform descriptor on the group's F frames, clipped to the frames that
     // exist (lanes of missing frames read zeros and their stores are dropped by the bounds check), one
     // 32-bit lane offset, uniform steps of T elements.
-    const int lane_in = STAGED ? tid * 8 : (int)((size_t)fr * frame_stride + tau) * 8;
+    static_assert(!(CI16 && STAGED), "the int16 input format has no staged form");
+    constexpr int IN_ELEM = CI16 ? 4 : 8;
+    const int lane_in = STAGED ? tid * 8 : (int)((size_t)fr * frame_stride + tau) * IN_ELEM;
     constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
     const int lane_out = STAGED ? tid * OUT_ELEM : (fr * N + tau) * OUT_ELEM;
     constexpr int IN_STEP = STAGED ? 256 : T;   // elements between a thread's consecutive loads
-    v2u nxt[16];
+    typename InWord<CI16>::type nxt[16];
     auto issue_loads = [&](size_t g) {
         const size_t f0 = g * F;
         const size_t valid = n_frames - f0 < (size_t)F ? n_frames - f0 : (size_t)F;
-        const __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + f0 * frame_stride, (unsigned)(((valid - 1) * frame_stride + N) * 8));
+        const __amdgpu_buffer_rsrc_t r = frame_rsrc(reinterpret_cast<const char*>(iq) + f0 * frame_stride * IN_ELEM,
+                                                    (unsigned)(((valid - 1) * frame_stride + N) * IN_ELEM));
 #pragma unroll
-        for (int q = 0; q < 16; ++q) nxt[q] = __builtin_amdgcn_raw_buffer_load_b64(r, lane_in, q * IN_STEP * 8, 2);
+        for (int q = 0; q < 16; ++q) {
+            if constexpr (CI16) nxt[q] = __builtin_amdgcn_raw_buffer_load_b32(r, lane_in, q * IN_STEP * 4, 2);
+            else nxt[q] = __builtin_amdgcn_raw_buffer_load_b64(r, lane_in, q * IN_STEP * 8, 2);
+        }
     };
-    if (C::PREFETCH && blockIdx.x < n_groups) issue_loads(blockIdx.x);
+    // (N = 512 with a window and int16 input: the widening converts on top of the window's loads and eight pass-0 twiddles
+    // need two registers more than three waves per SIMD have when the next group is in flight as well; that one form loads
+    // each group when it gets to it)
+    constexpr bool PREFETCH = C::PREFETCH && !(CI16 && HAS_WINDOW && LOG2N == 9);
+    if (PREFETCH && blockIdx.x < n_groups) issue_loads(blockIdx.x);
 
     for (size_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
-        if (!C::PREFETCH) issue_loads(g);
+        if (!PREFETCH) issue_loads(g);
         cf v[16];
         if constexpr (STAGED) {
             // park element e = tid + 256 q of the group (frame e / N, sample e % N) ...
@@ -90,11 +106,17 @@ __global__ __launch_bounds__(LdsCfg<LOG2N>::WG, LdsCfg<LOG2N>::WAVES) void fft_l
             for (int i = 0; i < C0; ++i)
 #pragma unroll
                 for (int j = 0; j < R0; ++j) {
-                    const v2f t = __builtin_bit_cast(v2f, nxt[i + C0 * j]);
-                    v[i * R0 + j] = cf{t.x, t.y};
+                    if constexpr (CI16) {
+                        float re, im;
+                        ci16_unpack(nxt[i + C0 * j], re, im);
+                        v[i * R0 + j] = cf{re, im};
+                    } else {
+                        const v2f t = __builtin_bit_cast(v2f, nxt[i + C0 * j]);
+                        v[i * R0 + j] = cf{t.x, t.y};
+                    }
                 }
         }
-        if (C::PREFETCH) {
+        if (PREFETCH) {
             const size_t gn = g + gridDim.x;
             issue_loads(gn < n_groups ? gn : g);
         }
@@ -166,7 +188,7 @@ __global__ __launch_bounds__(LdsCfg<LOG2N>::WG, LdsCfg<LOG2N>::WAVES) void fft_l
     }
 }
 
-template <int LOG2N>
+template <int LOG2N, bool CI16 = false>
 static hipError_t launch_lds_n(const LaunchArgs& a) {
     using C = LdsCfg<LOG2N>;
     const size_t n_groups = (a.n_frames + C::F - 1) / C::F;
@@ -183,8 +205,8 @@ static hipError_t launch_lds_n(const LaunchArgs& a) {
     const bool staged = LOG2N <= 7 && a.frame_stride == (size_t)C::N;
 #define SDRK_LDS(W, E)                                                                                        \
     do {                                                                                                      \
-        auto kern = (LOG2N <= 7 && staged) ? fft_lds_kernel<LOG2N, W, E, (LOG2N <= 7)>                        \
-                                            : fft_lds_kernel<LOG2N, W, E, false>;                             \
+        auto kern = (LOG2N <= 7 && staged) ? fft_lds_kernel<LOG2N, W, E, (LOG2N <= 7), false>                 \
+                                            : fft_lds_kernel<LOG2N, W, E, false, CI16>;                       \
         static std::atomic<uint64_t> lds_ok{0};   /* per instantiation, one bit per device */                  \
         hipError_t e0 = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes, lds_ok);           \
         if (e0 != hipSuccess) return e0;                                                                      \
@@ -219,6 +241,28 @@ hipError_t launch_fft_lds(const LaunchArgs& a) {
         case 2048: return launch_lds_n<11>(a);
         case 8192: return launch_lds_n<13>(a);
         case 16384: return launch_lds_n<14>(a);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// The int16 input format: the lengths whose frames take at least one whole wave (N >= 256); shorter frames, like every other
+// length without a kernel of its own, are widened by unpack_ci16_kernel first (ci16_api.hip).
+bool fft_lds_ci16_supports(int nfft, size_t frame_stride) {
+    if (!fft_lds_supports(nfft) || nfft < 256) return false;
+    // (as launch_fft_lds: one descriptor per group of frames, 32-bit lane offsets)
+    return nfft >= 4096 || ((size_t)(4096 / nfft) * frame_stride + (size_t)nfft) * 4 < ((size_t)1 << 31);
+}
+
+hipError_t launch_fft_lds_ci16(const LaunchArgs& a) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (!fft_lds_ci16_supports(a.nfft, a.frame_stride)) return hipErrorInvalidValue;
+    switch (a.nfft) {
+        case 256: return launch_lds_n<8, true>(a);
+        case 512: return launch_lds_n<9, true>(a);
+        case 1024: return launch_lds_n<10, true>(a);
+        case 2048: return launch_lds_n<11, true>(a);
+        case 8192: return launch_lds_n<13, true>(a);
+        case 16384: return launch_lds_n<14, true>(a);
         default: return hipErrorInvalidValue;
     }
 }

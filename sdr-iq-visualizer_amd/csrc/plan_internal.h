@@ -86,6 +86,13 @@ struct sdrk_plan {
     double* d_window64 = nullptr;   // nfft doubles, or nullptr for rectangular
     double* d_tw64 = nullptr;       // W_4096^m, m < 4096, complex128 (interleaved)
     void* d_scratch64 = nullptr;    // two-pass lengths: scratch_frames * nfft complex128
+    // int16 input (ci16_api.hip) at the lengths without an int16-reading kernel: complex64 staging the frames are widened
+    // into, at most 64 MiB, only grows; ev_ci16 follows the last work enqueued on it (on ci16_stream)
+    void* d_ci16 = nullptr;
+    size_t ci16_cap = 0;
+    hipEvent_t ev_ci16 = nullptr;
+    hipStream_t ci16_stream = nullptr;
+    bool ci16_busy = false;
 };
 
 namespace sdrk_host {
@@ -135,12 +142,14 @@ int grow(int device, void** buf, size_t* cap, size_t need);   // device staging 
 int check_precision(const sdrk_plan* p, int precision);
 // NULL plan, plan of another precision, NULL buffers, zero stride
 int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out, int precision = 32);
-bool takes_fused(const sdrk_plan* p, size_t n_frames);   // the persistent N = 65536 kernel for this many frames?
+bool takes_fused(const sdrk_plan* p, size_t n_frames);   // the persistent N = 65536 kernel for a call of this many frames?
 struct EpiArgs;   // chirp-z epilogues riding on an inner plan's row pass (sdrk_plan.hip)
 // One float32 transform of the plan.  d_mip / mip_written: see LaunchArgs (kernels.h) — *mip_written tells whether the launch
-// wrote the by-16 companion rows.
+// wrote the by-16 companion rows.  call_frames: when this launch is one chunk of a larger call, the frames of that call — the
+// N = 65536 form is picked for the call (takes_fused), so that its chunks do not each fall under the threshold (0: n_frames).
 int plan_launch(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out, int epilogue,
-                hipStream_t stream, float* d_mip = nullptr, bool* mip_written = nullptr, const EpiArgs* epi = nullptr);
+                hipStream_t stream, float* d_mip = nullptr, bool* mip_written = nullptr, const EpiArgs* epi = nullptr,
+                size_t call_frames = 0);
 int fused_check(sdrk_plan* p);   // after a stream sync: the fused launches since the last check
 
 // ---- sdrk_probes.hip ----
@@ -157,6 +166,7 @@ struct HostIo {
     int epilogue = 0;              // handed to `launch`
     int precision = 32;            // the plan kind the entry point serves (32 / 64)
     int zero_copy_max_nfft = 0;    // longest frame whose kernel may read / write pinned host memory itself
+    int zero_copy_min_nfft = 0;    // ... and the shortest
     LaunchFn launch = nullptr;
 };
 

@@ -183,9 +183,10 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     // Caller arrays in pinned memory (sdrk_host_alloc / sdrk_host_register) are not staged: the copy engines read
     // and write them directly.  Decided per side.
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
-    const bool zero_copy = p->nfft <= io.zero_copy_max_nfft && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES &&
+    const bool zc_length = p->nfft <= io.zero_copy_max_nfft && p->nfft >= io.zero_copy_min_nfft;
+    const bool zero_copy = zc_length && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES &&
                            !in_pinned && !out_pinned;
-    if (in_pinned && out_pinned && p->nfft <= io.zero_copy_max_nfft && !p->blu_inner && frame_stride >= nfft &&
+    if (in_pinned && out_pinned && zc_length && !p->blu_inner && frame_stride >= nfft &&
         in_bytes <= ZERO_COPY_MAX_BYTES) {
         // both arrays pinned, a call small enough that the link's latency matters more than its last 10 %: ONE launch
         // that reads the caller's frames and writes the caller's rows over PCIe — no staging, no copy engine, no chunks

@@ -82,7 +82,7 @@ FusedGate& fused_gate(int device) {
 }
 
 int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
-                     int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi);
+                     int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi, size_t call_frames);
 
 }  // namespace
 
@@ -93,17 +93,18 @@ bool takes_fused(const sdrk_plan* p, size_t n_frames) {
 
 // d_mip / mip_written: see LaunchArgs (kernels.h) — *mip_written tells whether the launch wrote the by-16 companion rows.
 int plan_launch(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
-                int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi) {
+                int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi, size_t call_frames) {
     if (p->precision != 32) return fail(SDRK_ERR_INVALID, "float32 transform requested of a float64 plan");
     RoctxRange range(p, n_frames, frame_stride, epilogue);
     if (mip_written) *mip_written = false;
-    return plan_launch_impl(p, d_iq, n_frames, frame_stride, d_out, epilogue, stream, d_mip, mip_written, epi);
+    return plan_launch_impl(p, d_iq, n_frames, frame_stride, d_out, epilogue, stream, d_mip, mip_written, epi,
+                            call_frames > n_frames ? call_frames : n_frames);
 }
 
 namespace {
 
 int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
-                     int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi) {
+                     int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi, size_t call_frames) {
     sdrk::LaunchArgs a;
     a.d_mip = d_mip;
     a.mip_written = mip_written;
@@ -193,7 +194,7 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
         e = sdrk::launch_fft_lds(a);
     else if (p->nfft < 4096)
         e = sdrk::launch_fft_small(a);
-    else if (takes_fused(p, n_frames) && !d_mip && epilogue <= sdrk::EPI_COMPLEX) {
+    else if (takes_fused(p, call_frames) && !d_mip && epilogue <= sdrk::EPI_COMPLEX) {
         // The persistent grid needs every one of its workgroups resident at the same time; two such grids on two streams could
         // each hold part of the device and wait for the rest.  One at a time per device: each launch waits for the one before.
         FusedGate& gate = fused_gate(p->device);
@@ -514,6 +515,8 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_in) (void)hipFree(p->d_in);
     if (p->d_out) (void)hipFree(p->d_out);
     if (p->d_feat) (void)hipFree(p->d_feat);
+    if (p->d_ci16) (void)hipFree(p->d_ci16);
+    if (p->ev_ci16) (void)hipEventDestroy(p->ev_ci16);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {

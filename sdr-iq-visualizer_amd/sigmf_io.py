@@ -1,4 +1,6 @@
-"""Minimal SigMF reader/writer for ``cf32_le`` recordings (BASELINE.json config 1).
+"""Minimal SigMF reader/writer for ``cf32_le`` recordings (BASELINE.json config 1), and for ``ci16_le`` ones in their own
+format (``write_sigmf(..., datatype="ci16_le")``, ``read_sigmf(..., native=True)`` -> the ``(n, 2)`` int16 array the
+``*_ci16`` spectrum functions take).
 
 Format = what the reference's dashboard exports (app/dashboard/callbacks.py:285-319):
 a ``.sigmf-data`` file of interleaved little-endian float32 I,Q and a ``.sigmf-meta``
@@ -25,12 +27,13 @@ _DTYPES = {"cf32_le": np.dtype("<c8"), "cf64_le": np.dtype("<c16"),
 
 
 def make_metadata(sample_rate: float, center_freq: float, *, description: str = "IQ recording",
-                  author: str = "sdr_iq_visualizer_amd", hw: str = "", when: Optional[datetime] = None) -> dict:
+                  author: str = "sdr_iq_visualizer_amd", hw: str = "", when: Optional[datetime] = None,
+                  datatype: str = "cf32_le") -> dict:
     """Metadata dict with the keys of app/dashboard/callbacks.py:285-304."""
     when = when or datetime.now(timezone.utc)
     return {
         "global": {
-            "core:datatype": "cf32_le",
+            "core:datatype": datatype,
             "core:sample_rate": int(sample_rate),
             "core:version": "1.0.0",
             "core:description": description,
@@ -47,12 +50,34 @@ def make_metadata(sample_rate: float, center_freq: float, *, description: str = 
     }
 
 
-def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float, **meta_kw) -> Tuple[str, str]:
-    """Write ``<base>.sigmf-data`` (cf32_le) and ``<base>.sigmf-meta``; returns both paths."""
+def _to_ci16(samples) -> np.ndarray:
+    """``(n, 2)`` little-endian int16 from an int16 ``(..., 2)`` array (as is) or from complex / integer samples whose
+    parts are whole numbers in the int16 range (anything else would lose information: ValueError)."""
+    x = np.asarray(samples)
+    if x.dtype == np.int16 and x.ndim >= 2 and x.shape[-1] == 2:
+        return np.ascontiguousarray(x.reshape(-1, 2)).astype("<i2", copy=False)
+    z = x.reshape(-1).astype(np.complex128)
+    parts = np.stack([z.real, z.imag], axis=-1)
+    if not np.all(parts == np.rint(parts)) or parts.min(initial=0) < -32768 or parts.max(initial=0) > 32767:
+        raise ValueError("datatype='ci16_le' needs samples whose I and Q are integers in [-32768, 32767]")
+    return parts.astype("<i2")
+
+
+def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float, datatype: str = "cf32_le",
+                **meta_kw) -> Tuple[str, str]:
+    """Write ``<base>.sigmf-data`` (cf32_le, or ci16_le on request: interleaved int16 I,Q from an int16 ``(n, 2)`` array or
+    from integer-valued complex samples) and ``<base>.sigmf-meta``; returns both paths."""
+    if datatype not in ("cf32_le", "ci16_le"):
+        raise ValueError(f"write_sigmf writes 'cf32_le' or 'ci16_le', not {datatype!r}")
+    data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
+    if datatype == "ci16_le":
+        _to_ci16(samples).tofile(data_path)
+        with open(meta_path, "w") as fh:
+            json.dump(make_metadata(sample_rate, center_freq, datatype="ci16_le", **meta_kw), fh, indent=2)
+        return data_path, meta_path
     x = np.asarray(samples)
     if x.dtype != np.complex64:                       # callbacks.py:307-308
         x = x.astype(np.complex64)
-    data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
     x.astype("<c8", copy=False).tofile(data_path)     # callbacks.py:310 (tobytes)
     with open(meta_path, "w") as fh:
         json.dump(make_metadata(sample_rate, center_freq, **meta_kw), fh, indent=2)
@@ -68,10 +93,12 @@ def _decode(raw: bytes, datatype: str) -> np.ndarray:
     return a.astype(np.complex64, copy=False)
 
 
-def read_sigmf(path: str, max_samples: Optional[int] = None) -> Tuple[np.ndarray, dict]:
+def read_sigmf(path: str, max_samples: Optional[int] = None, native: bool = False) -> Tuple[np.ndarray, dict]:
     """Read a recording given its ``.sigmf-meta``, ``.sigmf-data``, base name, or the
     ``.zip`` the dashboard's download button produces.  Returns ``(samples complex64, meta)``;
-    ``meta['sample_rate']`` and ``meta['center_freq']`` are lifted out for convenience."""
+    ``meta['sample_rate']`` and ``meta['center_freq']`` are lifted out for convenience.
+    ``native=True``: a ``ci16_le`` recording comes back as its own ``(n, 2)`` int16 array, not widened (for the ``*_ci16``
+    spectrum functions); every other datatype as without it."""
     if path.endswith(".zip"):
         with zipfile.ZipFile(path) as z:
             names = z.namelist()
@@ -90,7 +117,11 @@ def read_sigmf(path: str, max_samples: Optional[int] = None) -> Tuple[np.ndarray
         with open(base + ".sigmf-data", "rb") as fh:
             raw = fh.read() if max_samples is None else fh.read(int(max_samples) * itemsize * 2)
     g = meta.get("global", {})
-    samples = _decode(raw, g.get("core:datatype", "cf32_le"))
+    if native and g.get("core:datatype") == "ci16_le":
+        a = np.frombuffer(raw, dtype="<i2")
+        samples = a[: a.size // 2 * 2].reshape(-1, 2).astype(np.int16, copy=False)
+    else:
+        samples = _decode(raw, g.get("core:datatype", "cf32_le"))
     if max_samples is not None:
         samples = samples[: int(max_samples)]
     caps = meta.get("captures") or [{}]

@@ -22,6 +22,11 @@ csrc/fft_f64.hip.  ``precision="auto"`` picks by the input's dtype as numpy's FF
 does — complex64 / float32 / float16 single, everything else (complex128, float64,
 integers) double — so the reference's complex128 samples get float64 rows.
 
+``*_ci16`` (plan methods and module functions) take what the radio produces before pyadi-iio widens it, and what SigMF
+calls ``ci16_le``: a C-contiguous int16 array whose last axis holds (I, Q).  ``x = float32(I) + 1j*float32(Q)`` exactly, then
+the float32 path — the result has the same bits as the complex64 call on the widened samples, from half the input bytes.
+No scale is applied (fold 1/32768 into a custom window, or add a constant to the dB rows).
+
 All arithmetic on samples happens on the GPU through ``libsdrk.so``; nothing in
 this module computes a spectrum with numpy, and every entry point raises if the
 library or a device is missing.
@@ -92,6 +97,25 @@ def _as_c128(a) -> np.ndarray:
     if arr.dtype != np.complex128:
         arr = arr.astype(np.complex128)
     return np.ascontiguousarray(arr)
+
+
+def _as_ci16(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
+    """Check an int16 I,Q array (no copy, no conversion): C-contiguous int16, last axis of length 2; ``(nfft, 2)`` or
+    ``(B, nfft, 2)`` for frames, ``(n_samples, 2)`` for a stream.  Anything else is a ValueError, before any device call."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.int16:
+        raise ValueError(f"ci16 input must be a numpy int16 array of (I, Q) pairs, got "
+                         f"{getattr(a, 'dtype', type(a).__name__)}")
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError(f"ci16 input must have a last axis of length 2 (I, Q), got shape {a.shape}")
+    if not a.flags.c_contiguous:
+        raise ValueError("ci16 input must be C-contiguous (interleaved I, Q)")
+    if stream:
+        if a.ndim != 2:
+            raise ValueError(f"ci16 stream must have shape (n_samples, 2), got {a.shape}")
+    elif a.ndim > 3 or (nfft is not None and a.shape[-2] != nfft):
+        want = "(N, 2) or (B, N, 2)" if nfft is None else f"({nfft}, 2) or (B, {nfft}, 2)"
+        raise ValueError(f"ci16 frames must have shape {want}, got {a.shape}")
+    return a
 
 
 class SpectrumPlan:
@@ -249,6 +273,68 @@ class SpectrumPlan:
         if rows:
             self._run_host(self._exec_host_fn(), x, rows, hop, out)
         return out
+
+    # -- int16 I,Q input (float32 plans; same bits as the complex64 calls on the widened samples) --------------
+    def _frames_ci16(self, iq):
+        x = _as_ci16(iq, self.nfft)
+        self._float32_only("ci16 input")
+        return (x.reshape(1, self.nfft, 2), True) if x.ndim == 2 else (x, False)
+
+    def spectrum_db_ci16(self, iq, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """float32 rows of int16 I,Q frames ``(nfft, 2)`` or ``(B, nfft, 2)``: bit-identical to ``spectrum_db`` on
+        ``float32(I) + 1j*float32(Q)``."""
+        x, one = self._frames_ci16(iq)
+        res = self._out_array(out, (self.nfft,) if one else x.shape[:2], np.float32)
+        if x.shape[0]:
+            self._run_host(lib().sdrk_exec_host_ci16, x, x.shape[0], self.nfft, res)
+        return res
+
+    def fft_ci16(self, iq) -> np.ndarray:
+        """complex64 spectrum of int16 I,Q frames: bit-identical to ``fft`` on the widened samples."""
+        x, one = self._frames_ci16(iq)
+        out = np.empty(x.shape[:2], dtype=np.complex64)
+        if x.shape[0]:
+            self._run_host(lib().sdrk_exec_fft_host_ci16, x, x.shape[0], self.nfft, out)
+        return out[0] if one else out
+
+    def stft_db_ci16(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Spectrogram rows over one contiguous int16 I,Q stream ``(n_samples, 2)``; rows as ``stft_db``."""
+        x = _as_ci16(iq, stream=True)
+        self._float32_only("ci16 input")
+        hop = self.nfft if hop is None else int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        rows = 0 if x.shape[0] < self.nfft else 1 + (x.shape[0] - self.nfft) // hop
+        out = self._out_array(out, (rows, self.nfft), np.float32)
+        if rows:
+            self._run_host(lib().sdrk_exec_host_ci16, x, rows, hop, out)
+        return out
+
+    def exec_device_ci16(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
+                         stream: int = 0) -> None:
+        """Device pointers: int16 I,Q in (4 bytes per sample) / float32 rows out, asynchronous on ``stream`` (0: the
+        plan's stream); any number of frames."""
+        self._float32_only("ci16 input")
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_ci16(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                              c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def exec_device_ci16_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
+                                    frame_stride: Optional[int] = None) -> list:
+        """``exec_device_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        self._float32_only("ci16 input")
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                                         c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
+    def exec_device_ci16_timed(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
+                               frame_stride: Optional[int] = None) -> float:
+        """The same, all launches together (the sum of the per-launch times)."""
+        return float(sum(self.exec_device_ci16_timed_each(d_iq, n_frames, d_out, launches, frame_stride=frame_stride)))
 
     def welch_psd(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
         """Averaged periodogram of one contiguous stream, float32 ``(nfft,)``:
@@ -433,6 +519,29 @@ def fft_c64(samples, *, window: WindowArg = None, shift: bool = False, device: i
     log), optionally fftshifted."""
     nfft = _nfft_of(samples)
     return _cached_plan(nfft, window, 1e-12, shift, device).fft(samples)
+
+
+def spectrum_db_ci16(iq, *, window: WindowArg = None, eps: float = 1e-12, shift: bool = True, device: int = 0,
+                     out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``spectrum_db`` for int16 I,Q frames ``(N, 2)`` or ``(B, N, 2)`` as the radio delivers them (the AD936x behind
+    app/sdr/streamer.py:114; SigMF ``ci16_le``): float32 rows with exactly the bits of
+    ``spectrum_db((iq[..., 0] + 1j*iq[..., 1]).astype(complex64))``, from half the input bytes.  No scaling to full scale;
+    one device (no ``devices=[...]``)."""
+    x = _as_ci16(iq)
+    return _cached_plan(int(x.shape[-2]), window, eps, shift, device).spectrum_db_ci16(x, out=out)
+
+
+def fft_ci16(iq, *, window: WindowArg = None, shift: bool = False, device: int = 0) -> np.ndarray:
+    """``fft_c64`` for int16 I,Q frames ``(N, 2)`` or ``(B, N, 2)``: the same bits as on the widened samples."""
+    x = _as_ci16(iq)
+    return _cached_plan(int(x.shape[-2]), window, 1e-12, shift, device).fft_ci16(x)
+
+
+def stft_db_ci16(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,
+                 shift: bool = True, device: int = 0) -> np.ndarray:
+    """``stft_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit."""
+    x = _as_ci16(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).stft_db_ci16(x, hop)
 
 
 def fft_c128(samples, *, window: WindowArg = None, shift: bool = False, device: int = 0) -> np.ndarray:

@@ -30,8 +30,8 @@ def fmix32(h: np.ndarray) -> np.ndarray:
     return h
 
 
-def synth_iq(seed: int, first_frame: int, n_frames: int, nfft: int) -> np.ndarray:
-    """complex64 ``(n_frames, nfft)`` — bit-identical to sdrk_synth_fill."""
+def _codes(seed: int, first_frame: int, n_frames: int, nfft: int):
+    """The generator's integers: int64 (I, Q), each ``(n_frames, nfft)`` in [-2048, 2047]."""
     F = np.uint64(first_frame) + np.arange(n_frames, dtype=np.uint64)
     lo, hi = F & _M32, F >> np.uint64(32)
     base = fmix32(np.uint64(seed & 0xFFFFFFFF) ^ lo) ^ fmix32((hi + np.uint64(0x9E3779B1)) & _M32)
@@ -39,9 +39,25 @@ def synth_iq(seed: int, first_frame: int, n_frames: int, nfft: int) -> np.ndarra
     h = fmix32(base[:, None] ^ n[None, :])
     i = (h & np.uint64(0xFFF)).astype(np.int64) - 2048
     q = ((h >> np.uint64(12)) & np.uint64(0xFFF)).astype(np.int64) - 2048
+    return i, q
+
+
+def synth_iq(seed: int, first_frame: int, n_frames: int, nfft: int) -> np.ndarray:
+    """complex64 ``(n_frames, nfft)`` — bit-identical to sdrk_synth_fill."""
+    i, q = _codes(seed, first_frame, n_frames, nfft)
     out = np.empty((n_frames, nfft), dtype=np.complex64)
     out.real = i.astype(np.float32)
     out.imag = q.astype(np.float32)
+    return out
+
+
+def synth_iq_ci16(seed: int, first_frame: int, n_frames: int, nfft: int) -> np.ndarray:
+    """int16 ``(n_frames, nfft, 2)`` of (I, Q) — the same values as ``synth_iq`` in the radio's own format, bit-identical
+    to sdrk_synth_fill_ci16."""
+    i, q = _codes(seed, first_frame, n_frames, nfft)
+    out = np.empty((n_frames, nfft, 2), dtype=np.int16)
+    out[..., 0] = i
+    out[..., 1] = q
     return out
 
 

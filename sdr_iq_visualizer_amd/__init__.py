@@ -20,10 +20,13 @@ from .spectrum import (  # noqa: E402
     SpectrumPlan,
     fft_c64,
     fft_c128,
+    fft_ci16,
     freq_axis,
     process_frame,
     spectrum_db,
+    spectrum_db_ci16,
     stft_db,
+    stft_db_ci16,
     welch_psd,
 )
 from .waterfall import WaterfallBuffer  # noqa: E402
@@ -38,6 +41,7 @@ __all__ = [
     "device_info",
     "fft_c64",
     "fft_c128",
+    "fft_ci16",
     "freq_axis",
     "is_pinned",
     "library_path",
@@ -45,6 +49,8 @@ __all__ = [
     "process_frame",
     "registered",
     "spectrum_db",
+    "spectrum_db_ci16",
     "stft_db",
+    "stft_db_ci16",
     "welch_psd",
 ]
