@@ -275,6 +275,35 @@ int sdrk_exec_device_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, siz
 int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,
                          void* stream);
 
+/* ---- integrated spectra: one row per K frames ---------------------------------------
+ * What a spectrum analyser does with the rows of streamer.py:119-121 before anybody looks at them: average the power of K
+ * consecutive frames (video averaging; Welch, scripts/process_sigmf_data.py:188-189), or hold the maximum (peak hold) or
+ * the minimum (noise floor) per bin.  Frames are cut as for sdrk_exec_device — frame f at sample f*frame_stride, any stride
+ * >= 1 — and group g is the frames [g*k_frames, (g+1)*k_frames).  With p_f[k] = |fft(w*x_f)[k]|^2,
+ *     SDRK_DET_MEAN  R[k] = (1/K) sum_f p_f[k]        SDRK_DET_MAX  R[k] = max_f p_f[k]        SDRK_DET_MIN  R[k] = min_f p_f[k]
+ * and the row of a group, float32[nfft] in the plan's shift order, is
+ *     SDRK_INT_OUT_DB     20*log10(sqrt(R[k]) + eps)    (the plan's own expression on the RMS / largest / smallest magnitude;
+ *                                                        K = 1 is the ordinary row)
+ *     SDRK_INT_OUT_POWER  scale * R[k]                  (with scale = 1/(Fs*sum(w^2)) and MEAN: matplotlib's mlab.psd)
+ * `scale` is ignored for SDRK_INT_OUT_DB.  Any k_frames >= 1 and n_groups >= 1; the device entry has no frame limit (the
+ * plan's max_batch does not apply) and the host entry runs in device memory that does not depend on the stream length.
+ * The mean is a compensated sum; there are no floating-point atomics: the same input gives the same bits, from the device
+ * entry and from the host entry alike.  Served by float32 plans of every nfft (N = 4096 inside the transform's registers,
+ * other lengths through plan-owned staging of at most 64 MiB); an f64 plan, an unknown detector or form and zero counts
+ * return SDRK_ERR_INVALID. */
+enum sdrk_detector { SDRK_DET_MEAN = 0, SDRK_DET_MAX = 1, SDRK_DET_MIN = 2 };
+enum sdrk_int_out { SDRK_INT_OUT_DB = 0, SDRK_INT_OUT_POWER = 1 };
+/* device in / device out (d_out: n_groups * nfft float32), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_integrated(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                int detector, int out_form, float scale, float* d_out, void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` calls (bench harness) */
+int sdrk_exec_device_integrated_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames,
+                                           size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                           int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
+int sdrk_exec_host_integrated(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                              int detector, int out_form, float scale, float* out);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

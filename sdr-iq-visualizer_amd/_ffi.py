@@ -35,6 +35,8 @@ FEAT_PLANES = 19                  # SDRK_FEAT_* plane numbers of include/sdrk.h
 (FEAT_MAX_DB, FEAT_NOISE_FLOOR_DB, FEAT_SNR_DB, FEAT_FLATNESS, FEAT_KURTOSIS, FEAT_THRESHOLD_DB, FEAT_PEAK_SPACING_STD_HZ,
  FEAT_PEAK_DENSITY, FEAT_BANDWIDTH_HZ) = range(9)
 FEAT_ARGMAX, FEAT_PEAK_COUNT, FEAT_OCCUPIED_BINS = 11, 12, 13
+DETECTORS = {"mean": 0, "max": 1, "min": 2}   # SDRK_DET_*
+INT_OUT_FORMS = {"db": 0, "power": 1}         # SDRK_INT_OUT_*
 PLAN_FUSED64K = 0x1
 PLAN_OVERLAP_PASSES = 0x2
 PLAN_TUNE_STAGING = 0x4
@@ -137,6 +139,13 @@ SYMBOLS = [
     ("sdrk_exec_device_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     ("sdrk_exec_device_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_synth_fill_ci16", c_int, [c_int, c_uint32, c_uint64, c_size_t, c_int, c_void_p, c_void_p]),
+    # one row per K frames: mean / max / min of the power inside the transform
+    ("sdrk_exec_device_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                            c_void_p, c_void_p]),
+    ("sdrk_exec_device_integrated_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                       c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                          c_void_p]),
 ]
 
 _lib = None

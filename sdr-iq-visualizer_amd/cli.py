@@ -1,6 +1,6 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
-    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
@@ -16,6 +16,13 @@ import sys
 import numpy as np
 
 
+def _positive(text: str) -> int:
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+    return v
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="sdr_iq_visualizer_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -23,6 +30,9 @@ def main(argv=None) -> int:
     p.add_argument("path")
     p.add_argument("--nfft", type=int, default=4096)
     p.add_argument("--welch", type=int, default=0, help="also compute the averaged PSD with this NFFT (Hann)")
+    p.add_argument("--integrate", type=_positive, default=0, metavar="K",
+                   help="also write one dB row per K frames of --nfft samples (integrated_db)")
+    p.add_argument("--detector", choices=["mean", "max", "min"], default="mean", help="what --integrate keeps per bin")
     p.add_argument("--window", default=None)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--out", default=None, help="write results to this .npz")
@@ -72,6 +82,17 @@ def main(argv=None) -> int:
         report["welch_nfft"] = args.welch
         report["welch_segments"] = 1 + (samples.size - args.welch) // args.welch
         report["welch_peak_db_per_hz"] = float(10 * np.log10(pxx.max()))
+    if args.integrate:
+        if raw16 is not None and samples.dtype == np.int16:
+            samples = raw16.astype(np.float32).view(np.complex64).reshape(-1)
+        rows = spectrum.integrated_db(samples, args.nfft, args.integrate, detector=args.detector, window=args.window,
+                                      device=args.device)
+        results["integrated_db"] = rows
+        report["integrate_k"] = args.integrate
+        report["integrate_detector"] = args.detector
+        report["integrated_rows"] = int(rows.shape[0])
+        if rows.shape[0] == 0:
+            print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no integrated row", file=sys.stderr)
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out

@@ -93,6 +93,16 @@ struct sdrk_plan {
     hipEvent_t ev_ci16 = nullptr;
     hipStream_t ci16_stream = nullptr;
     bool ci16_busy = false;
+    // integrated spectra (integrate_api.hip): d_int_state = two carry rows + the partial rows of split groups; d_int_stage =
+    // complex64 spectra of the lengths without a fused kernel, at most 64 MiB; both only grow; ev_int follows the last work
+    // enqueued on them (on int_stream)
+    void* d_int_state = nullptr;
+    size_t int_state_cap = 0;
+    void* d_int_stage = nullptr;
+    size_t int_stage_cap = 0;
+    hipEvent_t ev_int = nullptr;
+    hipStream_t int_stream = nullptr;
+    bool int_busy = false;
 };
 
 namespace sdrk_host {

@@ -517,6 +517,9 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_feat) (void)hipFree(p->d_feat);
     if (p->d_ci16) (void)hipFree(p->d_ci16);
     if (p->ev_ci16) (void)hipEventDestroy(p->ev_ci16);
+    if (p->d_int_state) (void)hipFree(p->d_int_state);
+    if (p->d_int_stage) (void)hipFree(p->d_int_stage);
+    if (p->ev_int) (void)hipEventDestroy(p->ev_int);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {

@@ -7,9 +7,9 @@ the waterfall at app/dashboard/callbacks.py:176-182.  A maintainer switching to
 this build imports these names there (INTEGRATION.md shows the three-line
 change); the Dash callbacks keep reading the same ``plot_data`` dict.
 """
-from .spectrum import (fft_c64, fft_ci16, freq_axis, process_frame, spectrum_db, spectrum_db_ci16, stft_db,  # noqa: F401
-                       stft_db_ci16, welch_psd)
+from .spectrum import (fft_c64, fft_ci16, freq_axis, integrated_db, process_frame, spectrum_db,  # noqa: F401
+                       spectrum_db_ci16, stft_db, stft_db_ci16, welch_psd, welch_psd_streamed)
 from .waterfall import WaterfallBuffer  # noqa: F401
 
 __all__ = ["spectrum_db", "fft_c64", "freq_axis", "process_frame", "stft_db", "welch_psd", "WaterfallBuffer",
-           "spectrum_db_ci16", "fft_ci16", "stft_db_ci16"]
+           "spectrum_db_ci16", "fft_ci16", "stft_db_ci16", "integrated_db", "welch_psd_streamed"]

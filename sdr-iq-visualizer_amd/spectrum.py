@@ -364,6 +364,94 @@ class SpectrumPlan:
                                             c_float(scale), out.ctypes.data_as(c_void_p)))
         return out
 
+    # -- integrated spectra: one row per k frames (float32 plans) ---------------------------------------------
+    @staticmethod
+    def _int_codes(detector: str, out: str):
+        if detector not in _ffi.DETECTORS:
+            raise ValueError(f"detector must be one of {sorted(_ffi.DETECTORS)}, got {detector!r}")
+        if out not in _ffi.INT_OUT_FORMS:
+            raise ValueError(f"out must be one of {sorted(_ffi.INT_OUT_FORMS)}, got {out!r}")
+        return _ffi.DETECTORS[detector], _ffi.INT_OUT_FORMS[out]
+
+    def integrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
+        """Rows ``integrate`` returns for a stream of ``n_samples``: the ``1 + (n - nfft)//hop`` full frames in whole
+        groups of ``k``; trailing frames that do not fill a group are dropped (as ``mlab.psd`` drops a partial segment)."""
+        hop = self.nfft if hop is None else int(hop)
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        frames = 0 if n_samples < self.nfft else 1 + (int(n_samples) - self.nfft) // hop
+        return frames // int(k)
+
+    def integrate(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                  scale: float = 1.0) -> np.ndarray:
+        """One float32 row per ``k`` consecutive frames of one contiguous stream, ``(groups, nfft)``: per bin the mean
+        (``detector="mean"``), maximum or minimum over the group's frames of ``|fft(w*x_f)|^2``, returned as
+        ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``).  Frame f covers samples
+        ``[f*hop, f*hop + nfft)``.  The reduction runs inside the transform on the GPU; the stream goes through in
+        chunks, in device memory that does not depend on its length."""
+        self._float32_only("integrate")
+        det, form = self._int_codes(detector, out)
+        x = _as_c64(iq).reshape(-1)
+        hop = self.nfft if hop is None else int(hop)
+        groups = self.integrated_groups(x.shape[0], k, hop)
+        res = np.empty((groups, self.nfft), dtype=np.float32)
+        if groups:
+            with self._lock:
+                check(lib().sdrk_exec_host_integrated(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
+                                                      c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
+                                                      res.ctypes.data_as(c_void_p)))
+        return res
+
+    def exec_device_integrated(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                               detector: str = "mean", out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: complex64 in, ``n_groups`` float32 rows out (one per ``k`` frames), asynchronous on
+        ``stream`` (0: the plan's stream); any number of frames."""
+        self._float32_only("integrate")
+        det, form = self._int_codes(detector, out)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_integrated(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
+                                                    c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
+                                                    c_void_p(stream) if stream else None))
+
+    def exec_device_integrated_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                          frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                          scale: float = 1.0) -> list:
+        """``exec_device_integrated`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        self._float32_only("integrate")
+        det, form = self._int_codes(detector, out)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_integrated_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
+                                                               c_size_t(int(k)), c_size_t(stride), det, form,
+                                                               c_float(scale), c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
+    def window_power(self) -> float:
+        """``sum(w^2)`` of the plan's window (float64)."""
+        if self._wkey == "rect":
+            return float(self.nfft)
+        if self._wkey == "hann":
+            return float(np.sum(np.hanning(self.nfft) ** 2))
+        return float(np.sum(np.frombuffer(self._wkey[1], dtype=np.float32).astype(np.float64) ** 2))
+
+    def welch_psd_streamed(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
+        """``welch_psd`` through the integrated path: one group of all full segments, mean, linear power.  No
+        ``max_batch`` limit, and the stream is not staged whole on the device."""
+        self._float32_only("welch_psd_streamed")
+        x = _as_c64(iq).reshape(-1)
+        hop = self.nfft if hop is None else int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        if x.shape[0] < self.nfft:
+            raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {self.nfft}-sample segment")
+        rows = 1 + (x.shape[0] - self.nfft) // hop
+        scale = 1.0 / (float(sample_rate) * self.window_power())
+        return self.integrate(x, rows, hop, "mean", "power", scale)[0]
+
     # -- device pointers (bench / pipelines that keep data resident) -------------
     def exec_device(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                     stream: int = 0) -> None:
@@ -603,6 +691,19 @@ def welch_psd(iq, nfft: int, sample_rate: float, hop: Optional[int] = None, wind
     reference's offline plots (scripts/process_sigmf_data.py:188-189: NFFT=1024, Hann,
     noverlap=0).  Returns float32 ``(nfft,)`` in fftshift order (use ``freq_axis`` for x)."""
     return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd(iq, sample_rate, hop)
+
+
+def integrated_db(iq, nfft: int, k: int, hop: Optional[int] = None, detector: str = "mean", window: WindowArg = None,
+                  eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """dB rows of a spectrogram whose time axis is reduced on the device: one row per ``k`` frames of ``iq``, the
+    mean / max / min power per bin (``SpectrumPlan.integrate``)."""
+    return _cached_plan(int(nfft), window, eps, shift, device).integrate(iq, k, hop, detector, "db")
+
+
+def welch_psd_streamed(iq, nfft: int, sample_rate: float, hop: Optional[int] = None, window: WindowArg = "hann",
+                       shift: bool = True, device: int = 0) -> np.ndarray:
+    """``welch_psd`` for streams of any length: the averaging runs inside the transform, chunk by chunk."""
+    return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed(iq, sample_rate, hop)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

@@ -22,12 +22,14 @@ from .spectrum import (  # noqa: E402
     fft_c128,
     fft_ci16,
     freq_axis,
+    integrated_db,
     process_frame,
     spectrum_db,
     spectrum_db_ci16,
     stft_db,
     stft_db_ci16,
     welch_psd,
+    welch_psd_streamed,
 )
 from .waterfall import WaterfallBuffer  # noqa: E402
 from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
@@ -43,6 +45,7 @@ __all__ = [
     "fft_c128",
     "fft_ci16",
     "freq_axis",
+    "integrated_db",
     "is_pinned",
     "library_path",
     "pinned_empty",
@@ -53,4 +56,5 @@ __all__ = [
     "stft_db",
     "stft_db_ci16",
     "welch_psd",
+    "welch_psd_streamed",
 ]
