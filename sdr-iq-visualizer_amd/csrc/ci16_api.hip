@@ -87,19 +87,7 @@ int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, 
     const bool flagship = p->nfft == 4096 && !p->blu_inner;
     if (!flagship && (p->blu_inner || !sdrk::fft_lds_ci16_supports(p->nfft, stride)))
         return unpack_route(p, d_in, n_frames, stride, d_out, epilogue, stream);
-    sdrk::LaunchArgs a;
-    a.d_iq = d_in;
-    a.frame_stride = stride;
-    a.d_out = d_out;
-    a.n_frames = n_frames;
-    a.nfft = p->nfft;
-    a.d_window = p->d_window;
-    a.d_twiddle = p->d_twiddle;
-    a.eps = p->eps;
-    a.shift = p->shift;
-    a.epilogue = epilogue;
-    a.stream = stream;
-    a.num_cus = p->num_cus;
+    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
     const hipError_t e = flagship ? sdrk::launch_fft4096_ci16(a) : sdrk::launch_fft_lds_ci16(a);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "ci16 kernel launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;
@@ -145,22 +133,9 @@ int sdrk_exec_device_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t
     if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
     int st = check_exec_args(p, d_iq_ci16, n_frames, frame_stride, d_out_db);
     if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    std::vector<hipEvent_t> ev((size_t)launches + 1, nullptr);
-    auto cleanup = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(SDRK_ERR_HIP, "hipEventCreate failed"); }
-    hipError_t e = hipEventRecord(ev[0], p->stream);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) {
-        st = launch_ci16(p, d_iq_ci16, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream);
-        if (st != SDRK_OK) { (void)hipStreamSynchronize(p->stream); cleanup(); return st; }
-        e = hipEventRecord(ev[(size_t)i + 1], p->stream);
-    }
-    if (e == hipSuccess) e = hipEventSynchronize(ev[(size_t)launches]);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) e = hipEventElapsedTime(&each_ms[i], ev[i], ev[(size_t)i + 1]);
-    cleanup();
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "timed launches failed: %s", hipGetErrorString(e));
-    return fused_check(p);
+    st = timed_each(p, launches, each_ms,
+                    [&] { return launch_ci16(p, d_iq_ci16, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
+    return st == SDRK_OK ? fused_check(p) : st;
 }
 
 int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,

@@ -29,50 +29,38 @@
 // transformed, so each resident workgroup keeps 32 KiB of HBM reads outstanding.
 #include "fft4096_core.h"
 
-#ifndef F4K_WINREG
-#define F4K_WINREG 0   // 1: window coefficients in 16 VGPRs per thread instead of a 16 KiB LDS copy
-#endif
-#ifndef F4K_NT
-#define F4K_NT 2       // cache-policy bits of the streaming loads/stores (2 = nt)
-#endif
-
 namespace sdrk {
 
+// fft4096_ci16_kernel (fft4096_ci16.hip) is this function with another input policy: a change here is made there too.
+//
 // (Tried and dropped, A/B on the same buffers: two frames prefetched (2 % slower, again in round 5 at 140 VGPRs), a sqrt-free
 // log epilogue (1.5 % slower), and sending the row through LDS once more so that it leaves as four 16-byte stores
 // per thread instead of sixteen 4-byte ones (1.0-1.5 % slower: two more barriers per frame cost more than the
 // narrower stores do); issuing the prefetch through inline asm with an exact `s_waitcnt vmcnt(16)` in front of its first
 // use — hipcc waits vmcnt(0) there, i.e. also for the previous frame's stores — changed nothing either: with three
-// workgroups per CU another wave always has work while one waits for its store acknowledgements.)
+// workgroups per CU another wave always has work while one waits for its store acknowledgements.  The window coefficients
+// in 16 VGPRs per thread instead of the 16 KiB LDS copy were a build switch, F4K_WINREG, that nothing set; it is gone.)
 template <bool HAS_WINDOW, int EPILOGUE>
 __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kernel(
     const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
     size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
     float eps, int shift) {
-    __shared__ float2 lds[F4K_XCH_ELEMS + F4K_TW_ELEMS + ((HAS_WINDOW && !F4K_WINREG) ? F4K_N / 2 : 0)];
+    typedef F4kInC64 In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
     float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
     float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
     float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
 
     const int tid = threadIdx.x;
     F4kAddr A = f4k_addr(tid);
-    f4k_init_tables(tw256, tw1, tw4096, tid, A);
-#if F4K_WINREG
-    float win[16];
-    if (HAS_WINDOW) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) win[j] = window[tid + 256 * j];
-    }
-#else
+    f4k_init_tables(tw256, tw1, tw4096, tid);
     if (HAS_WINDOW) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
     }
-#endif
     __syncthreads();
 
     const int xor_k2 = shift ? 8 : 0;
-    const int voff_in = tid * 8;
     constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
     const int voff_out = tid * OUT_ELEM;
 
@@ -82,62 +70,28 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kernel(
     // Software pipeline: each workgroup keeps the loads of its next frame in flight while it transforms the
     // current one.  (Two frames ahead — 64 KiB per workgroup in flight — measured 2.5 % slower against the
     // same-buffers copy: 1.055x instead of 1.030x its time.)
-    auto issue = [&](v2u (&x)[16], size_t fr) {
+    auto issue = [&](In::word (&x)[16], size_t fr) {
         if (fr >= n_frames) fr = first;  // harmless re-read past the end
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + fr * frame_stride, F4K_N * 8);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, voff_in, j * 2048, F4K_NT);
+        In::issue(x, iq + fr * frame_stride, tid);
     };
-    auto process = [&](v2u (&x)[16], size_t f) {
+    auto process = [&](In::word (&x)[16], size_t f) {
+        In::to_owners(x, lds, tid);
         cf v[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            v2f t = __builtin_bit_cast(v2f, x[j]);
-            v[j] = cf{t.x, t.y};
-        }
+        for (int j = 0; j < 16; ++j) v[j] = In::widen(x[j]);
         issue(x, f + step);
-        if (HAS_WINDOW) {
-#if !F4K_WINREG
-            float win[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
-#endif
-            f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
-        } else {
-            f4k_transform(v, lds, tw256, tw1, A, tid);
-        }
-        // ---- epilogue + store: bin k = tid + 256 k2 -> index tid + 256 (k2 ^ xor) ----
-        __amdgpu_buffer_rsrc_t w = frame_rsrc(
-            static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM);
-        if (EPILOGUE == EPI_LOGPSD) {
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                cf z = v[rev16(k2)];
-                float db = logpsd_db(z.x, z.y, eps);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, voff_out,
-                                                      (k2 ^ xor_k2) * 1024, F4K_NT);
-            }
-        } else {
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                cf z = v[rev16(k2)];
-                v2f o = {z.x, z.y};
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), w, voff_out,
-                                                      (k2 ^ xor_k2) * 2048, 0);
-            }
-        }
+        f4k_windowed_transform<HAS_WINDOW>(v, lds, tw256, tw1, lds_win, A, tid);
+        f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                voff_out, xor_k2, eps);
     };
-    v2u nxt[16];
+    In::word nxt[16];
     issue(nxt, first);
     for (size_t f = first; f < n_frames; f += step) process(nxt, f);
 }
 
 hipError_t launch_fft4096(const LaunchArgs& a) {
     if (a.n_frames == 0) return hipSuccess;
-    // Persistent grid: F4K_WAVES workgroups per CU.
-    size_t max_blocks = (size_t)a.num_cus * F4K_WAVES;
-    unsigned grid = (unsigned)(a.n_frames < max_blocks ? a.n_frames : max_blocks);
-    dim3 g(grid), b(F4K_THREADS);
+    dim3 g(f4k_grid(a.num_cus, F4K_WAVES, a.n_frames)), b(F4K_THREADS);
     const float2* iq = static_cast<const float2*>(a.d_iq);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
 #define SDRK_LAUNCH(W, E)                                                                            \

@@ -16,13 +16,6 @@
 #include "fft4096_core.h"
 #include "kernels_ci16.h"
 
-#ifndef F4K_WINREG
-#define F4K_WINREG 0   // as fft4096.hip
-#endif
-#ifndef F4K_NT
-#define F4K_NT 2       // cache-policy bits of the streaming loads/stores (2 = nt)
-#endif
-
 #include <cstdlib>
 
 namespace sdrk {
@@ -31,45 +24,15 @@ constexpr bool CI16_WIDE_DEFAULT = false;
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-template <bool HAS_WINDOW, int EPILOGUE, bool WIDE>
-__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ci16_kernel(
-    const unsigned* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
-    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
-    float eps, int shift) {
-    __shared__ __attribute__((aligned(16))) float2 lds[F4K_XCH_ELEMS + F4K_TW_ELEMS + ((HAS_WINDOW && !F4K_WINREG) ? F4K_N / 2 : 0)];
-    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
-    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
-    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
-
-    const int tid = threadIdx.x;
-    F4kAddr A = f4k_addr(tid);
-    f4k_init_tables(tw256, tw1, tw4096, tid, A);
-#if F4K_WINREG
-    float win[16];
-    if (HAS_WINDOW) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) win[j] = window[tid + 256 * j];
-    }
-#else
-    if (HAS_WINDOW) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
-    }
-#endif
-    __syncthreads();
-
-    const int xor_k2 = shift ? 8 : 0;
-    const int voff_in = tid * 4;
-    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
-    const int voff_out = tid * OUT_ELEM;
-
-    const size_t first = blockIdx.x;
-    const size_t step = gridDim.x;
-
-    // nxt: the next frame's raw dwords — direct: nxt[j] = x[tid + 256 j]; WIDE: dwords 4 i .. 4 i + 3 = x[1024 i + 4 tid + 0..3]
-    auto issue = [&](unsigned (&x)[16], size_t fr) {
-        if (fr >= n_frames) fr = first;  // harmless re-read past the end
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + fr * frame_stride, F4K_N * 4);
+// Input policy, int16 pairs: one dword per sample, widened by ci16_unpack.
+// x: the frame's raw dwords — direct: x[j] = sample tid + 256 j; WIDE: dwords 4 i .. 4 i + 3 = samples 1024 i + 4 tid + 0..3 until
+// to_owners has sent them through the exchange LDS to the lanes that own them.
+template <bool WIDE>
+struct F4kInCi16 {
+    typedef unsigned word;
+    typedef unsigned sample;
+    static __device__ __forceinline__ void issue(word (&x)[16], const sample* frame, int tid) {
+        __amdgpu_buffer_rsrc_t r = frame_rsrc(frame, F4K_N * 4);
         if constexpr (WIDE) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -78,10 +41,10 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ci16_kernel(
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b32(r, voff_in, j * 1024, F4K_NT);
+            for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b32(r, tid * 4, j * 1024, F4K_NT);
         }
-    };
-    auto process = [&](unsigned (&x)[16], size_t f) {
+    }
+    static __device__ __forceinline__ void to_owners(word (&x)[16], float2* lds, int tid) {
         if constexpr (WIDE) {
             unsigned* __restrict__ raw = reinterpret_cast<unsigned*>(lds);   // the exchange buffer, 16 KiB of it
             __syncthreads();   // the previous frame's pass-3 reads of the exchange buffer are done
@@ -95,56 +58,64 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ci16_kernel(
             for (int j = 0; j < 16; ++j) x[j] = raw[tid + 256 * j];
             // (f4k_transform's first barrier stands between these reads and its exchange-1 writes)
         }
+    }
+    static __device__ __forceinline__ cf widen(word w) {
+        float re, im;
+        ci16_unpack(w, re, im);
+        return cf{re, im};
+    }
+};
+
+// fft4096_kernel (fft4096.hip) with the int16 input policy, statement for statement; see there.
+template <bool HAS_WINDOW, int EPILOGUE, bool WIDE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ci16_kernel(
+    const unsigned* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift) {
+    typedef F4kInCi16<WIDE> In;
+    __shared__ __attribute__((aligned(16))) float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+
+    const size_t first = blockIdx.x;
+    const size_t step = gridDim.x;
+
+    auto issue = [&](typename In::word (&x)[16], size_t fr) {
+        if (fr >= n_frames) fr = first;  // harmless re-read past the end
+        In::issue(x, iq + fr * frame_stride, tid);
+    };
+    auto process = [&](typename In::word (&x)[16], size_t f) {
+        In::to_owners(x, lds, tid);
         cf v[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            float re, im;
-            ci16_unpack(x[j], re, im);
-            v[j] = cf{re, im};
-        }
+        for (int j = 0; j < 16; ++j) v[j] = In::widen(x[j]);
         issue(x, f + step);
-        if (HAS_WINDOW) {
-#if !F4K_WINREG
-            float win[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
-#endif
-            f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
-        } else {
-            f4k_transform(v, lds, tw256, tw1, A, tid);
-        }
-        // ---- epilogue + store: bin k = tid + 256 k2 -> index tid + 256 (k2 ^ xor) ----
-        __amdgpu_buffer_rsrc_t w = frame_rsrc(
-            static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM);
-        if (EPILOGUE == EPI_LOGPSD) {
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                cf z = v[rev16(k2)];
-                float db = logpsd_db(z.x, z.y, eps);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, voff_out,
-                                                      (k2 ^ xor_k2) * 1024, F4K_NT);
-            }
-        } else {
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                cf z = v[rev16(k2)];
-                v2f o = {z.x, z.y};
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), w, voff_out,
-                                                      (k2 ^ xor_k2) * 2048, 0);
-            }
-        }
+        f4k_windowed_transform<HAS_WINDOW>(v, lds, tw256, tw1, lds_win, A, tid);
+        f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                voff_out, xor_k2, eps);
     };
-    unsigned nxt[16];
+    typename In::word nxt[16];
     issue(nxt, first);
     for (size_t f = first; f < n_frames; f += step) process(nxt, f);
 }
 
 hipError_t launch_fft4096_ci16(const LaunchArgs& a) {
     if (a.n_frames == 0) return hipSuccess;
-    // Persistent grid: F4K_WAVES workgroups per CU.
-    size_t max_blocks = (size_t)a.num_cus * F4K_WAVES;
-    unsigned grid = (unsigned)(a.n_frames < max_blocks ? a.n_frames : max_blocks);
-    dim3 g(grid), b(F4K_THREADS);
+    dim3 g(f4k_grid(a.num_cus, F4K_WAVES, a.n_frames)), b(F4K_THREADS);
     const unsigned* iq = static_cast<const unsigned*>(a.d_iq);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
     // Which load form: measured in one process on 2^20 Hann frames, alternating (tools/bench_ci16.py, profiles/ci16/SUMMARY.md),

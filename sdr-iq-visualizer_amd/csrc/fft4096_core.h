@@ -1,5 +1,10 @@
-// fft4096_core.h — the in-LDS 4096-point transform shared by the flagship kernel
-// (fft4096.hip) and the strided first step of the large-N plans (fft_large.hip).
+// fft4096_core.h — the in-LDS 4096-point transform and the parts the N = 4096 streaming kernels are put together from:
+//   f4k_transform, pow_tree                      every N = 4096 kernel, and fft_lds.hip through fft_lds_core.h
+//   f4k_lds_elems, f4k_init_tables, f4k_grid      fft4096.hip, fft4096_ci16.hip, fft4096_integrate.hip, fft4096_features.hip
+//   F4kInC64 (input policy: 16-load issue, widening)   fft4096.hip, fft4096_integrate.hip; fft4096_ci16.hip has F4kInCi16
+//   f4k_windowed_transform, f4k_store_row        fft4096.hip, fft4096_ci16.hip
+// The persistent loop and the few statements of the prologue stay in each __global__ function: moved into a function of
+// their own they compile to other machine code than they do now (profiles/f4k_shared_body/SUMMARY.md).
 // See fft4096.hip for the decomposition and the LDS layouts.
 #pragma once
 #include "cplx.h"
@@ -14,6 +19,11 @@ constexpr int F4K_THREADS = 256;
 #endif
 constexpr int F4K_XCH_ELEMS = 4112;  // exchange buffer (max index 4110), 32,896 B
 constexpr int F4K_TW_ELEMS = 512;    // W256^(n k) as [k][n] and W4096^tid, 2 KiB each
+#ifndef F4K_NT
+#define F4K_NT 2       // cache-policy bits of the streaming loads/stores (2 = nt)
+#endif
+// float2 elements of a kernel's LDS array: exchange buffer, the two tables and, where the window is kept in LDS, its 16 KiB
+constexpr int f4k_lds_elems(bool lds_window) { return F4K_XCH_ELEMS + F4K_TW_ELEMS + (lds_window ? F4K_N / 2 : 0); }
 
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
@@ -48,8 +58,7 @@ __device__ __forceinline__ F4kAddr f4k_addr(int tid) {
 // table reads and a product per twiddle were 30; parity unchanged, 162 -> 126 VGPRs in the flagship, DESIGN_APPENDIX.md A.13).
 // Caller must __syncthreads() before the first f4k_transform().
 __device__ __forceinline__ void f4k_init_tables(float2* __restrict__ tw256, float2* __restrict__ tw1,
-                                                const float2* __restrict__ tw4096, int tid, F4kAddr& A) {
-    (void)A;
+                                                const float2* __restrict__ tw4096, int tid) {
     const int lo = tid & 15, hi = tid >> 4;
     tw256[tid] = tw4096[(16 * lo * hi) & (F4K_N - 1)];  // [k=hi][n=lo] = W256^(lo hi)
     tw1[tid] = tw4096[tid];                              // W4096^tid
@@ -120,6 +129,68 @@ __device__ __forceinline__ void f4k_transform(cf (&v)[16], float2* __restrict__ 
         v[j] = cf{t.x, t.y};
     }
     radix16(v);
+}
+
+// ---- parts of the streaming kernels: persistent grid, one frame per workgroup and iteration, buffer loads and stores ----
+
+// Persistent grid: wg_per_cu workgroups per CU, and no more workgroups than there is work.
+inline unsigned f4k_grid(int num_cus, int wg_per_cu, size_t work_items) {
+    const size_t max_blocks = (size_t)num_cus * wg_per_cu;
+    return (unsigned)(work_items < max_blocks ? work_items : max_blocks);
+}
+
+// Input policy: issue() starts the 16 words of a frame on their way, to_owners() leaves x[j] = the word of sample tid + 256 j
+// (a step only the int16 WIDE form has: F4kInCi16, fft4096_ci16.hip), widen() makes a word the complex64 sample.
+// complex64: the raw bits, widened by a bit cast.
+struct F4kInC64 {
+    typedef v2u word;
+    typedef float2 sample;
+    static __device__ __forceinline__ void issue(word (&x)[16], const sample* frame, int tid) {
+        __amdgpu_buffer_rsrc_t r = frame_rsrc(frame, F4K_N * 8);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, tid * 8, j * 2048, F4K_NT);
+    }
+    static __device__ __forceinline__ void to_owners(word (&)[16], float2*, int) {}   // the loads are per owner already
+    static __device__ __forceinline__ cf widen(word w) {
+        v2f t = __builtin_bit_cast(v2f, w);
+        return cf{t.x, t.y};
+    }
+};
+
+// window (16 coefficients per thread from LDS) * v -> transform
+template <bool HAS_WINDOW>
+__device__ __forceinline__ void f4k_windowed_transform(cf (&v)[16], float2* __restrict__ lds, const float2* __restrict__ tw256,
+                                                       const float2* __restrict__ tw1, const float* __restrict__ lds_win,
+                                                       const F4kAddr& A, int tid) {
+    if (HAS_WINDOW) {
+        float win[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
+        f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
+    } else {
+        f4k_transform(v, lds, tw256, tw1, A, tid);
+    }
+}
+
+// Epilogue + store of one row through its descriptor w: bin k = tid + 256 k2 -> index tid + 256 (k2 ^ xor_k2), the fftshift.
+// voff = tid * (bytes per bin).
+template <int EPILOGUE>
+__device__ __forceinline__ void f4k_store_row(const cf (&v)[16], __amdgpu_buffer_rsrc_t w, int voff, int xor_k2, float eps) {
+    if (EPILOGUE == EPI_LOGPSD) {
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            cf z = v[rev16(k2)];
+            float db = logpsd_db(z.x, z.y, eps);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, voff, (k2 ^ xor_k2) * 1024, F4K_NT);
+        }
+    } else {
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            cf z = v[rev16(k2)];
+            v2f o = {z.x, z.y};
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), w, voff, (k2 ^ xor_k2) * 2048, 0);
+        }
+    }
 }
 
 }  // namespace sdrk

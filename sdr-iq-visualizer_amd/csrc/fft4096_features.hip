@@ -52,11 +52,7 @@ __global__ __launch_bounds__(F4K_THREADS, F4KF_WAVES) void fft4096_features_kern
     float* __restrict__ row = reinterpret_cast<float*>(lds);                                  // 4096 float32
     RowFeatShared& sh = *reinterpret_cast<RowFeatShared*>(reinterpret_cast<char*>(lds) + F4K_N * sizeof(float));
 
-    {
-        const int tid = threadIdx.x;
-        F4kAddr A = f4k_addr(tid);
-        f4k_init_tables(tw256, tw1, tw4096, tid, A);
-    }
+    f4k_init_tables(tw256, tw1, tw4096, threadIdx.x);
     __syncthreads();
 
     const int xor_k2 = shift ? 8 : 0;
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(F4K_THREADS, F4KF_WAVES) void fft4096_features_kern
             const __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + f * frame_stride, F4K_N * 8);
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                const v2f t = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, tid * 8, j * 2048, 2));
+                const v2f t = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, tid * 8, j * 2048, F4K_NT));
                 v[j] = cf{t.x, t.y};
             }
         }
@@ -96,7 +92,7 @@ __global__ __launch_bounds__(F4K_THREADS, F4KF_WAVES) void fft4096_features_kern
             const cf z = v[rev16(k2)];
             const float db = logpsd_db(z.x, z.y, eps);
             row[tid + 256 * (k2 ^ xor_k2)] = db;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, tid * 4, (k2 ^ xor_k2) * 1024, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, db), w, tid * 4, (k2 ^ xor_k2) * 1024, F4K_NT);
         }
         __syncthreads();
         row_features_wg(row, F4K_N, prm, sh, stats + f * 16, thr ? thr + f : nullptr,
@@ -111,8 +107,7 @@ hipError_t launch_fft4096_features(const LaunchArgs& a, int rank, float gamma, i
     if (a.n_frames == 0) return hipSuccess;
     if (a.nfft != F4K_N) return hipErrorInvalidValue;
     RowFeatParams prm{rank, gamma, min_distance, max_peaks};
-    const size_t max_blocks = (size_t)a.num_cus * F4KF_WAVES;
-    const unsigned grid = (unsigned)(a.n_frames < max_blocks ? a.n_frames : max_blocks);
+    const unsigned grid = f4k_grid(a.num_cus, F4KF_WAVES, a.n_frames);
     const float2* iq = static_cast<const float2*>(a.d_iq);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
     float* out = static_cast<float*>(a.d_out);

@@ -12,10 +12,6 @@
 #include "fft4096_core.h"
 #include "kernels_integrate.h"
 
-#ifndef F4K_NT
-#define F4K_NT 2
-#endif
-
 namespace sdrk {
 
 template <bool HAS_WINDOW, int DET>
@@ -23,14 +19,14 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_integrate_kern
     const float2* __restrict__ iq, size_t frame_stride, IntUnits c, float* __restrict__ out, float2* __restrict__ partials,
     const float2* __restrict__ carry_in, float2* __restrict__ carry_out, const float* __restrict__ window,
     const float2* __restrict__ tw4096, int shift) {
-    __shared__ float2 lds[F4K_XCH_ELEMS + F4K_TW_ELEMS + (HAS_WINDOW ? F4K_N / 2 : 0)];
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
     float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;
     float2* __restrict__ tw1 = tw256 + 256;
     float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
 
     const int tid = threadIdx.x;
     F4kAddr A = f4k_addr(tid);
-    f4k_init_tables(tw256, tw1, tw4096, tid, A);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
     if (HAS_WINDOW) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
@@ -40,11 +36,7 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_integrate_kern
     const int xor_k2 = shift ? 8 : 0;   // bin k = tid + 256 k2 -> position tid + 256 (k2 ^ xor), as in fft4096.hip
     const int voff_in = tid * 8;
 
-    auto issue = [&](v2u (&x)[16], size_t fr) {
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(iq + (fr - c.f0) * frame_stride, F4K_N * 8);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, voff_in, j * 2048, F4K_NT);
-    };
+    auto issue = [&](v2u (&x)[16], size_t fr) { F4kInC64::issue(x, iq + (fr - c.f0) * frame_stride, tid); };
 
     size_t u = c.u_first + blockIdx.x;   // (the launcher starts no more workgroups than there are units)
     v2u nxt[16];
@@ -72,11 +64,9 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_integrate_kern
         for (size_t f = fb; f < fe; ++f) {
             cf v[16];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                v2f t = __builtin_bit_cast(v2f, nxt[j]);
-                v[j] = cf{t.x, t.y};
-            }
+            for (int j = 0; j < 16; ++j) v[j] = F4kInC64::widen(nxt[j]);
             issue(nxt, f + 1 < fe ? f + 1 : n_fb);   // the last unit's last frame: a harmless re-read of its first
+            // (not f4k_windowed_transform: through it this kernel compiles to other machine code)
             if (HAS_WINDOW) {
                 float win[16];
 #pragma unroll
@@ -129,8 +119,7 @@ hipError_t launch_fft4096_integrate(const IntegrateArgs& a) {
     c.scale = a.scale;
     c.eps = a.eps;
     c.inv_k = 1.0f / (float)a.k;
-    const size_t units = c.u_last - c.u_first + 1, max_blocks = (size_t)a.num_cus * F4K_WAVES;
-    dim3 g((unsigned)(units < max_blocks ? units : max_blocks)), b(F4K_THREADS);
+    dim3 g(f4k_grid(a.num_cus, F4K_WAVES, c.u_last - c.u_first + 1)), b(F4K_THREADS);
     const float2* iq = static_cast<const float2*>(a.d_in);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
 #define SDRK_LAUNCH(W, D)                                                                                               \

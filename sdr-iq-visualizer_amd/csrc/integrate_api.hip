@@ -201,22 +201,10 @@ int sdrk_exec_device_integrated_timed_each(sdrk_plan* p, const void* d_iq_c64, s
     if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
     int st = check_int_args(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, d_out);
     if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    std::vector<hipEvent_t> ev((size_t)launches + 1, nullptr);
-    auto cleanup = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(SDRK_ERR_HIP, "hipEventCreate failed"); }
-    hipError_t e = hipEventRecord(ev[0], p->stream);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) {
-        st = device_call(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, p->stream);
-        if (st != SDRK_OK) { (void)hipStreamSynchronize(p->stream); cleanup(); return st; }
-        e = hipEventRecord(ev[(size_t)i + 1], p->stream);
-    }
-    if (e == hipSuccess) e = hipEventSynchronize(ev[(size_t)launches]);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) e = hipEventElapsedTime(&each_ms[i], ev[i], ev[(size_t)i + 1]);
-    cleanup();
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "timed launches failed: %s", hipGetErrorString(e));
-    return fused_check(p);
+    st = timed_each(p, launches, each_ms, [&] {
+        return device_call(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, p->stream);
+    });
+    return st == SDRK_OK ? fused_check(p) : st;
 }
 
 // The numpy boundary.  Chunks of about HOST_CHUNK_BYTES of input, cut at frame boundaries wherever they fall within a group,

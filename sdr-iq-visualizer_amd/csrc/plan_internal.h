@@ -9,8 +9,10 @@
 #include <map>
 #include <mutex>
 #include <utility>
+#include <vector>
 
 #include "../../include/sdrk.h"
+#include "kernels.h"
 
 namespace sdrk_host {
 constexpr int HOST_SLOTS = 3;
@@ -161,6 +163,49 @@ int plan_launch(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_st
                 hipStream_t stream, float* d_mip = nullptr, bool* mip_written = nullptr, const EpiArgs* epi = nullptr,
                 size_t call_frames = 0);
 int fused_check(sdrk_plan* p);   // after a stream sync: the fused launches since the last check
+
+// What every launcher of a float32 plan's own kernel takes from the plan, and the call's input, frames, stride, output,
+// epilogue and stream (plan_launch adds its scratch, companion-row, epilogue-table and overlap fields).
+inline sdrk::LaunchArgs plan_launch_args(const sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
+                                         int epilogue, hipStream_t stream) {
+    sdrk::LaunchArgs a;
+    a.d_iq = d_iq;
+    a.frame_stride = frame_stride;
+    a.d_out = d_out;
+    a.n_frames = n_frames;
+    a.nfft = p->nfft;
+    a.d_window = p->d_window;
+    a.d_twiddle = p->d_twiddle;
+    a.eps = p->eps;
+    a.shift = p->shift;
+    a.epilogue = epilogue;
+    a.stream = stream;
+    a.num_cus = p->num_cus;
+    return a;
+}
+
+// The body of the sdrk_exec_device*_timed_each entry points, behind their argument checks: `launches` times launch() (-> a
+// sdrk_status) on the plan's stream with an event between consecutive ones, then the time of each in each_ms.  A failed launch
+// ends the call with its status once the stream has drained.
+template <class Launch>
+int timed_each(sdrk_plan* p, int launches, float* each_ms, Launch launch) {
+    HIP_TRY(hipSetDevice(p->device));
+    std::vector<hipEvent_t> ev((size_t)launches + 1, nullptr);
+    auto cleanup = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(SDRK_ERR_HIP, "hipEventCreate failed"); }
+    hipError_t e = hipEventRecord(ev[0], p->stream);
+    for (int i = 0; i < launches && e == hipSuccess; ++i) {
+        const int st = launch();
+        if (st != SDRK_OK) { (void)hipStreamSynchronize(p->stream); cleanup(); return st; }
+        e = hipEventRecord(ev[(size_t)i + 1], p->stream);
+    }
+    if (e == hipSuccess) e = hipEventSynchronize(ev[(size_t)launches]);
+    for (int i = 0; i < launches && e == hipSuccess; ++i) e = hipEventElapsedTime(&each_ms[i], ev[i], ev[(size_t)i + 1]);
+    cleanup();
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "timed launches failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
 
 // ---- sdrk_probes.hip ----
 int tune_staging(sdrk_plan* p);   // SDRK_PLAN_TUNE_STAGING, at plan creation

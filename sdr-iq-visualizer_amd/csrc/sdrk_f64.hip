@@ -166,22 +166,8 @@ int sdrk_exec_device_f64_timed_each(sdrk_plan* p, const void* d_iq_c128, size_t 
     int st = sdrk_host::check_exec_args(p, d_iq_c128, n_frames, frame_stride, d_out_db, 64);
     if (st != SDRK_OK) return st;
     if (n_frames == 0) return fail(SDRK_ERR_INVALID, "nothing to time (n_frames is 0)");
-    HIP_TRY(hipSetDevice(p->device));
-    std::vector<hipEvent_t> ev((size_t)launches + 1, nullptr);
-    auto cleanup = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(SDRK_ERR_HIP, "hipEventCreate failed"); }
-    hipError_t e = hipEventRecord(ev[0], p->stream);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) {
-        st = launch64(p, d_iq_c128, n_frames, frame_stride, d_out_db, sdrk::EPI64_DB, p->stream);
-        if (st != SDRK_OK) { (void)hipStreamSynchronize(p->stream); cleanup(); return st; }
-        e = hipEventRecord(ev[(size_t)i + 1], p->stream);
-    }
-    if (e == hipSuccess) e = hipEventSynchronize(ev[(size_t)launches]);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) e = hipEventElapsedTime(&each_ms[i], ev[i], ev[(size_t)i + 1]);
-    cleanup();
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "timed launches failed: %s", hipGetErrorString(e));
-    return SDRK_OK;
+    return sdrk_host::timed_each(
+        p, launches, each_ms, [&] { return launch64(p, d_iq_c128, n_frames, frame_stride, d_out_db, sdrk::EPI64_DB, p->stream); });
 }
 
 }  // extern "C"

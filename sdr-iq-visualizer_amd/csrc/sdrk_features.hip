@@ -190,10 +190,7 @@ int sdrk_frame_features_device(sdrk_plan* p, const void* d_iq, size_t n_frames, 
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : p->stream;
     if (p->nfft == 4096) {
         // fused: the rows never leave the chip unless d_out_db asks for them (fft4096_features.hip)
-        sdrk::LaunchArgs a;
-        a.d_iq = d_iq; a.frame_stride = frame_stride; a.d_out = d_out_db; a.n_frames = n_frames; a.nfft = 4096;
-        a.d_window = p->d_window; a.d_twiddle = p->d_twiddle; a.eps = p->eps; a.shift = p->shift;
-        a.stream = s; a.num_cus = p->num_cus;
+        const sdrk::LaunchArgs a = plan_launch_args(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, s);
         hipError_t e = sdrk::launch_fft4096_features(a, rank, gamma, min_distance, max_peaks > 0 ? max_peaks : 1, d_stats,
                                                      d_thr, peaks ? d_idx : nullptr, peaks ? d_count : nullptr);
         if (e != hipSuccess) return fail(SDRK_ERR_HIP, "fused feature launch failed: %s", hipGetErrorString(e));

@@ -105,21 +105,9 @@ namespace {
 
 int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, void* d_out,
                      int epilogue, hipStream_t stream, float* d_mip, bool* mip_written, const EpiArgs* epi, size_t call_frames) {
-    sdrk::LaunchArgs a;
+    sdrk::LaunchArgs a = plan_launch_args(p, d_iq, n_frames, frame_stride, d_out, epilogue, stream);
     a.d_mip = d_mip;
     a.mip_written = mip_written;
-    a.d_iq = d_iq;
-    a.frame_stride = frame_stride;
-    a.d_out = d_out;
-    a.n_frames = n_frames;
-    a.nfft = p->nfft;
-    a.d_window = p->d_window;
-    a.d_twiddle = p->d_twiddle;
-    a.eps = p->eps;
-    a.shift = p->shift;
-    a.epilogue = epilogue;
-    a.stream = stream;
-    a.num_cus = p->num_cus;
     a.d_scratch = p->d_scratch;
     a.scratch_frames = p->scratch_frames;
     a.d_twiddle_2p = p->d_tw_2p;
@@ -581,22 +569,9 @@ int sdrk_exec_device_timed_each(sdrk_plan* p, const void* d_iq, size_t n_frames,
     if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
     int st = check_exec_args(p, d_iq, n_frames, frame_stride, d_out_db);
     if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    std::vector<hipEvent_t> ev((size_t)launches + 1, nullptr);
-    auto cleanup = [&] { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(SDRK_ERR_HIP, "hipEventCreate failed"); }
-    hipError_t e = hipEventRecord(ev[0], p->stream);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) {
-        st = plan_launch(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream);
-        if (st != SDRK_OK) { (void)hipStreamSynchronize(p->stream); cleanup(); return st; }
-        e = hipEventRecord(ev[(size_t)i + 1], p->stream);
-    }
-    if (e == hipSuccess) e = hipEventSynchronize(ev[(size_t)launches]);
-    for (int i = 0; i < launches && e == hipSuccess; ++i) e = hipEventElapsedTime(&each_ms[i], ev[i], ev[(size_t)i + 1]);
-    cleanup();
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "timed launches failed: %s", hipGetErrorString(e));
-    return fused_check(p);
+    st = timed_each(p, launches, each_ms,
+                    [&] { return plan_launch(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
+    return st == SDRK_OK ? fused_check(p) : st;
 }
 
 }  // extern "C"
