@@ -259,8 +259,9 @@ int sdrk_exec_device_f64_timed_each(sdrk_plan* plan, const void* d_iq_c128, size
  * scale is applied: a caller who wants full-scale normalisation folds 1/32768 (1/2048 for 12-bit data) into a custom window or
  * adds the constant 20*log10(scale) to the dB rows.  Served by ordinary float32 plans of any nfft; an f64 plan returns
  * SDRK_ERR_INVALID.  nfft = 256 ... 16384 are read as int16 by the transform itself (half the input bytes of the complex64
- * call); other lengths are widened on the device in chunks of at most 64 MiB first.  Welch, the feature entry points and the
- * waterfall appends have no int16 form. */
+ * call); other lengths are widened on the device in chunks of at most 64 MiB first.  The integrated spectra have an int16
+ * form (sdrk_exec_*_integrated_ci16, below); sdrk_welch_psd_host, the feature entry points and the waterfall appends have
+ * none. */
 /* streamer.py:114-121, host in / host out: the numpy boundary of sdrk_exec_host with 4-byte samples */
 int sdrk_exec_host_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_frames, size_t frame_stride, float* out_db);
 /* streamer.py:114-119: complex64 fft(w*x) of int16 samples, fftshifted if the plan shifts */
@@ -303,6 +304,19 @@ int sdrk_exec_device_integrated_timed_each(sdrk_plan* plan, const void* d_iq_c64
 /* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
 int sdrk_exec_host_integrated(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                               int detector, int out_form, float scale, float* out);
+/* The same three from int16 I,Q (the int16 section above: 4 bytes per sample, frame starts 4-byte aligned, any frame_stride
+ * >= 1, no scale applied to the samples): x[n] = float32(I[n]) + i*float32(Q[n]) exactly, then the same bits as the entry
+ * point above returns for those widened samples — every nfft of a float32 plan (chirp-z included), every detector, form,
+ * k_frames, n_groups and stride, device and host entry alike; the same refusals.  N = 4096 reads the int16 samples inside the
+ * reducing transform (4 + 4/K bytes per sample through device memory); other lengths run the plan's int16 transform into the
+ * same staging of at most 64 MiB. */
+int sdrk_exec_device_integrated_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                     size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_integrated_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                                size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                int launches, float* each_ms);
+int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                   int detector, int out_form, float scale, float* out);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

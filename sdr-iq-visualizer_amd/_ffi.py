@@ -146,6 +146,13 @@ SYMBOLS = [
                                                        c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
                                           c_void_p]),
+    # ... the same from int16 I,Q: the bits of the three above on the widened samples
+    ("sdrk_exec_device_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                 c_void_p, c_void_p]),
+    ("sdrk_exec_device_integrated_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                            c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                               c_void_p]),
 ]
 
 _lib = None

@@ -54,8 +54,8 @@ def main(argv=None) -> int:
         return 0
 
     from . import spectrum
-    # one read; an int16 recording stays int16 (the spectrum row is computed from the int16 samples themselves: the same
-    # bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
+    # one read; an int16 recording stays int16 (the spectrum row and the --integrate rows are computed from the int16 samples
+    # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
     samples, meta = sigmf_io.read_sigmf(args.path, native=True)
     raw16 = samples if samples.dtype == np.int16 else None
     n_samples = int(samples.shape[0])
@@ -83,10 +83,12 @@ def main(argv=None) -> int:
         report["welch_segments"] = 1 + (samples.size - args.welch) // args.welch
         report["welch_peak_db_per_hz"] = float(10 * np.log10(pxx.max()))
     if args.integrate:
-        if raw16 is not None and samples.dtype == np.int16:
-            samples = raw16.astype(np.float32).view(np.complex64).reshape(-1)
-        rows = spectrum.integrated_db(samples, args.nfft, args.integrate, detector=args.detector, window=args.window,
-                                      device=args.device)
+        if raw16 is not None:   # the int16 samples as they are: the same rows from half the bytes, nothing widened on the host
+            rows = spectrum.integrated_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.integrate, detector=args.detector,
+                                               window=args.window, device=args.device)
+        else:
+            rows = spectrum.integrated_db(samples, args.nfft, args.integrate, detector=args.detector, window=args.window,
+                                          device=args.device)
         results["integrated_db"] = rows
         report["integrate_k"] = args.integrate
         report["integrate_detector"] = args.detector

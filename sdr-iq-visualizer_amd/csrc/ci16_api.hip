@@ -80,8 +80,11 @@ int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride,
     return st;
 }
 
-// One transform of a float32 plan on int16 input: the ci16 form of plan_launch, and the LaunchFn of the ci16 numpy boundary.
-int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+}  // namespace
+
+// One transform of a float32 plan on int16 input: the ci16 form of plan_launch, the LaunchFn of the ci16 numpy boundary
+// and the transform of the int16 integrated calls (kgroup_ci16_api.hip); declared in plan_internal.h.
+int sdrk_host::launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
     if (p->precision != 32) return fail(SDRK_ERR_INVALID, "ci16 transform requested of a float64 plan");
     if (n_frames == 0) return SDRK_OK;
     const bool flagship = p->nfft == 4096 && !p->blu_inner;
@@ -92,6 +95,8 @@ int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, 
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "ci16 kernel launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;
 }
+
+namespace {
 
 // int16 pairs in; float32 rows or complex64 out.  The kernel reads and writes pinned host memory itself only at the lengths
 // whose transform reads int16 (the unpack route would cross PCIe for its staging's sake).

@@ -13,58 +13,13 @@
 //           the exchange LDS (ds_write_b128 at their sample index, ds_read_b32 at tid + 256 j: both conflict free) to the lanes
 //           that own them, at the price of two more workgroup barriers per frame.  Needs 16-byte aligned frame starts.
 // launch_fft4096_ci16 says which one runs, and what each measured.
-#include "fft4096_core.h"
-#include "kernels_ci16.h"
+#include "fft4096_in_ci16.h"
 
 #include <cstdlib>
 
 namespace sdrk {
 
 constexpr bool CI16_WIDE_DEFAULT = false;
-
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-// Input policy, int16 pairs: one dword per sample, widened by ci16_unpack.
-// x: the frame's raw dwords — direct: x[j] = sample tid + 256 j; WIDE: dwords 4 i .. 4 i + 3 = samples 1024 i + 4 tid + 0..3 until
-// to_owners has sent them through the exchange LDS to the lanes that own them.
-template <bool WIDE>
-struct F4kInCi16 {
-    typedef unsigned word;
-    typedef unsigned sample;
-    static __device__ __forceinline__ void issue(word (&x)[16], const sample* frame, int tid) {
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(frame, F4K_N * 4);
-        if constexpr (WIDE) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const v4u q = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, i * 4096, F4K_NT));
-                x[4 * i] = q.x, x[4 * i + 1] = q.y, x[4 * i + 2] = q.z, x[4 * i + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b32(r, tid * 4, j * 1024, F4K_NT);
-        }
-    }
-    static __device__ __forceinline__ void to_owners(word (&x)[16], float2* lds, int tid) {
-        if constexpr (WIDE) {
-            unsigned* __restrict__ raw = reinterpret_cast<unsigned*>(lds);   // the exchange buffer, 16 KiB of it
-            __syncthreads();   // the previous frame's pass-3 reads of the exchange buffer are done
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const v4u q = {x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
-                *reinterpret_cast<v4u*>(raw + 1024 * i + 4 * tid) = q;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = raw[tid + 256 * j];
-            // (f4k_transform's first barrier stands between these reads and its exchange-1 writes)
-        }
-    }
-    static __device__ __forceinline__ cf widen(word w) {
-        float re, im;
-        ci16_unpack(w, re, im);
-        return cf{re, im};
-    }
-};
 
 // fft4096_kernel (fft4096.hip) with the int16 input policy, statement for statement; see there.
 template <bool HAS_WINDOW, int EPILOGUE, bool WIDE>

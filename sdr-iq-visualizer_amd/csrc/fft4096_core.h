@@ -1,7 +1,8 @@
 // fft4096_core.h — the in-LDS 4096-point transform and the parts the N = 4096 streaming kernels are put together from:
 //   f4k_transform, pow_tree                      every N = 4096 kernel, and fft_lds.hip through fft_lds_core.h
-//   f4k_lds_elems, f4k_init_tables, f4k_grid      fft4096.hip, fft4096_ci16.hip, fft4096_integrate.hip, fft4096_features.hip
-//   F4kInC64 (input policy: 16-load issue, widening)   fft4096.hip, fft4096_integrate.hip; fft4096_ci16.hip has F4kInCi16
+//   f4k_lds_elems, f4k_init_tables, f4k_grid      fft4096.hip, fft4096_ci16.hip, fft4096_integrate.hip, fft4096_features.hip,
+//                                                fft4096_kgroup_ci16.hip
+//   F4kInC64 (input policy: 16-load issue, widening)   fft4096.hip, fft4096_integrate.hip; fft4096_in_ci16.h has F4kInCi16
 //   f4k_windowed_transform, f4k_store_row        fft4096.hip, fft4096_ci16.hip
 // The persistent loop and the few statements of the prologue stay in each __global__ function: moved into a function of
 // their own they compile to other machine code than they do now (profiles/f4k_shared_body/SUMMARY.md).
@@ -140,7 +141,7 @@ inline unsigned f4k_grid(int num_cus, int wg_per_cu, size_t work_items) {
 }
 
 // Input policy: issue() starts the 16 words of a frame on their way, to_owners() leaves x[j] = the word of sample tid + 256 j
-// (a step only the int16 WIDE form has: F4kInCi16, fft4096_ci16.hip), widen() makes a word the complex64 sample.
+// (a step only the int16 WIDE form has: F4kInCi16, fft4096_in_ci16.h), widen() makes a word the complex64 sample.
 // complex64: the raw bits, widened by a bit cast.
 struct F4kInC64 {
     typedef v2u word;

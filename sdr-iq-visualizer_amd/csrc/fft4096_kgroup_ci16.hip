@@ -1,0 +1,143 @@
+// fft4096_kgroup_ci16.hip — one row per group of K frames (mean, maximum or minimum of |X|^2 per bin) from interleaved
+// little-endian int16 I,Q at N = 4096: fft4096_integrate.hip's kernel with the int16 input policy (fft4096_in_ci16.h), 4 + 4/K
+// bytes per sample through HBM where the complex64 form moves 8 + 4/K and the per-frame int16 kernel 4 + 4.
+//
+//   x[n] = float32(I[n]) + i float32(Q[n])     (exact)
+// then the arithmetic of fft4096_integrate_kernel in the same order — f4k_transform, int_accumulate, the epilogue — so rows,
+// partial rows and carry rows have the bits the complex64 kernel produces on the widened samples, and integrate_rows.hip's
+// finalize serves both.  The direct load form only: 16 dword buffer loads per thread and frame (every wave instruction reads 64
+// consecutive samples), the next frame's in flight while the current one is transformed, across unit boundaries too; frame
+// starts need 4-byte alignment only.  (The wide form lost at the per-frame kernel, fft4096_ci16.hip, and costs two more
+// barriers per frame; it is not instantiated here.)  The prefetch holds 16 VGPRs where the complex64 kernel's holds 32.
+#include "fft4096_in_ci16.h"
+#include "kernels_integrate.h"
+#include "kernels_kgroup_ci16.h"
+
+namespace sdrk {
+
+// fft4096_integrate_kernel (fft4096_integrate.hip) with the int16 input policy, statement for statement; see there.  (The
+// loads are the policy's issue_few_sgprs: with issue()'s 15 offset registers beside the state rows' the rectangular
+// instantiations parked 17-18 scalar values in vector lanes, with 3 they park fewer than the complex64 kernel.)
+template <bool HAS_WINDOW, int DET>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kgroup_ci16_kernel(
+    const unsigned* __restrict__ iq, size_t frame_stride, IntUnits c, float* __restrict__ out, float2* __restrict__ partials,
+    const float2* __restrict__ carry_in, float2* __restrict__ carry_out, const float* __restrict__ window,
+    const float2* __restrict__ tw4096, int shift) {
+    typedef F4kInCi16<false> In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;
+    float2* __restrict__ tw1 = tw256 + 256;
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;   // bin k = tid + 256 k2 -> position tid + 256 (k2 ^ xor), as in fft4096.hip
+    const int voff_in = tid * 8;
+
+    auto issue = [&](In::word (&x)[16], size_t fr) { In::issue_few_sgprs(x, iq + (fr - c.f0) * frame_stride, tid); };
+
+    size_t u = c.u_first + blockIdx.x;   // (the launcher starts no more workgroups than there are units)
+    In::word nxt[16];
+    issue(nxt, int_unit(c, u).fb);
+    for (;;) {
+        const IntUnit cur = int_unit(c, u);
+        const size_t g = cur.g, fb = cur.fb, fe = cur.fe;
+        const bool starts = cur.starts, ends = cur.ends;
+        float acc[16], cmp[16];
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) int_init<DET>(acc[k2], cmp[k2]);
+        if (!starts) {
+            __amdgpu_buffer_rsrc_t r = frame_rsrc(carry_in, F4K_N * 8);
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const v2f s = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, voff_in, (k2 ^ xor_k2) * 2048, 0));
+                acc[k2] = s.x;
+                cmp[k2] = s.y;
+            }
+        }
+        const size_t u_next = u + gridDim.x;
+        const bool more = u_next <= c.u_last;
+        const size_t n_fb = more ? int_unit(c, u_next).fb : fb;
+        for (size_t f = fb; f < fe; ++f) {
+            cf v[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = In::widen(nxt[j]);
+            issue(nxt, f + 1 < fe ? f + 1 : n_fb);   // the last unit's last frame: a harmless re-read of its first
+            if (HAS_WINDOW) {
+                float win[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
+                f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
+            } else {
+                f4k_transform(v, lds, tw256, tw1, A, tid);
+            }
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const cf z = v[rev16(k2)];
+                int_accumulate<DET>(acc[k2], cmp[k2], fmaf(z.x, z.x, z.y * z.y));
+            }
+        }
+        // ---- end of the unit ----
+        if (ends && c.slices == 1) {
+            __amdgpu_buffer_rsrc_t w = frame_rsrc(out + (g - c.out_row0) * (size_t)F4K_N, F4K_N * 4);
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const float r = int_reduced<DET>(acc[k2], cmp[k2], c.inv_k);
+                const float o = int_epilogue(r, c.out_form, c.scale, c.eps);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), w, tid * 4, (k2 ^ xor_k2) * 1024, F4K_NT);
+            }
+        } else {
+            __amdgpu_buffer_rsrc_t w = frame_rsrc(ends ? partials + u * (size_t)F4K_N : carry_out, F4K_N * 8);
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const v2f s = {acc[k2], cmp[k2]};
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, s), w, voff_in, (k2 ^ xor_k2) * 2048, 0);
+            }
+        }
+        if (!more) break;
+        u = u_next;
+    }
+}
+
+hipError_t launch_fft4096_kgroup_ci16(const IntegrateArgs& a) {
+    if (a.f1 <= a.f0) return hipSuccess;
+    IntUnits c;
+    const IntSplit sp{a.slices, a.slice_len};
+    c.f0 = a.f0;
+    c.f1 = a.f1;
+    c.k = a.k;
+    c.slice_len = a.slice_len;
+    c.slices = (unsigned)a.slices;
+    c.u_first = integrate_unit_of(a.f0, a.k, sp);
+    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
+    c.out_row0 = a.out_row0;
+    c.out_form = a.out_form;
+    c.scale = a.scale;
+    c.eps = a.eps;
+    c.inv_k = 1.0f / (float)a.k;
+    dim3 g(f4k_grid(a.num_cus, F4K_WAVES, c.u_last - c.u_first + 1)), b(F4K_THREADS);
+    const unsigned* iq = static_cast<const unsigned*>(a.d_in);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(W, D)                                                                                                 \
+    hipLaunchKernelGGL((fft4096_kgroup_ci16_kernel<W, D>), g, b, 0, a.stream, iq, a.in_stride, c, a.d_out, a.d_partials,    \
+                       a.d_carry_in, a.d_carry_out, a.d_window, tw, a.shift)
+#define SDRK_LAUNCH_W(D)                                                                                                \
+    do {                                                                                                                \
+        if (a.d_window) SDRK_LAUNCH(true, D); else SDRK_LAUNCH(false, D);                                               \
+    } while (0)
+    if (a.detector == INT_DET_MEAN) SDRK_LAUNCH_W(INT_DET_MEAN);
+    else if (a.detector == INT_DET_MAX) SDRK_LAUNCH_W(INT_DET_MAX);
+    else SDRK_LAUNCH_W(INT_DET_MIN);
+#undef SDRK_LAUNCH_W
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace sdrk

@@ -1,23 +1,17 @@
-// integrate_api.hip — host side of the integrated-spectrum entry points of include/sdrk.h (sdrk_exec_*_integrated): per
-// group of K consecutive frames ONE row — the mean, maximum or minimum over the frames of |fft(w x_f)|^2 per bin — as dB or as
-// scaled linear power.  Video averaging / Welch, peak hold and noise-floor hold inside the transform.
+// integrate_api.hip — the complex64 integrated-spectrum entry points of include/sdrk.h (sdrk_exec_*_integrated): per group of
+// K consecutive frames ONE row — the mean, maximum or minimum over the frames of |fft(w x_f)|^2 per bin — as dB or as scaled
+// linear power.  Video averaging / Welch, peak hold and noise-floor hold inside the transform.
 //
-// N = 4096 runs fft4096_integrate.hip on the caller's samples: one launch, plus a finalize when the groups are too few to
-// fill the device and were cut into slices (integrate_split.h).  Every other length (chirp-z included) runs "the plan's own
-// transform with EPI_COMPLEX into at most 64 MiB of plan-owned staging, then integrate_rows.hip down the columns", chunk by
-// chunk at frame boundaries.  A unit that a chunk boundary cuts is carried: its accumulator state goes to one of two carry
-// rows (launch i writes row (i + 1) & 1, launch i + 1 reads it) and the next launch continues from it, so the result does
-// not depend on where the chunks were cut.  The numpy boundary feeds the same machinery through the three pinned staging
-// slots of sdrk_host_pipeline.hip, in device memory that does not grow with the stream.
+// The call itself — the N = 4096 kernel on the caller's samples, every other length through the plan's own transform and at
+// most 64 MiB of staging, carry rows across chunks, slices and their finalize, the numpy boundary through the three staging
+// slots — is integrate_call.h, shared with the int16 form (kgroup_ci16_api.hip).  This file gives it the complex64 launchers:
+// fft4096_integrate.hip and plan_launch.
 // Host code only (not named sdrk_*.hip: tests/host_sources.py globs those for the stand-in kernel builds).
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <vector>
-
-#include "host_pool.h"
+#include "integrate_call.h"
 #include "kernels_integrate.h"
 #include "plan_internal.h"
 
@@ -25,161 +19,16 @@ using namespace sdrk_host;
 
 namespace {
 
-constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
-
-struct IntCall {
-    sdrk_plan* p = nullptr;
-    size_t n_groups = 0, k = 0, stride = 0;
-    int detector = 0, out_form = 0;
-    float scale = 1.0f;
-    sdrk::IntSplit sp{1, 1};
-    bool fused = false;          // fft4096_integrate.hip
-    size_t stage_frames = 0;     // generic route: frames per staging chunk
-    unsigned launches = 0;       // reduction launches so far: picks the carry rows
-    hipStream_t stream = nullptr;
-    float2* carry[2] = {nullptr, nullptr};
-    float2* partials = nullptr;
-};
-
-int check_int_args(const sdrk_plan* p, const void* in, size_t n_groups, size_t k, size_t stride, int detector, int out_form,
-                   const void* out) {
-    if (detector != SDRK_DET_MEAN && detector != SDRK_DET_MAX && detector != SDRK_DET_MIN)
-        return fail(SDRK_ERR_INVALID, "detector %d is none of SDRK_DET_MEAN / _MAX / _MIN", detector);
-    if (out_form != SDRK_INT_OUT_DB && out_form != SDRK_INT_OUT_POWER)
-        return fail(SDRK_ERR_INVALID, "out_form %d is neither SDRK_INT_OUT_DB nor SDRK_INT_OUT_POWER", out_form);
-    if (n_groups == 0 || k == 0) return fail(SDRK_ERR_INVALID, "n_groups and k_frames must be >= 1");
-    if (k > ((size_t)1 << 40) || n_groups > (~(size_t)0 >> 1) / k)
-        return fail(SDRK_ERR_INVALID, "n_groups * k_frames is out of range");
-    if (stride == 0) return fail(SDRK_ERR_INVALID, "frame_stride must be >= 1");
-    if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
-    if (int st = check_precision(p, 32); st != SDRK_OK) return st;
-    if (!in || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
-    return SDRK_OK;
+int transform_c64(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+    return plan_launch(p, d_in, n_frames, stride, d_out, epilogue, stream);
 }
 
-// Plan-owned buffers only grow, and never under work that still uses them.
-int int_reserve(sdrk_plan* p, void** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return SDRK_OK;
-    if (p->int_busy) {
-        HIP_TRY(hipEventSynchronize(p->ev_int));
-        p->int_busy = false;
-    }
-    if (*buf) {
-        HIP_TRY(hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-    }
-    HIP_TRY(hipMalloc(buf, need));
-    *cap = need;
-    return SDRK_OK;
-}
-
-int call_begin(IntCall& c, sdrk_plan* p, size_t n_groups, size_t k, size_t stride, int detector, int out_form, float scale,
-               hipStream_t stream) {
-    c.p = p;
-    c.n_groups = n_groups;
-    c.k = k;
-    c.stride = stride;
-    c.detector = detector;
-    c.out_form = out_form;
-    c.scale = scale;
-    c.stream = stream;
-    const size_t nfft = (size_t)p->nfft;
-    c.fused = p->nfft == 4096 && !p->blu_inner;
-    // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel
-    const size_t ways = c.fused ? 1 : (nfft + 255) / 256;
-    c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
-    if (!p->ev_int) HIP_TRY(hipEventCreateWithFlags(&p->ev_int, hipEventDisableTiming));
-    const size_t row = nfft * sizeof(float2);
-    const size_t n_partials = c.sp.slices > 1 ? n_groups * c.sp.slices : 0;
-    int st = int_reserve(p, &p->d_int_state, &p->int_state_cap, (2 + n_partials) * row);
-    if (st != SDRK_OK) return st;
-    if (!c.fused) {
-        c.stage_frames = INT_STAGE_BYTES / row ? INT_STAGE_BYTES / row : 1;
-        if (c.stage_frames > n_groups * k) c.stage_frames = n_groups * k;
-        st = int_reserve(p, &p->d_int_stage, &p->int_stage_cap, c.stage_frames * row);
-        if (st != SDRK_OK) return st;
-    }
-    c.carry[0] = static_cast<float2*>(p->d_int_state);
-    c.carry[1] = c.carry[0] + nfft;
-    c.partials = c.carry[1] + nfft;
-    // one state and one staging per plan: a call on another stream waits for the last one's work
-    if (p->int_busy && p->int_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, p->ev_int, 0));
-    return SDRK_OK;
-}
-
-// The frames [f0, f1) of the call, d_in at frame f0's first sample.  Rows of the groups that end in the range go to
-// d_out + (group - out_row0) * nfft (unsplit calls only).
-int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float* d_out, size_t out_row0) {
-    sdrk_plan* p = c.p;
-    sdrk::IntegrateArgs a;
-    a.k = c.k;
-    a.slices = c.sp.slices;
-    a.slice_len = c.sp.len;
-    a.detector = c.detector;
-    a.out_form = c.out_form;
-    a.scale = c.scale;
-    a.eps = p->eps;
-    a.d_out = d_out;
-    a.out_row0 = out_row0;
-    a.d_partials = c.partials;
-    a.nfft = p->nfft;
-    a.d_window = p->d_window;
-    a.d_twiddle = p->d_twiddle;
-    a.shift = p->shift;
-    a.num_cus = p->num_cus;
-    a.stream = c.stream;
-    const size_t step = c.fused ? f1 - f0 : c.stage_frames;
-    for (size_t s0 = f0; s0 < f1; s0 += step) {
-        const size_t s1 = f1 - s0 < step ? f1 : s0 + step;
-        const float2* src = static_cast<const float2*>(d_in) + (s0 - f0) * c.stride;
-        a.f0 = s0;
-        a.f1 = s1;
-        a.d_carry_in = c.carry[c.launches & 1];
-        a.d_carry_out = c.carry[(c.launches + 1) & 1];
-        ++c.launches;
-        hipError_t e;
-        if (c.fused) {
-            a.d_in = src;
-            a.in_stride = c.stride;
-            e = sdrk::launch_fft4096_integrate(a);
-        } else {
-            int st = plan_launch(p, src, s1 - s0, c.stride, p->d_int_stage, sdrk::EPI_COMPLEX, c.stream);
-            if (st != SDRK_OK) return st;
-            a.d_in = p->d_int_stage;
-            a.in_stride = (size_t)p->nfft;
-            e = sdrk::launch_integrate_rows(a);
-        }
-        if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return SDRK_OK;
-}
-
-// Split calls: every group's partial rows -> its row.
-int call_finalize(IntCall& c, float* d_out) {
-    if (c.sp.slices == 1) return SDRK_OK;
-    const hipError_t e = sdrk::launch_integrate_finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector,
-                                                         c.out_form, c.scale, c.p->eps, d_out, c.p->num_cus, c.stream);
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate finalize launch failed: %s", hipGetErrorString(e));
-    return SDRK_OK;
-}
-
-int call_end(IntCall& c, int st) {   // (also after a failed launch: earlier launches are in flight)
-    const hipError_t e = hipEventRecord(c.p->ev_int, c.stream);
-    c.p->int_stream = c.stream;
-    c.p->int_busy = true;
-    if (st == SDRK_OK && e != hipSuccess) st = fail(SDRK_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
-    return st;
-}
-
-int device_call(sdrk_plan* p, const void* d_iq, size_t n_groups, size_t k, size_t stride, int detector, int out_form,
-                float scale, float* d_out, hipStream_t stream) {
-    IntCall c;
-    int st = call_begin(c, p, n_groups, k, stride, detector, out_form, scale, stream);
-    if (st != SDRK_OK) return st;
-    st = call_range(c, d_iq, 0, n_groups * k, d_out, 0);
-    if (st == SDRK_OK) st = call_finalize(c, d_out);
-    return call_end(c, st);
+IntIo c64_io() {
+    IntIo io;
+    io.in_elem = sizeof(float2);
+    io.fused = sdrk::launch_fft4096_integrate;
+    io.transform = transform_c64;
+    return io;
 }
 
 }  // namespace
@@ -188,104 +37,20 @@ extern "C" {
 
 int sdrk_exec_device_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                                 int detector, int out_form, float scale, float* d_out, void* stream) {
-    int st = check_int_args(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, d_out);
-    if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    return device_call(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
-                       stream ? static_cast<hipStream_t>(stream) : p->stream);
+    return exec_device_integrated(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                  stream);
 }
 
 int sdrk_exec_device_integrated_timed_each(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames,
                                            size_t frame_stride, int detector, int out_form, float scale, float* d_out,
                                            int launches, float* each_ms) {
-    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
-    int st = check_int_args(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, d_out);
-    if (st != SDRK_OK) return st;
-    st = timed_each(p, launches, each_ms, [&] {
-        return device_call(p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, p->stream);
-    });
-    return st == SDRK_OK ? fused_check(p) : st;
+    return exec_device_integrated_timed_each(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale,
+                                             d_out, launches, each_ms);
 }
 
-// The numpy boundary.  Chunks of about HOST_CHUNK_BYTES of input, cut at frame boundaries wherever they fall within a group,
-// go through the three staging slots: (helper threads: pageable -> pinned) -> H2D on the copy stream -> reduction on the plan's
-// stream -> the rows of the groups that ended in the chunk D2H on the other copy stream.  Everything is asynchronous, so the
-// H2D of chunk c + 1 runs beside the transform of chunk c; a slot is reused once its chunk's rows have arrived.
 int sdrk_exec_host_integrated(sdrk_plan* p, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                               int detector, int out_form, float scale, float* out) {
-    int st = check_int_args(p, iq_c64, n_groups, k_frames, frame_stride, detector, out_form, out);
-    if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    st = ensure_copy_streams(p);
-    if (st != SDRK_OK) return st;
-    IntCall c;
-    st = call_begin(c, p, n_groups, k_frames, frame_stride, detector, out_form, scale, p->stream);
-    if (st != SDRK_OK) return st;
-    const size_t nfft = (size_t)p->nfft, K = k_frames, n_frames = n_groups * K;
-    const bool direct = c.sp.slices == 1;   // rows leave per chunk; split calls finalize once at the end
-    // frames per chunk: bounded by the input bytes and, through the rows a chunk can complete, by the output bytes
-    size_t per = HOST_CHUNK_BYTES / (frame_stride * sizeof(float2));
-    size_t rows_cap = HOST_CHUNK_BYTES / (nfft * sizeof(float));
-    if (rows_cap < 1) rows_cap = 1;
-    if (per / K >= rows_cap) per = rows_cap * K;
-    if (per < 1) per = 1;
-    if (per > n_frames) per = n_frames;
-    const size_t chunk_in = ((per - 1) * frame_stride + nfft) * sizeof(float2);
-    const size_t chunk_out = direct ? (per / K + 1) * nfft * sizeof(float) : 0;
-    const size_t in_bytes = ((n_frames - 1) * frame_stride + nfft) * sizeof(float2);
-    const size_t out_bytes = n_groups * nfft * sizeof(float);
-    const bool in_pinned = pinned_ranges().covers(iq_c64, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
-    auto retire = [&](HostSlot& s) -> int {
-        if (!s.busy) return SDRK_OK;
-        s.busy = false;
-        HIP_TRY(hipEventSynchronize(s.ev_done));
-        if (s.user_out && s.out_bytes) sdrk::CopyPool::get().copy(s.user_out, s.h_out, s.out_bytes);
-        return SDRK_OK;
-    };
-    auto bail = [&](int status) { slots_abandon(p); (void)call_end(c, status); return status; };
-    size_t n = 0;
-    for (size_t f0 = 0; f0 < n_frames; f0 += per, ++n) {
-        HostSlot& s = p->slot[n % HOST_SLOTS];
-        const size_t f1 = n_frames - f0 < per ? n_frames : f0 + per;
-        const size_t cin = ((f1 - f0 - 1) * frame_stride + nfft) * sizeof(float2);
-        const size_t row0 = f0 / K, rows = direct ? f1 / K - row0 : 0, cout = rows * nfft * sizeof(float);
-        st = retire(s);
-        if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);
-        if (st != SDRK_OK) return bail(st);
-        const void* src = chunk_pinned_src(s, static_cast<const char*>(iq_c64) + f0 * frame_stride * sizeof(float2), cin, in_pinned);
-        hipError_t e = stage_chunk_in(p, s, src, cin);
-        if (e == hipSuccess) {
-            st = call_range(c, s.d_in, f0, f1, static_cast<float*>(s.d_out), row0);
-            if (st != SDRK_OK) return bail(st);
-            e = hipEventRecord(s.ev_k, p->stream);
-        }
-        float* user_rows = out + row0 * nfft;
-        if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
-        if (e == hipSuccess && cout)
-            e = hipMemcpyAsync(out_pinned ? static_cast<void*>(user_rows) : s.h_out, s.d_out, cout, hipMemcpyDeviceToHost, p->s_d2h);
-        if (e == hipSuccess) e = hipEventRecord(s.ev_done, p->s_d2h);
-        if (e != hipSuccess) return bail(fail(SDRK_ERR_HIP, "host pipeline failed: %s", hipGetErrorString(e)));
-        s.busy = true;
-        s.user_out = out_pinned ? nullptr : user_rows;
-        s.out_bytes = cout;
-    }
-    for (size_t i = 0; i < HOST_SLOTS; ++i) {   // drain in submission order
-        st = retire(p->slot[(n + i) % HOST_SLOTS]);
-        if (st != SDRK_OK) return bail(st);
-    }
-    if (!direct) {   // fewer groups than the device has workgroups: a handful of rows
-        HostSlot& s = p->slot[0];
-        st = slot_reserve(p, s, 0, out_bytes);
-        if (st == SDRK_OK) st = call_finalize(c, static_cast<float*>(s.d_out));
-        if (st != SDRK_OK) return bail(st);
-        hipError_t e = hipMemcpyAsync(out, s.d_out, out_bytes, hipMemcpyDeviceToHost, p->stream);
-        if (e != hipSuccess) return bail(fail(SDRK_ERR_HIP, "host pipeline failed: %s", hipGetErrorString(e)));
-    }
-    st = call_end(c, SDRK_OK);
-    if (st != SDRK_OK) return st;
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    p->int_busy = false;
-    return fused_check(p);
+    return exec_host_integrated(c64_io(), p, iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }
 
 }  // extern "C"

@@ -236,4 +236,8 @@ hipError_t stage_chunk_in(sdrk_plan* p, HostSlot& s, const void* pinned_src, siz
 // the small mapped call, the zero-copy chunks and the three-slot pipeline of sdrk_exec_host, for any element sizes
 int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io);
 
+// ---- ci16_api.hip ----
+// One transform of a float32 plan on int16 I,Q input (4 bytes per sample), the ci16 form of plan_launch: a LaunchFn.
+int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
+
 }  // namespace sdrk_host

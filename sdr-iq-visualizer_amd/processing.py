@@ -7,9 +7,11 @@ the waterfall at app/dashboard/callbacks.py:176-182.  A maintainer switching to
 this build imports these names there (INTEGRATION.md shows the three-line
 change); the Dash callbacks keep reading the same ``plot_data`` dict.
 """
-from .spectrum import (fft_c64, fft_ci16, freq_axis, integrated_db, process_frame, spectrum_db,  # noqa: F401
-                       spectrum_db_ci16, stft_db, stft_db_ci16, welch_psd, welch_psd_streamed)
+from .spectrum import (fft_c64, fft_ci16, freq_axis, integrated_db, integrated_db_ci16, process_frame,  # noqa: F401
+                       spectrum_db, spectrum_db_ci16, stft_db, stft_db_ci16, welch_psd, welch_psd_streamed,
+                       welch_psd_streamed_ci16)
 from .waterfall import WaterfallBuffer  # noqa: F401
 
 __all__ = ["spectrum_db", "fft_c64", "freq_axis", "process_frame", "stft_db", "welch_psd", "WaterfallBuffer",
-           "spectrum_db_ci16", "fft_ci16", "stft_db_ci16", "integrated_db", "welch_psd_streamed"]
+           "spectrum_db_ci16", "fft_ci16", "stft_db_ci16", "integrated_db", "welch_psd_streamed",
+           "integrated_db_ci16", "welch_psd_streamed_ci16"]

@@ -430,6 +430,52 @@ class SpectrumPlan:
                                                                c_float(scale), c_void_p(d_out), int(launches), ms))
         return [float(v) for v in ms]
 
+    # ... from int16 I,Q: the bits of the three above on the widened samples, from half the input bytes
+    def integrate_ci16(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                       scale: float = 1.0) -> np.ndarray:
+        """``integrate`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``integrate`` on
+        ``float32(I) + 1j*float32(Q)``; no scale is applied to the samples.  At nfft = 4096 the int16 samples are read
+        inside the reducing transform."""
+        x = _as_ci16(iq, stream=True)
+        self._float32_only("integrate_ci16")
+        det, form = self._int_codes(detector, out)
+        hop = self.nfft if hop is None else int(hop)
+        groups = self.integrated_groups(x.shape[0], k, hop)
+        res = np.empty((groups, self.nfft), dtype=np.float32)
+        if groups:
+            with self._lock:
+                check(lib().sdrk_exec_host_integrated_ci16(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
+                                                           c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
+                                                           res.ctypes.data_as(c_void_p)))
+        return res
+
+    def exec_device_integrated_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
+                                    frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                    scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: int16 I,Q in (4 bytes per sample, frame starts 4-byte aligned), ``n_groups`` float32 rows out,
+        asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        self._float32_only("integrate_ci16")
+        det, form = self._int_codes(detector, out)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_integrated_ci16(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
+                                                         c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
+                                                         c_void_p(stream) if stream else None))
+
+    def exec_device_integrated_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                               frame_stride: Optional[int] = None, detector: str = "mean",
+                                               out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        self._float32_only("integrate_ci16")
+        det, form = self._int_codes(detector, out)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_integrated_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
+                                                                    c_size_t(int(k)), c_size_t(stride), det, form,
+                                                                    c_float(scale), c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -451,6 +497,20 @@ class SpectrumPlan:
         rows = 1 + (x.shape[0] - self.nfft) // hop
         scale = 1.0 / (float(sample_rate) * self.window_power())
         return self.integrate(x, rows, hop, "mean", "power", scale)[0]
+
+    def welch_psd_streamed_ci16(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
+        """``welch_psd_streamed`` over an int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples (in
+        units of the integer samples: no scale is applied to them)."""
+        x = _as_ci16(iq, stream=True)
+        self._float32_only("welch_psd_streamed_ci16")
+        hop = self.nfft if hop is None else int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        if x.shape[0] < self.nfft:
+            raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {self.nfft}-sample segment")
+        rows = 1 + (x.shape[0] - self.nfft) // hop
+        scale = 1.0 / (float(sample_rate) * self.window_power())
+        return self.integrate_ci16(x, rows, hop, "mean", "power", scale)[0]
 
     # -- device pointers (bench / pipelines that keep data resident) -------------
     def exec_device(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
@@ -704,6 +764,21 @@ def welch_psd_streamed(iq, nfft: int, sample_rate: float, hop: Optional[int] = N
                        shift: bool = True, device: int = 0) -> np.ndarray:
     """``welch_psd`` for streams of any length: the averaging runs inside the transform, chunk by chunk."""
     return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed(iq, sample_rate, hop)
+
+
+def integrated_db_ci16(iq, nfft: int, k: int, hop: Optional[int] = None, detector: str = "mean", window: WindowArg = None,
+                       eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """``integrated_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on
+    ``float32(I) + 1j*float32(Q)``, from half the input bytes."""
+    x = _as_ci16(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).integrate_ci16(x, k, hop, detector, "db")
+
+
+def welch_psd_streamed_ci16(iq, nfft: int, sample_rate: float, hop: Optional[int] = None, window: WindowArg = "hann",
+                            shift: bool = True, device: int = 0) -> np.ndarray:
+    """``welch_psd_streamed`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
+    x = _as_ci16(iq, stream=True)
+    return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed_ci16(x, sample_rate, hop)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

@@ -23,6 +23,7 @@ from .spectrum import (  # noqa: E402
     fft_ci16,
     freq_axis,
     integrated_db,
+    integrated_db_ci16,
     process_frame,
     spectrum_db,
     spectrum_db_ci16,
@@ -30,6 +31,7 @@ from .spectrum import (  # noqa: E402
     stft_db_ci16,
     welch_psd,
     welch_psd_streamed,
+    welch_psd_streamed_ci16,
 )
 from .waterfall import WaterfallBuffer  # noqa: E402
 from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
@@ -46,6 +48,7 @@ __all__ = [
     "fft_ci16",
     "freq_axis",
     "integrated_db",
+    "integrated_db_ci16",
     "is_pinned",
     "library_path",
     "pinned_empty",
@@ -57,4 +60,5 @@ __all__ = [
     "stft_db_ci16",
     "welch_psd",
     "welch_psd_streamed",
+    "welch_psd_streamed_ci16",
 ]
