@@ -318,6 +318,42 @@ int sdrk_exec_device_integrated_ci16_timed_each(sdrk_plan* plan, const void* d_i
 int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                    int detector, int out_form, float scale, float* out);
 
+/* ---- polyphase filter bank spectra: a T-tap weighted fold in front of the transform ------
+ * A plain windowed FFT gives every bin the window's response: a wide main lobe, side lobes that fall slowly.  A polyphase
+ * filter bank (weighted overlap-add) applies a prototype filter h of T*nfft coefficients (typically a windowed sinc) to T*nfft
+ * consecutive samples, folds the T blocks into nfft samples and transforms those: the bins become nearly rectangular channels.
+ * It sits in front of app/sdr/streamer.py:119-121 (`samples` becomes the folded frame); the reference has no counterpart (a
+ * build-side extension, like the decimated waterfall read-out).
+ * With N = nfft, frame f starts at sample s = f*frame_stride (any stride >= 1) and reads T*N samples; the buffer holds
+ * (n_frames-1)*frame_stride + T*N samples:
+ *     y_f[n] = (((h[n]*x[s+n]) + h[N+n]*x[s+N+n]) + h[2N+n]*x[s+2N+n]) + ...        (taps in ascending order)
+ * per real component in float32, every product rounded to float32, then every sum: no fused multiply-add — what numpy computes
+ * on float32 arrays.  The row is then exactly what the plan's complex64 entry point returns for the frame y_f with a rectangular
+ * window: the same bits at every length (chirp-z and the two-pass lengths included), as dB rows or as the complex spectrum, in
+ * the plan's shift order and with its eps.
+ * The prototype is the window: these entry points serve float32 plans created with SDRK_WINDOW_RECT only.  A windowed plan, an
+ * f64 plan, a plan with no prototype set, taps < 1 or > 32, NULL pointers and n_frames = 0 return SDRK_ERR_INVALID.  T = 1 is
+ * the rectangular transform of numpy's float32 h*x.  Every other entry point of a plan with a prototype set behaves as before.
+ * N = 4096 folds inside the transform's registers (8 B/sample from device memory at frame_stride = nfft, 4 B/sample out); other
+ * lengths fold into plan-owned staging of at most 64 MiB and run the plan's own transform.
+ * Not provided: int16 input, integration over K folded frames, double precision, waterfall appends. */
+/* the prototype: taps*nfft float32 from host memory into a plan-owned device copy; may be called again with another prototype
+ * or another T (not while work of this plan is in flight) */
+int sdrk_plan_set_pfb(sdrk_plan* plan, int taps, const float* h);
+/* taps of the prototype set on the plan; 0 = none */
+int sdrk_plan_pfb_taps(const sdrk_plan* plan);
+/* device in / device out (d_out_db: n_frames*nfft float32), asynchronous on `stream` (NULL: the plan's stream); any number of frames */
+int sdrk_exec_device_pfb(sdrk_plan* plan, const void* d_iq_c64, size_t n_frames, size_t frame_stride, float* d_out_db,
+                         void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_pfb_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_frames, size_t frame_stride,
+                                    float* d_out_db, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked through pinned staging in device memory that does not depend
+ * on the stream length (n_frames <= the plan's max_batch, as for sdrk_exec_host) */
+int sdrk_exec_host_pfb(sdrk_plan* plan, const void* iq_c64, size_t n_frames, size_t frame_stride, float* out_db);
+/* the complex spectrum of the folded frames: out_c64[f][k] = fft(y_f)[k], fftshifted if the plan shifts */
+int sdrk_exec_fft_host_pfb(sdrk_plan* plan, const void* iq_c64, size_t n_frames, size_t frame_stride, void* out_c64);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

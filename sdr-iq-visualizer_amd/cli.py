@@ -1,6 +1,6 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
-    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K] [--pfb T] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
@@ -33,6 +33,9 @@ def main(argv=None) -> int:
     p.add_argument("--integrate", type=_positive, default=0, metavar="K",
                    help="also write one dB row per K frames of --nfft samples (integrated_db)")
     p.add_argument("--detector", choices=["mean", "max", "min"], default="mean", help="what --integrate keeps per bin")
+    p.add_argument("--pfb", type=_positive, default=0, metavar="T",
+                   help="also write polyphase-filter-bank dB rows: T blocks of --nfft samples folded under the default "
+                        "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db)")
     p.add_argument("--window", default=None)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--out", default=None, help="write results to this .npz")
@@ -95,6 +98,14 @@ def main(argv=None) -> int:
         report["integrated_rows"] = int(rows.shape[0])
         if rows.shape[0] == 0:
             print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no integrated row", file=sys.stderr)
+    if args.pfb:   # the prototype is the window: --window does not apply; int16 recordings are widened (no int16 PFB form)
+        x = raw16.astype(np.float32).view(np.complex64).reshape(-1) if raw16 is not None else samples
+        rows = spectrum.pfb_db(x, args.nfft, args.pfb, device=args.device)
+        results["pfb_db"] = rows
+        report["pfb_taps"] = args.pfb
+        report["pfb_rows"] = int(rows.shape[0])
+        if rows.shape[0] == 0:
+            print(f"recording holds fewer than {args.pfb} blocks of {args.nfft} samples: no PFB row", file=sys.stderr)
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out

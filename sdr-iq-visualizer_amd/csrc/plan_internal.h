@@ -105,6 +105,17 @@ struct sdrk_plan {
     hipEvent_t ev_int = nullptr;
     hipStream_t int_stream = nullptr;
     bool int_busy = false;
+    // polyphase filter bank (pfb_api.hip): d_pfb_h = the prototype, pfb_taps * nfft float32 (sdrk_plan_set_pfb; 0 taps = none);
+    // pfb_assign = pfb4096_kernel's frame assignment (kernels_pfb.h); d_pfb_stage = folded complex64 frames of the lengths
+    // without a folding transform, at most 64 MiB, only grows; ev_pfb follows the last work enqueued on it (on pfb_stream)
+    float* d_pfb_h = nullptr;
+    int pfb_taps = 0;
+    int pfb_assign = 0;
+    void* d_pfb_stage = nullptr;
+    size_t pfb_stage_cap = 0;
+    hipEvent_t ev_pfb = nullptr;
+    hipStream_t pfb_stream = nullptr;
+    bool pfb_busy = false;
 };
 
 namespace sdrk_host {
@@ -222,6 +233,7 @@ struct HostIo {
     int precision = 32;            // the plan kind the entry point serves (32 / 64)
     int zero_copy_max_nfft = 0;    // longest frame whose kernel may read / write pinned host memory itself
     int zero_copy_min_nfft = 0;    // ... and the shortest
+    size_t in_span = 0;            // input samples a frame reads from its start (0: nfft; pfb_api.hip: taps * nfft)
     LaunchFn launch = nullptr;
 };
 

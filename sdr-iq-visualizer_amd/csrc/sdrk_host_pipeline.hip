@@ -112,7 +112,8 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
                     p->max_batch);
     HIP_TRY(hipSetDevice(p->device));
     const size_t nfft = (size_t)p->nfft;
-    const size_t in_samples = (n_frames - 1) * frame_stride + nfft;
+    const size_t span = io.in_span ? io.in_span : nfft;   // samples a frame reads from its start
+    const size_t in_samples = (n_frames - 1) * frame_stride + span;
     const size_t in_elem = io.in_elem, out_elem = io.out_elem;
     const int epilogue = io.epilogue;
     const size_t in_bytes = in_samples * in_elem;
@@ -170,7 +171,7 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     if (per > target / (nfft * out_elem)) per = target / (nfft * out_elem);   // heavily overlapped frames: bound the rows too
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
-    const size_t chunk_in = ((per - 1) * frame_stride + nfft) * in_elem;
+    const size_t chunk_in = ((per - 1) * frame_stride + span) * in_elem;   // (with the span's overlap into the next chunk)
     const size_t chunk_out = per * nfft * out_elem;
     sdrk::CopyPool& pool = sdrk::CopyPool::get();
     HostTrace tr;
@@ -205,7 +206,7 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     for (size_t f0 = 0; f0 < n_frames; f0 += per, ++c) {
         HostSlot& s = p->slot[c % HOST_SLOTS];
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
-        const size_t cin = ((nf - 1) * frame_stride + nfft) * in_elem;
+        const size_t cin = ((nf - 1) * frame_stride + span) * in_elem;
         const size_t cout = nf * nfft * out_elem;
         st = slot_retire(s, tr);                               // chunk c - HOST_SLOTS: rows out, slot free
         if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);

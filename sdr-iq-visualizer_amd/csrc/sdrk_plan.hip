@@ -508,6 +508,9 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_int_state) (void)hipFree(p->d_int_state);
     if (p->d_int_stage) (void)hipFree(p->d_int_stage);
     if (p->ev_int) (void)hipEventDestroy(p->ev_int);
+    if (p->d_pfb_h) (void)hipFree(p->d_pfb_h);
+    if (p->d_pfb_stage) (void)hipFree(p->d_pfb_stage);
+    if (p->ev_pfb) (void)hipEventDestroy(p->ev_pfb);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {

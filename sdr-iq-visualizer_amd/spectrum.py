@@ -27,12 +27,19 @@ calls ``ci16_le``: a C-contiguous int16 array whose last axis holds (I, Q).  ``x
 the float32 path — the result has the same bits as the complex64 call on the widened samples, from half the input bytes.
 No scale is applied (fold 1/32768 into a custom window, or add a constant to the dB rows).
 
+``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` and the module function ``pfb_db``) put a polyphase filter
+bank front end before the transform: a prototype filter of ``T*nfft`` float32 coefficients (``pfb_prototype``: a windowed
+sinc) weights ``T*nfft`` consecutive samples, the ``T`` blocks are summed into ``nfft`` samples (float32, products and sums
+rounded one by one as numpy does on float32 arrays) and that frame is transformed, so that the bins are nearly rectangular
+channels instead of a window's main lobe and side lobes.  float32 plans with the rectangular window only.
+
 All arithmetic on samples happens on the GPU through ``libsdrk.so``; nothing in
 this module computes a spectrum with numpy, and every entry point raises if the
 library or a device is missing.
 """
 from __future__ import annotations
 
+import hashlib
 import threading
 import time
 from typing import Optional, Sequence, Union
@@ -118,6 +125,34 @@ def _as_ci16(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
     return a
 
 
+PFB_MAX_TAPS = 32                 # sdrk.h: taps of a prototype filter
+
+
+def pfb_prototype(nfft: int, taps: int, window: WindowArg = "hann") -> np.ndarray:
+    """The default prototype filter of a polyphase filter bank with ``nfft`` channels and ``taps`` blocks: float32
+    ``sinc((m - (T*N - 1)/2) / N) * window(T*N)[m]`` for ``m < T*N``, computed in float64 and rounded once.  ``window``:
+    ``"hann"`` (``numpy.hanning``), ``"hamming"``, ``"blackman"``, ``None`` / ``"rect"``, or ``T*N`` coefficients."""
+    nfft, taps = int(nfft), int(taps)
+    if nfft < 2:
+        raise ValueError(f"nfft must be >= 2, got {nfft}")
+    if not 1 <= taps <= PFB_MAX_TAPS:
+        raise ValueError(f"taps must be in 1..{PFB_MAX_TAPS}, got {taps}")
+    n = taps * nfft
+    if window is None or (isinstance(window, str) and window.lower() in ("rect", "rectangular", "boxcar", "none")):
+        w = np.ones(n, dtype=np.float64)
+    elif isinstance(window, str):
+        makers = {"hann": np.hanning, "hanning": np.hanning, "hamming": np.hamming, "blackman": np.blackman}
+        if window.lower() not in makers:
+            raise ValueError(f"unknown window {window!r} (use 'hann', 'hamming', 'blackman', None or an array of taps*nfft floats)")
+        w = makers[window.lower()](n)
+    else:
+        w = np.asarray(window, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f"window must have shape ({n},), got {w.shape}")
+    m = np.arange(n, dtype=np.float64)
+    return (np.sinc((m - (n - 1) / 2.0) / nfft) * w).astype(np.float32)
+
+
 class SpectrumPlan:
     """A compiled plan for one (nfft, window, eps, shift, device, precision) combination.
 
@@ -153,6 +188,7 @@ class SpectrumPlan:
         self.shift = bool(shift)
         self.device = int(device)
         self._lock = threading.Lock()
+        self.pfb_taps = 0                              # taps of the prototype filter set by set_pfb() (0: none)
         self.last_placement: Optional[dict] = None     # report of the last tune_scratch() on this plan
         self._handle = c_void_p()
         wptr = warr.ctypes.data_as(c_void_p) if warr is not None else None
@@ -476,6 +512,84 @@ class SpectrumPlan:
                                                                     c_float(scale), c_void_p(d_out), int(launches), ms))
         return [float(v) for v in ms]
 
+    # -- polyphase filter bank: T blocks folded under a prototype in front of the transform (float32, rectangular plans) ----
+    def set_pfb(self, h) -> int:
+        """Set the prototype filter: ``taps*nfft`` float32 coefficients (``pfb_prototype`` makes the usual windowed sinc);
+        ``taps`` follows from the length and is returned.  May be called again with another prototype or another ``taps``."""
+        self._float32_only("the polyphase filter bank")
+        if self._wkey != "rect":
+            raise ValueError("the polyphase filter bank needs a plan with the rectangular window: the prototype is the window")
+        c = np.ascontiguousarray(np.asarray(h, dtype=np.float32))
+        if c.ndim != 1 or c.shape[0] == 0 or c.shape[0] % self.nfft:
+            raise ValueError(f"prototype must be a 1-D array of taps*{self.nfft} coefficients, got shape {c.shape}")
+        taps = c.shape[0] // self.nfft
+        if taps > PFB_MAX_TAPS:
+            raise ValueError(f"prototype has {taps} taps, at most {PFB_MAX_TAPS} are supported")
+        with self._lock:
+            check(lib().sdrk_plan_set_pfb(self.handle, taps, c.ctypes.data_as(c_void_p)))
+            self.pfb_taps = taps
+        return taps
+
+    def _pfb_ready(self) -> int:
+        self._float32_only("the polyphase filter bank")
+        if self.pfb_taps < 1:
+            raise ValueError("no prototype filter set: call set_pfb() first")
+        return self.pfb_taps * self.nfft
+
+    def pfb_frames(self, n_samples: int, hop: Optional[int] = None) -> int:
+        """Rows ``pfb_db`` returns for a stream of ``n_samples``: frame r covers samples ``[r*hop, r*hop + taps*nfft)``,
+        so ``1 + (n_samples - taps*nfft) // hop`` (0 if the stream is shorter than one span)."""
+        span = self._pfb_ready()
+        hop = self.nfft if hop is None else int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        return 0 if int(n_samples) < span else 1 + (int(n_samples) - span) // hop
+
+    def pfb_db(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """float32 dB rows ``(pfb_frames, nfft)`` of the polyphase filter bank over one contiguous complex64 stream: the
+        plan's ``spectrum_db`` of the folded frames ``sum_t h[t*nfft + n] * x[r*hop + t*nfft + n]``, bit for bit what
+        numpy's float32 fold followed by ``spectrum_db`` gives; the fold runs inside the transform on the GPU."""
+        self._pfb_ready()
+        x = _as_c64(iq).reshape(-1)
+        hop = self.nfft if hop is None else int(hop)
+        rows = self.pfb_frames(x.shape[0], hop)
+        out = self._out_array(out, (rows, self.nfft), np.float32)
+        if rows:
+            self._run_host(lib().sdrk_exec_host_pfb, x, rows, hop, out)
+        return out
+
+    def pfb_fft(self, iq, hop: Optional[int] = None) -> np.ndarray:
+        """complex64 spectra ``(pfb_frames, nfft)`` of the folded frames (fftshifted if the plan shifts), no log."""
+        self._pfb_ready()
+        x = _as_c64(iq).reshape(-1)
+        hop = self.nfft if hop is None else int(hop)
+        rows = self.pfb_frames(x.shape[0], hop)
+        out = np.empty((rows, self.nfft), dtype=np.complex64)
+        if rows:
+            self._run_host(lib().sdrk_exec_fft_host_pfb, x, rows, hop, out)
+        return out
+
+    def exec_device_pfb(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
+                        stream: int = 0) -> None:
+        """Device pointers: the raw complex64 stream in (``(n_frames-1)*frame_stride + taps*nfft`` samples) / float32 rows
+        out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        self._pfb_ready()
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                             c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def exec_device_pfb_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
+                                   frame_stride: Optional[int] = None) -> list:
+        """``exec_device_pfb`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        self._pfb_ready()
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                                        c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -779,6 +893,28 @@ def welch_psd_streamed_ci16(iq, nfft: int, sample_rate: float, hop: Optional[int
     """``welch_psd_streamed`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
     x = _as_ci16(iq, stream=True)
     return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed_ci16(x, sample_rate, hop)
+
+
+def pfb_db(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12, shift: bool = True,
+           device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Polyphase-filter-bank dB rows ``(rows, nfft)`` over one contiguous complex64 stream: ``taps`` blocks of ``nfft``
+    samples folded under ``prototype`` (``taps*nfft`` float32 coefficients; default ``pfb_prototype(nfft, taps)``) in front
+    of the transform, one row per ``hop`` samples (default ``nfft``); ``rows = 1 + (len(iq) - taps*nfft) // hop``.  A plan is
+    cached per prototype (``SpectrumPlan.set_pfb`` / ``pfb_db`` for explicit plans)."""
+    nfft, taps = int(nfft), int(taps)
+    h = pfb_prototype(nfft, taps) if prototype is None else np.ascontiguousarray(np.asarray(prototype, dtype=np.float32))
+    if h.shape != (taps * nfft,):
+        raise ValueError(f"prototype must have shape ({taps * nfft},), got {h.shape}")
+    key = (int(device), nfft, ("pfb", hashlib.sha1(h.tobytes()).digest()), float(eps), bool(shift), "single")
+    plan = _plans.get(key)
+    if plan is None:
+        with _plans_lock:
+            plan = _plans.get(key)
+            if plan is None:
+                plan = SpectrumPlan(nfft, eps=eps, shift=shift, device=device)
+                plan.set_pfb(h)
+                _plans[key] = plan
+    return plan.pfb_db(iq, hop, out=out)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

@@ -24,6 +24,8 @@ from .spectrum import (  # noqa: E402
     freq_axis,
     integrated_db,
     integrated_db_ci16,
+    pfb_db,
+    pfb_prototype,
     process_frame,
     spectrum_db,
     spectrum_db_ci16,
@@ -51,6 +53,8 @@ __all__ = [
     "integrated_db_ci16",
     "is_pinned",
     "library_path",
+    "pfb_db",
+    "pfb_prototype",
     "pinned_empty",
     "process_frame",
     "registered",
