@@ -336,7 +336,7 @@ int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t 
  * the rectangular transform of numpy's float32 h*x.  Every other entry point of a plan with a prototype set behaves as before.
  * N = 4096 folds inside the transform's registers (8 B/sample from device memory at frame_stride = nfft, 4 B/sample out); other
  * lengths fold into plan-owned staging of at most 64 MiB and run the plan's own transform.
- * Not provided: int16 input, integration over K folded frames, double precision, waterfall appends. */
+ * Integration over K folded frames is the next section.  Not provided: int16 input, double precision, waterfall appends. */
 /* the prototype: taps*nfft float32 from host memory into a plan-owned device copy; may be called again with another prototype
  * or another T (not while work of this plan is in flight) */
 int sdrk_plan_set_pfb(sdrk_plan* plan, int taps, const float* h);
@@ -353,6 +353,32 @@ int sdrk_exec_device_pfb_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_
 int sdrk_exec_host_pfb(sdrk_plan* plan, const void* iq_c64, size_t n_frames, size_t frame_stride, float* out_db);
 /* the complex spectrum of the folded frames: out_c64[f][k] = fft(y_f)[k], fftshifted if the plan shifts */
 int sdrk_exec_fft_host_pfb(sdrk_plan* plan, const void* iq_c64, size_t n_frames, size_t frame_stride, void* out_c64);
+
+/* ---- integrated polyphase filter bank spectra: one row per K folded frames ---------------
+ * The form a filter bank is used in (spectrometer back ends, monitoring receivers): fold, transform, |.|^2, and accumulate K
+ * spectra per output row.  Frames are cut as in the section above — frame f starts at sample f*frame_stride (any stride >= 1)
+ * and covers T*nfft samples; the buffer holds (n_groups*k_frames - 1)*frame_stride + T*nfft samples — and folded to y_f by the
+ * same float32 arithmetic; group g is the frames [g*k_frames, (g+1)*k_frames).  The row of a group is, bit for bit, what
+ * sdrk_exec_device_integrated returns on the same plan for the packed frames y_f (frame_stride = nfft) with the same n_groups,
+ * k_frames, detector, out_form and scale: SDRK_DET_MEAN (compensated), _MAX or _MIN of |fft(y_f)[k]|^2 as SDRK_INT_OUT_DB or
+ * SDRK_INT_OUT_POWER, in the plan's shift order and with its eps — at every nfft of a float32 plan (chirp-z and the two-pass
+ * lengths included), every T in [1, 32], K, number of groups and stride, from the device entry and the host entry alike.
+ * The refusals are those of the two sections together, each SDRK_ERR_INVALID with a message: a windowed plan, an f64 plan, a
+ * plan with no prototype set; an unknown detector or out_form; n_groups or k_frames = 0 or their product out of range;
+ * frame_stride = 0; NULL pointers.  A plan that has refused a call still works.
+ * N = 4096 folds and reduces inside the transform's registers: 8 B/sample read from device memory at frame_stride = nfft, 4/K
+ * written.  Other lengths fold into the PFB staging, transform into the integrate staging (each at most 64 MiB) and reduce
+ * from there.  The device entry has no frame limit; the host entry runs in device memory that does not grow with the stream. */
+/* device in / device out (d_out: n_groups * nfft float32), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_pfb_integrated(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                    int detector, int out_form, float scale, float* d_out, void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` calls (bench harness) */
+int sdrk_exec_device_pfb_integrated_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames,
+                                               size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                               int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
+int sdrk_exec_host_pfb_integrated(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                  int detector, int out_form, float scale, float* out);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

@@ -160,6 +160,12 @@ SYMBOLS = [
     ("sdrk_exec_device_pfb_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_pfb", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     ("sdrk_exec_fft_host_pfb", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                           c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                              c_void_p]),
 ]
 
 _lib = None

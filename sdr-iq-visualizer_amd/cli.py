@@ -35,7 +35,8 @@ def main(argv=None) -> int:
     p.add_argument("--detector", choices=["mean", "max", "min"], default="mean", help="what --integrate keeps per bin")
     p.add_argument("--pfb", type=_positive, default=0, metavar="T",
                    help="also write polyphase-filter-bank dB rows: T blocks of --nfft samples folded under the default "
-                        "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db)")
+                        "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db); with --integrate K also one "
+                        "row per K folded frames (pfb_integrated_db)")
     p.add_argument("--window", default=None)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--out", default=None, help="write results to this .npz")
@@ -106,6 +107,10 @@ def main(argv=None) -> int:
         report["pfb_rows"] = int(rows.shape[0])
         if rows.shape[0] == 0:
             print(f"recording holds fewer than {args.pfb} blocks of {args.nfft} samples: no PFB row", file=sys.stderr)
+        if args.integrate:   # both: the spectrometer form as well, one row per K folded frames
+            rows = spectrum.pfb_integrated_db(x, args.nfft, args.pfb, args.integrate, detector=args.detector, device=args.device)
+            results["pfb_integrated_db"] = rows
+            report["pfb_integrated_rows"] = int(rows.shape[0])
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out

@@ -1,5 +1,6 @@
 // integrate_call.h — the machinery of an integrated-spectrum call (one row per K frames), shared by the host files of its
-// input formats: integrate_api.hip (complex64 samples) and kgroup_ci16_api.hip (int16 I,Q).  An IntIo says what differs
+// input formats: integrate_api.hip (complex64 samples), kgroup_ci16_api.hip (int16 I,Q) and pfb_groups_api.hip (complex64
+// samples folded by the plan's polyphase filter bank).  An IntIo says what differs
 // between them, the way HostIo (plan_internal.h) does for exec_host: the bytes per input sample, the launcher of the N = 4096
 // kernel that reduces inside the transform, and the plan's own transform for every other length.  Each host file defines its
 // launchers and hands its IntIo in, so neither refers to a kernel the other's stand-ins (tests/fake_*) do not define.
@@ -24,6 +25,8 @@ struct IntIo {
     size_t in_elem = 0;                                            // bytes per input sample: 8 (complex64) or 4 (int16 I,Q)
     hipError_t (*fused)(const sdrk::IntegrateArgs&) = nullptr;     // N = 4096: the reduction inside the transform
     LaunchFn transform = nullptr;                                  // every other length: the plan's transform (EPI_COMPLEX)
+    size_t in_span = 0;                                            // input samples a frame reads from its start (0: nfft;
+                                                                   // pfb_groups_api.hip: taps * nfft)
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -132,6 +135,8 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
     a.shift = p->shift;
     a.num_cus = p->num_cus;
     a.stream = c.stream;
+    a.d_pfb_h = p->d_pfb_h;   // (read by the polyphase-filter-bank launcher alone)
+    a.pfb_taps = p->pfb_taps;
     const size_t step = c.fused ? f1 - f0 : c.stage_frames;
     for (size_t s0 = f0; s0 < f1; s0 += step) {
         const size_t s1 = f1 - s0 < step ? f1 : s0 + step;
@@ -223,6 +228,7 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     st = call_begin(c, io, p, n_groups, k_frames, frame_stride, detector, out_form, scale, p->stream);
     if (st != SDRK_OK) return st;
     const size_t nfft = (size_t)p->nfft, K = k_frames, n_frames = n_groups * K, elem = io.in_elem;
+    const size_t span = io.in_span ? io.in_span : nfft;   // a chunk carries its span - nfft samples of overlap
     const bool direct = c.sp.slices == 1;   // rows leave per chunk; split calls finalize once at the end
     // frames per chunk: bounded by the input bytes and, through the rows a chunk can complete, by the output bytes
     size_t per = HOST_CHUNK_BYTES / (frame_stride * elem);
@@ -231,9 +237,9 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     if (per / K >= rows_cap) per = rows_cap * K;
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
-    const size_t chunk_in = ((per - 1) * frame_stride + nfft) * elem;
+    const size_t chunk_in = ((per - 1) * frame_stride + span) * elem;
     const size_t chunk_out = direct ? (per / K + 1) * nfft * sizeof(float) : 0;
-    const size_t in_bytes = ((n_frames - 1) * frame_stride + nfft) * elem;
+    const size_t in_bytes = ((n_frames - 1) * frame_stride + span) * elem;
     const size_t out_bytes = n_groups * nfft * sizeof(float);
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
     auto retire = [&](HostSlot& s) -> int {
@@ -248,7 +254,7 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     for (size_t f0 = 0; f0 < n_frames; f0 += per, ++n) {
         HostSlot& s = p->slot[n % HOST_SLOTS];
         const size_t f1 = n_frames - f0 < per ? n_frames : f0 + per;
-        const size_t cin = ((f1 - f0 - 1) * frame_stride + nfft) * elem;
+        const size_t cin = ((f1 - f0 - 1) * frame_stride + span) * elem;
         const size_t row0 = f0 / K, rows = direct ? f1 / K - row0 : 0, cout = rows * nfft * sizeof(float);
         st = retire(s);
         if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);

@@ -33,6 +33,10 @@ struct IntegrateArgs {
     int shift = 1;
     int num_cus = 256;
     hipStream_t stream = nullptr;
+    // polyphase filter bank in front (pfb4096_groups.hip): the plan's prototype, pfb_taps * nfft float32; d_in is then the raw
+    // stream and a frame covers pfb_taps * nfft samples from its start
+    const float* d_pfb_h = nullptr;
+    int pfb_taps = 0;
 };
 
 hipError_t launch_fft4096_integrate(const IntegrateArgs& a);

@@ -15,29 +15,12 @@
 // bound; the coefficients come through the cache with ordinary loads (T * 16 KiB does not fit beside the exchange buffer in LDS
 // at three workgroups per CU).
 //
-// Out of scope here: int16 input, integration over K folded frames, double precision, waterfall appends.
+// Integration over K folded frames is pfb4096_groups.hip.  Out of scope here: int16 input, double precision, waterfall appends.
 #include "fft4096_core.h"
 #include "kernels_pfb.h"
+#include "pfb4096_in.h"
 
 namespace sdrk {
-
-// Input policy: one tap block (16 words per thread, sample tid + 256 j) and its coefficients h[tid + 256 j].  The samples are
-// read T times at hop = N, so unlike the flagship's they are loaded with the default cache policy.
-struct F4kInPfb {
-    typedef v2u word;
-    static __device__ __forceinline__ void issue(word (&x)[16], float (&c)[16], const float2* block, const float* hblock, int tid) {
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(block, F4K_N * 8);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, tid * 8, j * 2048, 0);
-        __amdgpu_buffer_rsrc_t rh = frame_rsrc(hblock, F4K_N * 4);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) c[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rh, tid * 4, j * 1024, 0));
-    }
-    static __device__ __forceinline__ cf widen(word w) {
-        v2f t = __builtin_bit_cast(v2f, w);
-        return cf{t.x, t.y};
-    }
-};
 
 template <int EPILOGUE>
 __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void pfb4096_kernel(

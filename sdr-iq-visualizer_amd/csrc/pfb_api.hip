@@ -8,7 +8,7 @@
 // staging, then plan_launch" on the same stream, the staging capped at 64 MiB and cut at frame boundaries however many frames
 // the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame:
 // a chunk carries its (T - 1) * nfft samples of overlap.
-// Out of scope: int16 input, integration over K folded frames, double precision, waterfall appends.
+// Integration over K folded frames is pfb_groups_api.hip.  Out of scope: int16 input, double precision, waterfall appends.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -98,17 +98,6 @@ int check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frames, size_t f
     return SDRK_OK;
 }
 
-// One PFB transform of the plan on a raw complex64 stream: a LaunchFn (the transform of the numpy boundary too).
-int launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
-    if (n_frames == 0) return SDRK_OK;
-    if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
-    if (p->nfft != 4096 || p->blu_inner) return fold_route(p, d_in, n_frames, stride, d_out, epilogue, stream);
-    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
-    const hipError_t e = sdrk::launch_pfb4096(a, p->d_pfb_h, p->pfb_taps, p->pfb_assign);
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "pfb kernel launch failed: %s", hipGetErrorString(e));
-    return SDRK_OK;
-}
-
 // complex64 stream in, T * nfft samples per frame; float32 rows or complex64 out; always through the copy engines (every
 // sample is read T times: over PCIe it would cross T times)
 HostIo pfb_io(const sdrk_plan* p, int epilogue) {
@@ -124,6 +113,18 @@ HostIo pfb_io(const sdrk_plan* p, int epilogue) {
 
 }  // namespace
 
+// One PFB transform of the plan on a raw complex64 stream: a LaunchFn (the transform of the numpy boundary and of
+// pfb_groups_api.hip's generic route too; declared in plan_internal.h).
+int sdrk_host::launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+    if (n_frames == 0) return SDRK_OK;
+    if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
+    if (p->nfft != 4096 || p->blu_inner) return fold_route(p, d_in, n_frames, stride, d_out, epilogue, stream);
+    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
+    const hipError_t e = sdrk::launch_pfb4096(a, p->d_pfb_h, p->pfb_taps, p->pfb_assign);
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "pfb kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
 extern "C" {
 
 int sdrk_plan_set_pfb(sdrk_plan* p, int taps, const float* h) {
@@ -135,6 +136,7 @@ int sdrk_plan_set_pfb(sdrk_plan* p, int taps, const float* h) {
     // not with work in flight, says the header; make it safe all the same for work on the plan's own stream and staging
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (p->pfb_busy) HIP_TRY(hipEventSynchronize(p->ev_pfb));
+    if (p->int_busy) HIP_TRY(hipEventSynchronize(p->ev_int));   // sdrk_exec_*_pfb_integrated reads the prototype too
     const size_t bytes = (size_t)taps * (size_t)p->nfft * sizeof(float);
     p->pfb_taps = 0;
     if (p->d_pfb_h) {

@@ -252,4 +252,9 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
 // One transform of a float32 plan on int16 I,Q input (4 bytes per sample), the ci16 form of plan_launch: a LaunchFn.
 int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 
+// ---- pfb_api.hip ----
+// One polyphase-filter-bank transform of a float32 plan on a raw complex64 stream (taps * nfft samples per frame): a LaunchFn.
+// N = 4096 is one launch; every other length folds into d_pfb_stage and runs the plan's transform on that.
+int launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
+
 }  // namespace sdrk_host

@@ -27,8 +27,8 @@ calls ``ci16_le``: a C-contiguous int16 array whose last axis holds (I, Q).  ``x
 the float32 path — the result has the same bits as the complex64 call on the widened samples, from half the input bytes.
 No scale is applied (fold 1/32768 into a custom window, or add a constant to the dB rows).
 
-``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` and the module function ``pfb_db``) put a polyphase filter
-bank front end before the transform: a prototype filter of ``T*nfft`` float32 coefficients (``pfb_prototype``: a windowed
+``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` / ``pfb_integrate`` and the module functions ``pfb_db`` and
+``pfb_integrated_db``) put a polyphase filter bank front end before the transform: a prototype filter of ``T*nfft`` float32 coefficients (``pfb_prototype``: a windowed
 sinc) weights ``T*nfft`` consecutive samples, the ``T`` blocks are summed into ``nfft`` samples (float32, products and sums
 rounded one by one as numpy does on float32 arrays) and that frame is transformed, so that the bins are nearly rectangular
 channels instead of a window's main lobe and side lobes.  float32 plans with the rectangular window only.
@@ -590,6 +590,72 @@ class SpectrumPlan:
                                                         c_void_p(d_out), int(launches), ms))
         return [float(v) for v in ms]
 
+    # ... integrated: one row per k folded frames (the spectrometer form of the filter bank)
+    def _pfb_int_ready(self, detector: str, out: str):
+        span = self._pfb_ready()
+        if self._wkey != "rect":
+            raise ValueError("the polyphase filter bank needs a plan with the rectangular window: the prototype is the window")
+        det, form = self._int_codes(detector, out)
+        return span, det, form
+
+    def pfb_integrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
+        """Rows ``pfb_integrate`` returns for a stream of ``n_samples``: the ``pfb_frames`` full frames in whole groups of
+        ``k``; trailing frames that do not fill a group are dropped."""
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        return self.pfb_frames(n_samples, hop) // int(k)
+
+    def pfb_integrate(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                      scale: float = 1.0) -> np.ndarray:
+        """One float32 row per ``k`` consecutive polyphase-filter-bank frames of one contiguous complex64 stream,
+        ``(groups, nfft)``: per bin the mean, maximum or minimum over the group of ``|fft(y_f)|^2`` with ``y_f`` the folded
+        frame of ``pfb_db``, as ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``) — bit for bit
+        ``integrate`` on the packed folded frames.  Fold, transform and reduction run in one kernel at nfft = 4096; the
+        stream goes through in chunks, in device memory that does not depend on its length."""
+        _, det, form = self._pfb_int_ready(detector, out)
+        x = _as_c64(iq).reshape(-1)
+        hop = self.nfft if hop is None else int(hop)
+        groups = self.pfb_integrated_groups(x.shape[0], k, hop)
+        res = np.empty((groups, self.nfft), dtype=np.float32)
+        if groups:
+            with self._lock:
+                check(lib().sdrk_exec_host_pfb_integrated(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
+                                                          c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
+                                                          res.ctypes.data_as(c_void_p)))
+        return res
+
+    def _pfb_int_device_args(self, n_groups: int, k: int, frame_stride: Optional[int], detector: str, out: str):
+        _, det, form = self._pfb_int_ready(detector, out)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        if int(k) < 1 or int(n_groups) < 1:
+            raise ValueError("k and n_groups must be >= 1")
+        if stride < 1:
+            raise ValueError("frame_stride must be >= 1")
+        return stride, det, form
+
+    def exec_device_pfb_integrated(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
+                                   frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                   scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: the raw complex64 stream in (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples),
+        ``n_groups`` float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_integrated(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
+                                                        c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
+                                                        c_void_p(stream) if stream else None))
+
+    def exec_device_pfb_integrated_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                              frame_stride: Optional[int] = None, detector: str = "mean",
+                                              out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_pfb_integrated`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_integrated_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
+                                                                   c_size_t(int(k)), c_size_t(stride), det, form,
+                                                                   c_float(scale), c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -895,13 +961,7 @@ def welch_psd_streamed_ci16(iq, nfft: int, sample_rate: float, hop: Optional[int
     return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed_ci16(x, sample_rate, hop)
 
 
-def pfb_db(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12, shift: bool = True,
-           device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
-    """Polyphase-filter-bank dB rows ``(rows, nfft)`` over one contiguous complex64 stream: ``taps`` blocks of ``nfft``
-    samples folded under ``prototype`` (``taps*nfft`` float32 coefficients; default ``pfb_prototype(nfft, taps)``) in front
-    of the transform, one row per ``hop`` samples (default ``nfft``); ``rows = 1 + (len(iq) - taps*nfft) // hop``.  A plan is
-    cached per prototype (``SpectrumPlan.set_pfb`` / ``pfb_db`` for explicit plans)."""
-    nfft, taps = int(nfft), int(taps)
+def _cached_pfb_plan(nfft: int, taps: int, prototype, eps: float, shift: bool, device: int) -> "SpectrumPlan":
     h = pfb_prototype(nfft, taps) if prototype is None else np.ascontiguousarray(np.asarray(prototype, dtype=np.float32))
     if h.shape != (taps * nfft,):
         raise ValueError(f"prototype must have shape ({taps * nfft},), got {h.shape}")
@@ -914,7 +974,28 @@ def pfb_db(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, 
                 plan = SpectrumPlan(nfft, eps=eps, shift=shift, device=device)
                 plan.set_pfb(h)
                 _plans[key] = plan
-    return plan.pfb_db(iq, hop, out=out)
+    return plan
+
+
+def pfb_db(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12, shift: bool = True,
+           device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Polyphase-filter-bank dB rows ``(rows, nfft)`` over one contiguous complex64 stream: ``taps`` blocks of ``nfft``
+    samples folded under ``prototype`` (``taps*nfft`` float32 coefficients; default ``pfb_prototype(nfft, taps)``) in front
+    of the transform, one row per ``hop`` samples (default ``nfft``); ``rows = 1 + (len(iq) - taps*nfft) // hop``.  A plan is
+    cached per prototype (``SpectrumPlan.set_pfb`` / ``pfb_db`` for explicit plans)."""
+    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_db(iq, hop, out=out)
+
+
+def pfb_integrated_db(iq, nfft: int, taps: int, k: int, hop: Optional[int] = None, detector: str = "mean", prototype=None, *,
+                      eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """dB rows of a polyphase-filter-bank spectrometer: one row per ``k`` folded frames of ``iq``, the mean / max / min
+    power per bin (``SpectrumPlan.pfb_integrate``); prototype and plan cache as for ``pfb_db``."""
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    if hop is not None and int(hop) < 1:
+        raise ValueError("hop must be >= 1")
+    SpectrumPlan._int_codes(detector, "db")
+    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_integrate(iq, k, hop, detector, "db")
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

@@ -25,6 +25,7 @@ from .spectrum import (  # noqa: E402
     integrated_db,
     integrated_db_ci16,
     pfb_db,
+    pfb_integrated_db,
     pfb_prototype,
     process_frame,
     spectrum_db,
@@ -54,6 +55,7 @@ __all__ = [
     "is_pinned",
     "library_path",
     "pfb_db",
+    "pfb_integrated_db",
     "pfb_prototype",
     "pinned_empty",
     "process_frame",
