@@ -336,7 +336,8 @@ int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t 
  * the rectangular transform of numpy's float32 h*x.  Every other entry point of a plan with a prototype set behaves as before.
  * N = 4096 folds inside the transform's registers (8 B/sample from device memory at frame_stride = nfft, 4 B/sample out); other
  * lengths fold into plan-owned staging of at most 64 MiB and run the plan's own transform.
- * Integration over K folded frames is the next section.  Not provided: int16 input, double precision, waterfall appends. */
+ * Integration over K folded frames is the next section, int16 I,Q input the one after it.  Not provided: double precision,
+ * waterfall appends. */
 /* the prototype: taps*nfft float32 from host memory into a plan-owned device copy; may be called again with another prototype
  * or another T (not while work of this plan is in flight) */
 int sdrk_plan_set_pfb(sdrk_plan* plan, int taps, const float* h);
@@ -379,6 +380,30 @@ int sdrk_exec_device_pfb_integrated_timed_each(sdrk_plan* plan, const void* d_iq
 /* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
 int sdrk_exec_host_pfb_integrated(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                                   int detector, int out_form, float scale, float* out);
+
+/* ---- polyphase filter bank spectra from int16 I,Q: per frame and integrated, 4 bytes per sample ----
+ * The two sections above on interleaved little-endian int16 I,Q (SigMF ci16_le), as a radio delivers it:
+ * x[n] = float32(I[n]) + i*float32(Q[n]) exactly, and every entry point returns the bits its complex64 counterpart above
+ * returns for those widened samples — at every nfft of a float32 rectangular plan, every T in [1, 32], stride, frame or group
+ * count, K, detector, out_form, scale and shift, from the device entries and the host entries alike.  The argument lists are
+ * the counterparts'; frame_stride counts samples; the buffer holds (frames - 1)*frame_stride + T*nfft samples of 4 bytes each;
+ * frame starts need 4-byte alignment only.  The refusals are the counterparts' too, each SDRK_ERR_INVALID with a message.
+ * N = 4096 folds the int16 samples inside the transform's registers: 4 B/sample read from device memory at frame_stride = nfft
+ * (4*T with the cached re-reads, half the complex64 form's), 4 or 4/K written.  Other lengths fold the int16 samples straight
+ * into the PFB staging (no widened copy of the stream) and go on as above.  The host entries move 4 B/sample over the link. */
+int sdrk_exec_device_pfb_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_frames, size_t frame_stride, float* d_out_db,
+                              void* stream);
+int sdrk_exec_device_pfb_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_frames, size_t frame_stride,
+                                         float* d_out_db, int launches, float* each_ms);
+int sdrk_exec_host_pfb_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_frames, size_t frame_stride, float* out_db);
+int sdrk_exec_fft_host_pfb_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_frames, size_t frame_stride, void* out_c64);
+int sdrk_exec_device_pfb_integrated_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                         size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_pfb_integrated_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                                    size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                    int launches, float* each_ms);
+int sdrk_exec_host_pfb_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                       int detector, int out_form, float scale, float* out);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

@@ -166,6 +166,17 @@ SYMBOLS = [
                                                            c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_pfb_integrated", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
                                               c_void_p]),
+    # ... the seven above from int16 I,Q: the bits of the complex64 forms on the widened samples
+    ("sdrk_exec_device_pfb_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_pfb_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                     c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                                c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                   c_void_p]),
 ]
 
 _lib = None

@@ -58,7 +58,7 @@ def main(argv=None) -> int:
         return 0
 
     from . import spectrum
-    # one read; an int16 recording stays int16 (the spectrum row and the --integrate rows are computed from the int16 samples
+    # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
     # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
     samples, meta = sigmf_io.read_sigmf(args.path, native=True)
     raw16 = samples if samples.dtype == np.int16 else None
@@ -99,16 +99,23 @@ def main(argv=None) -> int:
         report["integrated_rows"] = int(rows.shape[0])
         if rows.shape[0] == 0:
             print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no integrated row", file=sys.stderr)
-    if args.pfb:   # the prototype is the window: --window does not apply; int16 recordings are widened (no int16 PFB form)
-        x = raw16.astype(np.float32).view(np.complex64).reshape(-1) if raw16 is not None else samples
-        rows = spectrum.pfb_db(x, args.nfft, args.pfb, device=args.device)
+    if args.pfb:   # the prototype is the window: --window does not apply; an int16 recording goes in as it is
+        if raw16 is not None:
+            rows = spectrum.pfb_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.pfb, device=args.device)
+        else:
+            rows = spectrum.pfb_db(samples, args.nfft, args.pfb, device=args.device)
         results["pfb_db"] = rows
         report["pfb_taps"] = args.pfb
         report["pfb_rows"] = int(rows.shape[0])
         if rows.shape[0] == 0:
             print(f"recording holds fewer than {args.pfb} blocks of {args.nfft} samples: no PFB row", file=sys.stderr)
         if args.integrate:   # both: the spectrometer form as well, one row per K folded frames
-            rows = spectrum.pfb_integrated_db(x, args.nfft, args.pfb, args.integrate, detector=args.detector, device=args.device)
+            if raw16 is not None:
+                rows = spectrum.pfb_integrated_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.pfb, args.integrate,
+                                                       detector=args.detector, device=args.device)
+            else:
+                rows = spectrum.pfb_integrated_db(samples, args.nfft, args.pfb, args.integrate, detector=args.detector,
+                                                  device=args.device)
             results["pfb_integrated_db"] = rows
             report["pfb_integrated_rows"] = int(rows.shape[0])
     if args.out:

@@ -25,10 +25,17 @@ hipError_t launch_pfb4096(const LaunchArgs& a, const float* d_h, int taps, int a
 hipError_t launch_pfb_fold(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
                            void* d_out, int num_cus, hipStream_t stream);
 
+// The same two on interleaved little-endian int16 I,Q, 4 bytes per sample (pfb4096_i16.hip, pfb_fold_i16.hip): d_iq points at
+// int16 pairs, frame_stride counts samples, x = float32(I) + i float32(Q) exactly, then the arithmetic above.
+hipError_t launch_pfb4096_i16(const LaunchArgs& a, const float* d_h, int taps, int assign);
+hipError_t launch_pfb_fold_i16(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
+                               void* d_out, int num_cus, hipStream_t stream);
+
 // pfb4096_groups.hip: N = 4096, the fold in front of the transform and the reduction over K folded frames behind it, ONE row
 // per group; an IntegrateArgs (kernels_integrate.h) with d_pfb_h / pfb_taps set, d_in the raw stream, d_window null
 struct IntegrateArgs;
 hipError_t launch_pfb4096_groups(const IntegrateArgs& a);
+hipError_t launch_pfb4096_i16_groups(const IntegrateArgs& a);   // pfb4096_i16_groups.hip: d_in points at int16 pairs
 
 #ifdef __HIPCC__
 typedef float pfb_v2f __attribute__((ext_vector_type(2)));

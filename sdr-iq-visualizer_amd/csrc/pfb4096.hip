@@ -15,9 +15,11 @@
 // bound; the coefficients come through the cache with ordinary loads (T * 16 KiB does not fit beside the exchange buffer in LDS
 // at three workgroups per CU).
 //
-// Integration over K folded frames is pfb4096_groups.hip.  Out of scope here: int16 input, double precision, waterfall appends.
+// The body is pfb4096_body.h's (shared with the int16 form, pfb4096_i16.hip); this file instantiates it with F4kInPfb.
+// Integration over K folded frames is pfb4096_groups.hip.  Out of scope here: double precision, waterfall appends.
 #include "fft4096_core.h"
 #include "kernels_pfb.h"
+#include "pfb4096_body.h"
 #include "pfb4096_in.h"
 
 namespace sdrk {
@@ -26,71 +28,7 @@ template <int EPILOGUE>
 __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void pfb4096_kernel(
     const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw, size_t n_frames,
     const float* __restrict__ h, int taps, const float2* __restrict__ tw4096, float eps, int shift, int assign) {
-    typedef F4kInPfb In;
-    __shared__ float2 lds[f4k_lds_elems(false)];
-    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
-    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
-
-    // This workgroup's frames: first, first + step, ... below end.  Any partition gives the same rows; the choice decides which
-    // L2 the T readers of a block meet in (kernels_pfb.h).
-    size_t first = blockIdx.x, step = gridDim.x, end = n_frames;
-    if (assign == PFB_ASSIGN_XCD && gridDim.x >= 8) {
-        const size_t x = blockIdx.x & 7;
-        first = x * n_frames / 8 + (blockIdx.x >> 3);
-        end = (x + 1) * n_frames / 8;
-        step = (gridDim.x - x + 7) >> 3;   // workgroups with this x
-    } else if (assign == PFB_ASSIGN_RUNS) {
-        first = (size_t)blockIdx.x * n_frames / gridDim.x;
-        end = ((size_t)blockIdx.x + 1) * n_frames / gridDim.x;
-        step = 1;
-    }
-    if (first >= end) return;   // (the whole workgroup)
-
-    const int tid = threadIdx.x;
-    F4kAddr A = f4k_addr(tid);
-    f4k_init_tables(tw256, tw1, tw4096, tid);
-    __syncthreads();
-
-    const int xor_k2 = shift ? 8 : 0;
-    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
-    const int voff_out = tid * OUT_ELEM;
-
-    In::word nxt[16];
-    float cn[16];
-    auto issue = [&](size_t fr, int t) {
-        if (fr >= end) fr = first;  // harmless re-read past the end
-        In::issue(nxt, cn, iq + fr * frame_stride + (size_t)t * F4K_N, h + (size_t)t * F4K_N, tid);
-    };
-    // the block in flight -> w, c; the one after it (this frame's next tap, or the next frame's first) on its way
-    auto take = [&](cf (&w)[16], float (&c)[16], size_t f, int t) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            w[j] = In::widen(nxt[j]);
-            c[j] = cn[j];
-        }
-        if (t + 1 < taps) issue(f, t + 1); else issue(f + step, 0);
-    };
-    issue(first, 0);
-    for (size_t f = first; f < end; f += step) {
-        cf v[16];
-        {
-            cf w[16];
-            float c[16];
-            take(w, c, f, 0);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = pfb_mul(w[j], c[j]);
-        }
-        for (int t = 1; t < taps; ++t) {
-            cf w[16];
-            float c[16];
-            take(w, c, f, t);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = pfb_mac(v[j], w[j], c[j]);
-        }
-        f4k_transform(v, lds, tw256, tw1, A, tid);
-        f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + f * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
-                                voff_out, xor_k2, eps);
-    }
+    pfb4096_body<EPILOGUE, F4kInPfb>(iq, frame_stride, out_raw, n_frames, h, taps, tw4096, eps, shift, assign);
 }
 
 hipError_t launch_pfb4096(const LaunchArgs& a, const float* d_h, int taps, int assign) {

@@ -1,0 +1,51 @@
+// pfb4096_i16_groups.hip — pfb4096_groups.hip's spectrometer kernel reading interleaved little-endian int16 I,Q, 4 bytes per
+// sample: the T-tap fold, the transform and the reduction over K consecutive folded frames (mean with compensation, maximum
+// or minimum of |Y|^2 per bin) in one kernel, ONE row per group out.  The row is, bit for bit, pfb4096_groups_kernel's for the
+// widened samples x[n] = float32(I[n]) + i float32(Q[n]).
+//
+// The body is pfb4096_body.h's with the int16 input policy of pfb4096_in.h: the same unit bookkeeping, carry and partial rows,
+// the mean's compensation in the same 16 KiB of LDS, and across the transform only the next frame's samples in flight — 16
+// dwords here.  The registers that frees are left free.
+#include "pfb4096_body.h"
+
+namespace sdrk {
+
+template <int DET>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void pfb4096_i16_groups_kernel(
+    const unsigned* __restrict__ iq, size_t frame_stride, IntUnits c, float* __restrict__ out, float2* __restrict__ partials,
+    const float2* __restrict__ carry_in, float2* __restrict__ carry_out, const float* __restrict__ h, int taps,
+    const float2* __restrict__ tw4096, int shift) {
+    pfb4096_groups_body<DET, F4kInPfbI16>(iq, frame_stride, c, out, partials, carry_in, carry_out, h, taps, tw4096, shift);
+}
+
+hipError_t launch_pfb4096_i16_groups(const IntegrateArgs& a) {
+    if (a.f1 <= a.f0) return hipSuccess;
+    if (a.nfft != F4K_N || a.d_window || !a.d_pfb_h || a.pfb_taps < 1 || a.pfb_taps > PFB_MAX_TAPS) return hipErrorInvalidValue;
+    IntUnits c;
+    const IntSplit sp{a.slices, a.slice_len};
+    c.f0 = a.f0;
+    c.f1 = a.f1;
+    c.k = a.k;
+    c.slice_len = a.slice_len;
+    c.slices = (unsigned)a.slices;
+    c.u_first = integrate_unit_of(a.f0, a.k, sp);
+    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
+    c.out_row0 = a.out_row0;
+    c.out_form = a.out_form;
+    c.scale = a.scale;
+    c.eps = a.eps;
+    c.inv_k = 1.0f / (float)a.k;
+    dim3 g(f4k_grid(a.num_cus, F4K_WAVES, c.u_last - c.u_first + 1)), b(F4K_THREADS);
+    const unsigned* iq = static_cast<const unsigned*>(a.d_in);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(D)                                                                                                   \
+    hipLaunchKernelGGL((pfb4096_i16_groups_kernel<D>), g, b, 0, a.stream, iq, a.in_stride, c, a.d_out, a.d_partials, a.d_carry_in, \
+                       a.d_carry_out, a.d_pfb_h, a.pfb_taps, tw, a.shift)
+    if (a.detector == INT_DET_MEAN) SDRK_LAUNCH(INT_DET_MEAN);
+    else if (a.detector == INT_DET_MAX) SDRK_LAUNCH(INT_DET_MAX);
+    else SDRK_LAUNCH(INT_DET_MIN);
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace sdrk

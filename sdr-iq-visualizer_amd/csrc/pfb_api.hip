@@ -8,7 +8,8 @@
 // staging, then plan_launch" on the same stream, the staging capped at 64 MiB and cut at frame boundaries however many frames
 // the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame:
 // a chunk carries its (T - 1) * nfft samples of overlap.
-// Integration over K folded frames is pfb_groups_api.hip.  Out of scope: int16 input, double precision, waterfall appends.
+// Integration over K folded frames is pfb_groups_api.hip; int16 I,Q input is pfb_ci16_api.hip, which runs this file's generic
+// route and argument checks with its own fold kernel.  Out of scope: double precision, waterfall appends.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -50,7 +51,12 @@ int pfb_stage_reserve(sdrk_plan* p, size_t need) {
     return SDRK_OK;
 }
 
-int fold_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+}  // namespace
+
+// The generic route of a PFB transform, for samples of in_elem bytes and the fold kernel that reads them (declared in
+// plan_internal.h: pfb_ci16_api.hip hands in its own).
+int sdrk_host::pfb_fold_route(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, size_t n_frames, size_t stride,
+                              void* d_out, int epilogue, hipStream_t stream) {
     const size_t nfft = (size_t)p->nfft;
     const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
     size_t per = PFB_STAGE_BYTES / (nfft * sizeof(float2));   // one frame is at most 2^22 samples = 32 MiB
@@ -63,8 +69,8 @@ int fold_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, v
     // N = 65536: the form is chosen for the call, not for its chunks (plan_launch's call_frames), as in the int16 route
     for (size_t f0 = 0; f0 < n_frames && st == SDRK_OK; f0 += per) {
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
-        const hipError_t e = sdrk::launch_pfb_fold(static_cast<const float2*>(d_in) + f0 * stride, stride, nf, p->nfft, p->d_pfb_h,
-                                                   p->pfb_taps, p->d_pfb_stage, p->num_cus, stream);
+        const hipError_t e = fold(static_cast<const char*>(d_in) + f0 * stride * in_elem, stride, nf, p->nfft, p->d_pfb_h, p->pfb_taps,
+                                  p->d_pfb_stage, p->num_cus, stream);
         if (e != hipSuccess) {
             st = fail(SDRK_ERR_HIP, "pfb fold launch failed: %s", hipGetErrorString(e));
             break;
@@ -80,7 +86,7 @@ int fold_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, v
 }
 
 // Which plans the PFB entry points serve: float32, rectangular window (the prototype is the window), taps set.
-int check_pfb_plan(const sdrk_plan* p) {
+int sdrk_host::check_pfb_plan(const sdrk_plan* p) {
     if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
     if (p->precision != 32) return fail(SDRK_ERR_INVALID, "the polyphase filter bank serves float32 plans only (this is a float64 plan)");
     if (p->d_window)
@@ -88,15 +94,23 @@ int check_pfb_plan(const sdrk_plan* p) {
     return SDRK_OK;
 }
 
-int check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out) {
+int sdrk_host::check_pfb_ready(const sdrk_plan* p) {
     int st = check_pfb_plan(p);
     if (st != SDRK_OK) return st;
     if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
+    return SDRK_OK;
+}
+
+int sdrk_host::check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out) {
+    int st = check_pfb_ready(p);
+    if (st != SDRK_OK) return st;
     if (n_frames == 0) return fail(SDRK_ERR_INVALID, "n_frames must be >= 1");
     if (!in || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
     if (frame_stride == 0 && n_frames > 1) return fail(SDRK_ERR_INVALID, "frame_stride must be >= 1 for more than one frame");
     return SDRK_OK;
 }
+
+namespace {
 
 // complex64 stream in, T * nfft samples per frame; float32 rows or complex64 out; always through the copy engines (every
 // sample is read T times: over PCIe it would cross T times)
@@ -118,7 +132,8 @@ HostIo pfb_io(const sdrk_plan* p, int epilogue) {
 int sdrk_host::launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
     if (n_frames == 0) return SDRK_OK;
     if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
-    if (p->nfft != 4096 || p->blu_inner) return fold_route(p, d_in, n_frames, stride, d_out, epilogue, stream);
+    if (p->nfft != 4096 || p->blu_inner)
+        return pfb_fold_route(p, d_in, sizeof(float2), sdrk::launch_pfb_fold, n_frames, stride, d_out, epilogue, stream);
     const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
     const hipError_t e = sdrk::launch_pfb4096(a, p->d_pfb_h, p->pfb_taps, p->pfb_assign);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "pfb kernel launch failed: %s", hipGetErrorString(e));

@@ -4,6 +4,7 @@
 //   y[n] = (((h[n] x[n]) + h[N+n] x[N+n]) + h[2N+n] x[2N+n]) + ...      per real component, float32, no fused multiply-add
 // the arithmetic of pfb4096.hip (kernels_pfb.h), which numpy reproduces on float32 arrays.
 #include "kernels_pfb.h"
+#include "pfb_fold_body.h"
 
 namespace sdrk {
 
@@ -11,22 +12,7 @@ namespace sdrk {
 __global__ __launch_bounds__(256) void pfb_fold_kernel(const float2* __restrict__ iq, size_t frame_stride, size_t n_frames,
                                                        int nfft, const float* __restrict__ h, int taps,
                                                        float2* __restrict__ out) {
-    const size_t tiles_per_frame = ((size_t)nfft + 255) / 256;
-    const size_t tiles = n_frames * tiles_per_frame;
-    for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const size_t f = tile / tiles_per_frame;
-        const size_t n = (tile - f * tiles_per_frame) * 256 + threadIdx.x;
-        if (n >= (size_t)nfft) continue;
-        const float2* __restrict__ x = iq + f * frame_stride + n;
-        const float* __restrict__ c = h + n;
-        const float2 x0 = x[0];
-        pfb_v2f acc = pfb_mul(pfb_v2f{x0.x, x0.y}, c[0]);
-        for (int t = 1; t < taps; ++t) {
-            const float2 xt = x[(size_t)t * nfft];
-            acc = pfb_mac(acc, pfb_v2f{xt.x, xt.y}, c[(size_t)t * nfft]);
-        }
-        out[f * (size_t)nfft + n] = make_float2(acc.x, acc.y);
-    }
+    pfb_fold_body<PfbFoldInC64>(iq, frame_stride, n_frames, nfft, h, taps, out);
 }
 
 hipError_t launch_pfb_fold(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,

@@ -33,23 +33,13 @@ IntIo pfb_groups_io(const sdrk_plan* p) {
     return io;
 }
 
-// Which plans these entry points serve: those of the PFB (float32, rectangular window, prototype set).
-int check_pfb_groups_plan(const sdrk_plan* p) {
-    if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
-    if (p->precision != 32) return fail(SDRK_ERR_INVALID, "the polyphase filter bank serves float32 plans only (this is a float64 plan)");
-    if (p->d_window)
-        return fail(SDRK_ERR_INVALID, "the polyphase filter bank needs a plan created with SDRK_WINDOW_RECT: the prototype is the window");
-    if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
-    return SDRK_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int sdrk_exec_device_pfb_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                                     int detector, int out_form, float scale, float* d_out, void* stream) {
-    int st = check_pfb_groups_plan(p);
+    int st = check_pfb_ready(p);
     if (st != SDRK_OK) return st;
     return exec_device_integrated(pfb_groups_io(p), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
                                   stream);
@@ -58,7 +48,7 @@ int sdrk_exec_device_pfb_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n
 int sdrk_exec_device_pfb_integrated_timed_each(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames,
                                                size_t frame_stride, int detector, int out_form, float scale, float* d_out,
                                                int launches, float* each_ms) {
-    int st = check_pfb_groups_plan(p);
+    int st = check_pfb_ready(p);
     if (st != SDRK_OK) return st;
     return exec_device_integrated_timed_each(pfb_groups_io(p), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form,
                                              scale, d_out, launches, each_ms);
@@ -66,7 +56,7 @@ int sdrk_exec_device_pfb_integrated_timed_each(sdrk_plan* p, const void* d_iq_c6
 
 int sdrk_exec_host_pfb_integrated(sdrk_plan* p, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                                   int detector, int out_form, float scale, float* out) {
-    int st = check_pfb_groups_plan(p);
+    int st = check_pfb_ready(p);
     if (st != SDRK_OK) return st;
     return exec_host_integrated(pfb_groups_io(p), p, iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }

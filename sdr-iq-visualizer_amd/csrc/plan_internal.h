@@ -256,5 +256,21 @@ int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, 
 // One polyphase-filter-bank transform of a float32 plan on a raw complex64 stream (taps * nfft samples per frame): a LaunchFn.
 // N = 4096 is one launch; every other length folds into d_pfb_stage and runs the plan's transform on that.
 int launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
+// Its generic route for samples of in_elem bytes: chunks of frames folded by `fold` (kernels_pfb.h's launch_pfb_fold or its
+// int16 form) into d_pfb_stage, at most 64 MiB, each followed by plan_launch; ev_pfb behind the last.
+using PfbFoldFn = hipError_t (*)(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
+                                 void* d_out, int num_cus, hipStream_t stream);
+int pfb_fold_route(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, size_t n_frames, size_t stride, void* d_out,
+                   int epilogue, hipStream_t stream);
+// What every PFB entry point refuses: float64 or windowed plans; for any transform, per frame or integrated, also a plan
+// with no prototype set (check_pfb_ready); and for a per-frame one zero frames, NULL pointers, stride 0 with more than one
+// frame (the integrated calls leave those to integrate_call.h).
+int check_pfb_plan(const sdrk_plan* p);
+int check_pfb_ready(const sdrk_plan* p);
+int check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out);
+
+// ---- pfb_ci16_api.hip ----
+// The same on interleaved int16 I,Q (4 bytes per sample): a LaunchFn.
+int launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 
 }  // namespace sdrk_host

@@ -656,6 +656,91 @@ class SpectrumPlan:
                                                                    c_float(scale), c_void_p(d_out), int(launches), ms))
         return [float(v) for v in ms]
 
+    # ... from int16 I,Q: the bits of the seven above on the widened samples, from half the input bytes
+    def pfb_db_ci16(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``pfb_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``pfb_db`` on
+        ``float32(I) + 1j*float32(Q)``; no scale is applied to the samples.  The int16 samples are read by the folding
+        kernel itself (4 bytes per sample over the link and from device memory)."""
+        x = _as_ci16(iq, stream=True)
+        self._pfb_ready()
+        hop = self.nfft if hop is None else int(hop)
+        rows = self.pfb_frames(x.shape[0], hop)
+        out = self._out_array(out, (rows, self.nfft), np.float32)
+        if rows:
+            self._run_host(lib().sdrk_exec_host_pfb_ci16, x, rows, hop, out)
+        return out
+
+    def pfb_fft_ci16(self, iq, hop: Optional[int] = None) -> np.ndarray:
+        """``pfb_fft`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
+        x = _as_ci16(iq, stream=True)
+        self._pfb_ready()
+        hop = self.nfft if hop is None else int(hop)
+        rows = self.pfb_frames(x.shape[0], hop)
+        out = np.empty((rows, self.nfft), dtype=np.complex64)
+        if rows:
+            self._run_host(lib().sdrk_exec_fft_host_pfb_ci16, x, rows, hop, out)
+        return out
+
+    def exec_device_pfb_ci16(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
+                             stream: int = 0) -> None:
+        """Device pointers: the raw int16 I,Q stream in (``(n_frames-1)*frame_stride + taps*nfft`` samples of 4 bytes, frame
+        starts 4-byte aligned) / float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        self._pfb_ready()
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_ci16(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                                  c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def exec_device_pfb_ci16_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
+                                        frame_stride: Optional[int] = None) -> list:
+        """``exec_device_pfb_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        self._pfb_ready()
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
+                                                             c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
+    def pfb_integrate_ci16(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                           scale: float = 1.0) -> np.ndarray:
+        """``pfb_integrate`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``pfb_integrate`` on
+        ``float32(I) + 1j*float32(Q)``.  At nfft = 4096 the int16 samples are read inside the folding, reducing transform."""
+        x = _as_ci16(iq, stream=True)
+        _, det, form = self._pfb_int_ready(detector, out)
+        hop = self.nfft if hop is None else int(hop)
+        groups = self.pfb_integrated_groups(x.shape[0], k, hop)
+        res = np.empty((groups, self.nfft), dtype=np.float32)
+        if groups:
+            with self._lock:
+                check(lib().sdrk_exec_host_pfb_integrated_ci16(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
+                                                               c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
+                                                               res.ctypes.data_as(c_void_p)))
+        return res
+
+    def exec_device_pfb_integrated_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
+                                        frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                        scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: the raw int16 I,Q stream in (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples of 4 bytes),
+        ``n_groups`` float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_integrated_ci16(self.handle, c_void_p(d_iq), c_size_t(n_groups),
+                                                             c_size_t(int(k)), c_size_t(stride), det, form, c_float(scale),
+                                                             c_void_p(d_out), c_void_p(stream) if stream else None))
+
+    def exec_device_pfb_integrated_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                                   frame_stride: Optional[int] = None, detector: str = "mean",
+                                                   out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_pfb_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_pfb_integrated_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
+                                                                        c_size_t(int(k)), c_size_t(stride), det, form,
+                                                                        c_float(scale), c_void_p(d_out), int(launches), ms))
+        return [float(v) for v in ms]
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -996,6 +1081,27 @@ def pfb_integrated_db(iq, nfft: int, taps: int, k: int, hop: Optional[int] = Non
         raise ValueError("hop must be >= 1")
     SpectrumPlan._int_codes(detector, "db")
     return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_integrate(iq, k, hop, detector, "db")
+
+
+def pfb_db_ci16(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12,
+                shift: bool = True, device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``pfb_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on
+    ``float32(I) + 1j*float32(Q)``, from half the input bytes; prototype and plan cache as for ``pfb_db``."""
+    x = _as_ci16(iq, stream=True)
+    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_db_ci16(x, hop, out=out)
+
+
+def pfb_integrated_db_ci16(iq, nfft: int, taps: int, k: int, hop: Optional[int] = None, detector: str = "mean",
+                           prototype=None, *, eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """``pfb_integrated_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on the
+    widened samples, from half the input bytes."""
+    x = _as_ci16(iq, stream=True)
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    if hop is not None and int(hop) < 1:
+        raise ValueError("hop must be >= 1")
+    SpectrumPlan._int_codes(detector, "db")
+    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_integrate_ci16(x, k, hop, detector, "db")
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

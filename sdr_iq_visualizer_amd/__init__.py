@@ -25,7 +25,9 @@ from .spectrum import (  # noqa: E402
     integrated_db,
     integrated_db_ci16,
     pfb_db,
+    pfb_db_ci16,
     pfb_integrated_db,
+    pfb_integrated_db_ci16,
     pfb_prototype,
     process_frame,
     spectrum_db,
@@ -55,7 +57,9 @@ __all__ = [
     "is_pinned",
     "library_path",
     "pfb_db",
+    "pfb_db_ci16",
     "pfb_integrated_db",
+    "pfb_integrated_db_ci16",
     "pfb_prototype",
     "pinned_empty",
     "process_frame",
