@@ -6,7 +6,7 @@
 // data.  Every other length (N < 256, the two-pass lengths 2^15 ... 2^22 with the persistent N = 65536 form, chirp-z) runs
 // "widen a chunk of frames into plan-owned complex64 staging, then plan_launch" on the same stream, the staging capped at
 // 64 MiB however many frames the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with 4-byte samples.
-// Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
+// The integrated int16 entries are integrate_api.hip.  Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
@@ -23,21 +23,6 @@ namespace {
 constexpr size_t CI16_STAGE_BYTES = (size_t)64 << 20;   // complex64 staging of the unpack route, per plan
 constexpr size_t CI16_ELEM = 4;                          // bytes per int16 I,Q sample
 
-// The staging only grows, and never under work that still reads it: whatever was enqueued on it last is waited for first.
-int stage_reserve(sdrk_plan* p, size_t need) {
-    if (!p->ev_ci16) HIP_TRY(hipEventCreateWithFlags(&p->ev_ci16, hipEventDisableTiming));
-    if (need <= p->ci16_cap) return SDRK_OK;
-    if (p->ci16_busy) HIP_TRY(hipEventSynchronize(p->ev_ci16));
-    if (p->d_ci16) {
-        HIP_TRY(hipFree(p->d_ci16));
-        p->d_ci16 = nullptr;
-        p->ci16_cap = 0;
-    }
-    HIP_TRY(hipMalloc(&p->d_ci16, need));
-    p->ci16_cap = need;
-    return SDRK_OK;
-}
-
 int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
     const size_t nfft = (size_t)p->nfft;
     const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
@@ -50,10 +35,11 @@ int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride,
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
     const size_t st_stride = overlapped ? stride : nfft;
-    int st = stage_reserve(p, ((per - 1) * st_stride + nfft) * sizeof(float2));
+    sdrk_host::Staging& sg = p->ci16;   // one staging per plan: a call on another stream waits for the last one's reads
+    int st = sg.reserve(0, ((per - 1) * st_stride + nfft) * sizeof(float2));
+    if (st == SDRK_OK) st = sg.enter(stream);
     if (st != SDRK_OK) return st;
-    // one staging per plan: a call on another stream waits for the last one's reads
-    if (p->ci16_busy && p->ci16_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, p->ev_ci16, 0));
+    void* const d_stage = sg.buf[0].d;
     // N = 65536: the form is chosen for the call, not for its chunks (plan_launch's call_frames) — 128-frame chunks would never
     // reach the persistent kernel's threshold.  Two consequences: a short last chunk (513 frames: 128 x 4 + 1) runs the persistent
     // kernel too, and fused_check's mailbox holds the last 64 launches, so of a call of more than 64 chunks (8192 frames) only
@@ -63,27 +49,23 @@ int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride,
         const char* src = static_cast<const char*>(d_in) + f0 * stride * CI16_ELEM;
         hipError_t e;
         if (overlapped || stride == nfft)
-            e = sdrk::launch_unpack_ci16(src, 0, p->d_ci16, 1, (nf - 1) * st_stride + nfft, p->num_cus, stream);
+            e = sdrk::launch_unpack_ci16(src, 0, d_stage, 1, (nf - 1) * st_stride + nfft, p->num_cus, stream);
         else
-            e = sdrk::launch_unpack_ci16(src, stride, p->d_ci16, nf, nfft, p->num_cus, stream);
+            e = sdrk::launch_unpack_ci16(src, stride, d_stage, nf, nfft, p->num_cus, stream);
         if (e != hipSuccess) {
             st = fail(SDRK_ERR_HIP, "ci16 unpack launch failed: %s", hipGetErrorString(e));
             break;
         }
-        st = plan_launch(p, p->d_ci16, nf, st_stride, static_cast<char*>(d_out) + f0 * nfft * out_elem, epilogue, stream,
+        st = plan_launch(p, d_stage, nf, st_stride, static_cast<char*>(d_out) + f0 * nfft * out_elem, epilogue, stream,
                          nullptr, nullptr, nullptr, n_frames);
     }
-    const hipError_t e = hipEventRecord(p->ev_ci16, stream);   // (also after a failed launch: earlier chunks are in flight)
-    p->ci16_stream = stream;
-    p->ci16_busy = true;
-    if (st == SDRK_OK && e != hipSuccess) st = fail(SDRK_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
-    return st;
+    return sg.leave(stream, st);   // (also after a failed launch: earlier chunks are in flight)
 }
 
 }  // namespace
 
 // One transform of a float32 plan on int16 input: the ci16 form of plan_launch, the LaunchFn of the ci16 numpy boundary
-// and the transform of the int16 integrated calls (kgroup_ci16_api.hip); declared in plan_internal.h.
+// and the transform of the int16 integrated calls (integrate_api.hip); declared in plan_internal.h.
 int sdrk_host::launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
     if (p->precision != 32) return fail(SDRK_ERR_INVALID, "ci16 transform requested of a float64 plan");
     if (n_frames == 0) return SDRK_OK;
@@ -101,14 +83,9 @@ namespace {
 // int16 pairs in; float32 rows or complex64 out.  The kernel reads and writes pinned host memory itself only at the lengths
 // whose transform reads int16 (the unpack route would cross PCIe for its staging's sake).
 HostIo ci16_io(int epilogue) {
-    HostIo io;
-    io.in_elem = CI16_ELEM;
-    io.out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
-    io.epilogue = epilogue;
-    io.precision = 32;
+    HostIo io = frames_io(CI16_ELEM, 0, launch_ci16, epilogue);
     io.zero_copy_min_nfft = 256;
     io.zero_copy_max_nfft = 16384;
-    io.launch = launch_ci16;
     return io;
 }
 
@@ -126,21 +103,13 @@ int sdrk_exec_fft_host_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_frames, 
 
 int sdrk_exec_device_ci16(sdrk_plan* p, const void* d_iq_ci16, size_t n_frames, size_t frame_stride, float* d_out_db,
                           void* stream) {
-    int st = check_exec_args(p, d_iq_ci16, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK || n_frames == 0) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    return launch_ci16(p, d_iq_ci16, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD,
-                       stream ? static_cast<hipStream_t>(stream) : p->stream);
+    return exec_device_frames(check_exec_f32, launch_ci16, p, d_iq_ci16, n_frames, frame_stride, d_out_db, stream);
 }
 
 int sdrk_exec_device_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t n_frames, size_t frame_stride,
                                      float* d_out_db, int launches, float* each_ms) {
-    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
-    int st = check_exec_args(p, d_iq_ci16, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK) return st;
-    st = timed_each(p, launches, each_ms,
-                    [&] { return launch_ci16(p, d_iq_ci16, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
-    return st == SDRK_OK ? fused_check(p) : st;
+    return exec_device_frames_timed_each(check_exec_f32, launch_ci16, p, d_iq_ci16, n_frames, frame_stride, d_out_db, launches,
+                                         each_ms);
 }
 
 int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,

@@ -1,35 +1,47 @@
-// integrate_api.hip — the complex64 integrated-spectrum entry points of include/sdrk.h (sdrk_exec_*_integrated): per group of
-// K consecutive frames ONE row — the mean, maximum or minimum over the frames of |fft(w x_f)|^2 per bin — as dB or as scaled
-// linear power.  Video averaging / Welch, peak hold and noise-floor hold inside the transform.
+// integrate_api.hip — the integrated-spectrum entry points of include/sdrk.h (sdrk_exec_*_integrated, _integrated_ci16,
+// _pfb_integrated, _pfb_integrated_ci16): per group of K consecutive frames ONE row — the mean, maximum or minimum over the
+// frames of |fft(w x_f)|^2 per bin — as dB or as scaled linear power.  Video averaging / Welch, peak hold and noise-floor hold
+// inside the transform.  The samples are complex64 or interleaved little-endian int16 I,Q (4 bytes per sample; x[n] =
+// float32(I[n]) + i float32(Q[n]) exactly, then the bits of the complex64 call); the frames are cut from the stream as they
+// are, or folded from T blocks under the plan's prototype first (the spectrometer form of the polyphase filter bank: bit for
+// bit the integrated call on the packed folded frames).
 //
-// The call itself — the N = 4096 kernel on the caller's samples, every other length through the plan's own transform and at
+// The call itself — the N = 4096 kernel on the caller's samples, every other length through the mode's own transform and at
 // most 64 MiB of staging, carry rows across chunks, slices and their finalize, the numpy boundary through the three staging
-// slots — is integrate_call.h, shared with the int16 form (kgroup_ci16_api.hip).  This file gives it the complex64 launchers:
-// fft4096_integrate.hip and plan_launch.
-// Host code only (not named sdrk_*.hip: tests/host_sources.py globs those for the stand-in kernel builds).
+// slots — is integrate_call.h.  This file gives it one IntIo per mode: the N = 4096 kernel that reduces inside the transform
+// (fft4096_integrate.hip, fft4096_kgroup_ci16.hip, pfb4096_groups.hip, pfb4096_i16_groups.hip) and the per-frame transform of
+// the other lengths (plan_launch, ci16_api.hip's launch_ci16, pfb_api.hip's launch_pfb / launch_pfb_ci16, which keep their own
+// stagings and orderings).  The PFB entries refuse a plan without a prototype first (check_pfb_ready).
+// Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
 
 #include "integrate_call.h"
 #include "kernels_integrate.h"
+#include "kernels_kgroup_ci16.h"
+#include "kernels_pfb.h"
 #include "plan_internal.h"
 
 using namespace sdrk_host;
 
 namespace {
 
-int transform_c64(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
-    return plan_launch(p, d_in, n_frames, stride, d_out, epilogue, stream);
-}
+using FusedFn = hipError_t (*)(const sdrk::IntegrateArgs&);
 
-IntIo c64_io() {
+IntIo int_io(size_t in_elem, FusedFn fused, LaunchFn transform, const sdrk_plan* pfb_plan = nullptr) {
     IntIo io;
-    io.in_elem = sizeof(float2);
-    io.fused = sdrk::launch_fft4096_integrate;
-    io.transform = transform_c64;
+    io.in_elem = in_elem;
+    io.fused = fused;
+    io.transform = transform;
+    if (pfb_plan) io.in_span = (size_t)pfb_plan->pfb_taps * (size_t)pfb_plan->nfft;
     return io;
 }
+
+IntIo c64_io() { return int_io(sizeof(float2), sdrk::launch_fft4096_integrate, launch_f32); }
+IntIo ci16_io() { return int_io(4, sdrk::launch_fft4096_kgroup_ci16, launch_ci16); }
+IntIo pfb_io(const sdrk_plan* p) { return int_io(sizeof(float2), sdrk::launch_pfb4096_groups, launch_pfb, p); }
+IntIo pfb_ci16_io(const sdrk_plan* p) { return int_io(4, sdrk::launch_pfb4096_i16_groups, launch_pfb_ci16, p); }
 
 }  // namespace
 
@@ -37,20 +49,76 @@ extern "C" {
 
 int sdrk_exec_device_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                                 int detector, int out_form, float scale, float* d_out, void* stream) {
-    return exec_device_integrated(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
-                                  stream);
+    return exec_device_integrated(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, stream);
 }
 
 int sdrk_exec_device_integrated_timed_each(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames,
                                            size_t frame_stride, int detector, int out_form, float scale, float* d_out,
                                            int launches, float* each_ms) {
-    return exec_device_integrated_timed_each(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale,
-                                             d_out, launches, each_ms);
+    return exec_device_integrated_timed_each(c64_io(), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                             launches, each_ms);
 }
 
 int sdrk_exec_host_integrated(sdrk_plan* p, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                               int detector, int out_form, float scale, float* out) {
     return exec_host_integrated(c64_io(), p, iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
+}
+
+int sdrk_exec_device_integrated_ci16(sdrk_plan* p, const void* d_iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                     int detector, int out_form, float scale, float* d_out, void* stream) {
+    return exec_device_integrated(ci16_io(), p, d_iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, stream);
+}
+
+int sdrk_exec_device_integrated_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                                size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                int launches, float* each_ms) {
+    return exec_device_integrated_timed_each(ci16_io(), p, d_iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                             launches, each_ms);
+}
+
+int sdrk_exec_host_integrated_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                   int detector, int out_form, float scale, float* out) {
+    return exec_host_integrated(ci16_io(), p, iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
+}
+
+int sdrk_exec_device_pfb_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                    int detector, int out_form, float scale, float* d_out, void* stream) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_device_integrated(pfb_io(p), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, stream);
+}
+
+int sdrk_exec_device_pfb_integrated_timed_each(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames,
+                                               size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                               int launches, float* each_ms) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_device_integrated_timed_each(pfb_io(p), p, d_iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                             launches, each_ms);
+}
+
+int sdrk_exec_host_pfb_integrated(sdrk_plan* p, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                  int detector, int out_form, float scale, float* out) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_host_integrated(pfb_io(p), p, iq_c64, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
+}
+
+int sdrk_exec_device_pfb_integrated_ci16(sdrk_plan* p, const void* d_iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                         int detector, int out_form, float scale, float* d_out, void* stream) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_device_integrated(pfb_ci16_io(p), p, d_iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, stream);
+}
+
+int sdrk_exec_device_pfb_integrated_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                                    size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                    int launches, float* each_ms) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_device_integrated_timed_each(pfb_ci16_io(p), p, d_iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                             launches, each_ms);
+}
+
+int sdrk_exec_host_pfb_integrated_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                       int detector, int out_form, float scale, float* out) {
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
+    return exec_host_integrated(pfb_ci16_io(p), p, iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }
 
 }  // extern "C"

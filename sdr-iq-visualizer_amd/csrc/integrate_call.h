@@ -1,9 +1,7 @@
-// integrate_call.h — the machinery of an integrated-spectrum call (one row per K frames), shared by the host files of its
-// input formats: integrate_api.hip (complex64 samples), kgroup_ci16_api.hip (int16 I,Q) and pfb_groups_api.hip (complex64
-// samples folded by the plan's polyphase filter bank).  An IntIo says what differs
-// between them, the way HostIo (plan_internal.h) does for exec_host: the bytes per input sample, the launcher of the N = 4096
-// kernel that reduces inside the transform, and the plan's own transform for every other length.  Each host file defines its
-// launchers and hands its IntIo in, so neither refers to a kernel the other's stand-ins (tests/fake_*) do not define.
+// integrate_call.h — the machinery of an integrated-spectrum call (one row per K frames), shared by the four modes of
+// integrate_api.hip: complex64 or int16 I,Q samples, plain frames or frames folded by the plan's polyphase filter bank.  An
+// IntIo says what differs between them, the way HostIo (plan_internal.h) does for exec_host: the bytes per input sample, the
+// launcher of the N = 4096 kernel that reduces inside the transform, and the plan's own transform for every other length.
 //
 // N = 4096 runs the fused kernel on the caller's samples: one launch, plus a finalize when the groups are too few to fill the
 // device and were cut into slices (integrate_split.h).  Every other length (chirp-z included) runs "the plan's own transform
@@ -26,7 +24,7 @@ struct IntIo {
     hipError_t (*fused)(const sdrk::IntegrateArgs&) = nullptr;     // N = 4096: the reduction inside the transform
     LaunchFn transform = nullptr;                                  // every other length: the plan's transform (EPI_COMPLEX)
     size_t in_span = 0;                                            // input samples a frame reads from its start (0: nfft;
-                                                                   // pfb_groups_api.hip: taps * nfft)
+                                                                   // the filter bank: taps * nfft)
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -62,23 +60,6 @@ inline int check_int_args(const sdrk_plan* p, const void* in, size_t n_groups, s
     return SDRK_OK;
 }
 
-// Plan-owned buffers only grow, and never under work that still uses them.
-inline int int_reserve(sdrk_plan* p, void** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return SDRK_OK;
-    if (p->int_busy) {
-        HIP_TRY(hipEventSynchronize(p->ev_int));
-        p->int_busy = false;
-    }
-    if (*buf) {
-        HIP_TRY(hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-    }
-    HIP_TRY(hipMalloc(buf, need));
-    *cap = need;
-    return SDRK_OK;
-}
-
 inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups, size_t k, size_t stride, int detector,
                       int out_form, float scale, hipStream_t stream) {
     c.p = p;
@@ -95,23 +76,21 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
     // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel
     const size_t ways = c.fused ? 1 : (nfft + 255) / 256;
     c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
-    if (!p->ev_int) HIP_TRY(hipEventCreateWithFlags(&p->ev_int, hipEventDisableTiming));
     const size_t row = nfft * sizeof(float2);
     const size_t n_partials = c.sp.slices > 1 ? n_groups * c.sp.slices : 0;
-    int st = int_reserve(p, &p->d_int_state, &p->int_state_cap, (2 + n_partials) * row);
+    Staging& sg = p->integ;   // buf[0]: carry and partial rows; buf[1]: spectra of the generic route
+    int st = sg.reserve(0, (2 + n_partials) * row);
     if (st != SDRK_OK) return st;
     if (!c.fused) {
         c.stage_frames = INT_STAGE_BYTES / row ? INT_STAGE_BYTES / row : 1;
         if (c.stage_frames > n_groups * k) c.stage_frames = n_groups * k;
-        st = int_reserve(p, &p->d_int_stage, &p->int_stage_cap, c.stage_frames * row);
+        st = sg.reserve(1, c.stage_frames * row);
         if (st != SDRK_OK) return st;
     }
-    c.carry[0] = static_cast<float2*>(p->d_int_state);
+    c.carry[0] = static_cast<float2*>(sg.buf[0].d);
     c.carry[1] = c.carry[0] + nfft;
     c.partials = c.carry[1] + nfft;
-    // one state and one staging per plan: a call on another stream waits for the last one's work
-    if (p->int_busy && p->int_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, p->ev_int, 0));
-    return SDRK_OK;
+    return sg.enter(stream);   // one state and one staging per plan: a call on another stream waits for the last one's work
 }
 
 // The frames [f0, f1) of the call, d_in at frame f0's first sample.  Rows of the groups that end in the range go to
@@ -152,9 +131,10 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
             a.in_stride = c.stride;
             e = c.io.fused(a);
         } else {
-            int st = c.io.transform(p, src, s1 - s0, c.stride, p->d_int_stage, sdrk::EPI_COMPLEX, c.stream);
+            void* const d_stage = p->integ.buf[1].d;
+            int st = c.io.transform(p, src, s1 - s0, c.stride, d_stage, sdrk::EPI_COMPLEX, c.stream);
             if (st != SDRK_OK) return st;
-            a.d_in = p->d_int_stage;
+            a.d_in = d_stage;
             a.in_stride = (size_t)p->nfft;
             e = sdrk::launch_integrate_rows(a);
         }
@@ -173,11 +153,7 @@ inline int call_finalize(IntCall& c, float* d_out) {
 }
 
 inline int call_end(IntCall& c, int st) {   // (also after a failed launch: earlier launches are in flight)
-    const hipError_t e = hipEventRecord(c.p->ev_int, c.stream);
-    c.p->int_stream = c.stream;
-    c.p->int_busy = true;
-    if (st == SDRK_OK && e != hipSuccess) st = fail(SDRK_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
-    return st;
+    return c.p->integ.leave(c.stream, st);
 }
 
 inline int device_call(const IntIo& io, sdrk_plan* p, const void* d_iq, size_t n_groups, size_t k, size_t stride, int detector,
@@ -291,7 +267,7 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     st = call_end(c, SDRK_OK);
     if (st != SDRK_OK) return st;
     HIP_TRY(hipStreamSynchronize(p->stream));
-    p->int_busy = false;
+    p->integ.busy = false;
     return fused_check(p);
 }
 

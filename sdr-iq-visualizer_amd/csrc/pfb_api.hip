@@ -1,15 +1,17 @@
-// pfb_api.hip — host side of the polyphase-filter-bank entry points of include/sdrk.h (sdrk_plan_set_pfb, sdrk_plan_pfb_taps,
-// sdrk_exec_*_pfb): a prototype filter of T * nfft coefficients folds T consecutive blocks of a stream into each frame in front
-// of the plan's transform (kernels_pfb.h has the exact arithmetic).  Sits in front of app/sdr/streamer.py:119-121; the reference
-// has no counterpart.
+// pfb_api.hip — host side of the per-frame polyphase-filter-bank entry points of include/sdrk.h (sdrk_plan_set_pfb,
+// sdrk_plan_pfb_taps, sdrk_exec_*_pfb, sdrk_exec_*_pfb_ci16): a prototype filter of T * nfft coefficients folds T consecutive
+// blocks of a stream into each frame in front of the plan's transform (kernels_pfb.h has the exact arithmetic).  The stream is
+// complex64, or interleaved little-endian int16 I,Q at 4 bytes per sample: x[n] = float32(I[n]) + i float32(Q[n]) exactly, then
+// the bits of the complex64 call.  Sits in front of app/sdr/streamer.py:119-121; the reference has no counterpart.
 //
-// N = 4096 is one launch on the caller's stream (pfb4096.hip: the fold in the transform's registers).  Every other length
-// (single-pass, two-pass with the persistent N = 65536 form, chirp-z) runs "fold a chunk of frames into plan-owned complex64
-// staging, then plan_launch" on the same stream, the staging capped at 64 MiB and cut at frame boundaries however many frames
-// the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame:
-// a chunk carries its (T - 1) * nfft samples of overlap.
-// Integration over K folded frames is pfb_groups_api.hip; int16 I,Q input is pfb_ci16_api.hip, which runs this file's generic
-// route and argument checks with its own fold kernel.  Out of scope: double precision, waterfall appends.
+// N = 4096 is one launch on the caller's stream (pfb4096.hip, pfb4096_i16.hip: the fold in the transform's registers).  Every
+// other length (single-pass, two-pass with the persistent N = 65536 form, chirp-z) runs "fold a chunk of frames into plan-owned
+// complex64 staging (pfb_fold.hip, pfb_fold_i16.hip: no widened copy of an int16 stream), then plan_launch" on the same stream,
+// the staging capped at 64 MiB and cut at frame boundaries however many frames the call has.  The numpy boundary is
+// sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame: a chunk carries its (T - 1) * nfft
+// samples of overlap.
+// Integration over K folded frames is integrate_api.hip, with this file's launchers and checks.  Out of scope: double
+// precision, waterfall appends.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -36,54 +38,7 @@ int pfb_assign_default() {
     return sdrk::PFB_ASSIGN_XCD;
 }
 
-// The staging only grows, and never under work that still reads it: whatever was enqueued on it last is waited for first.
-int pfb_stage_reserve(sdrk_plan* p, size_t need) {
-    if (!p->ev_pfb) HIP_TRY(hipEventCreateWithFlags(&p->ev_pfb, hipEventDisableTiming));
-    if (need <= p->pfb_stage_cap) return SDRK_OK;
-    if (p->pfb_busy) HIP_TRY(hipEventSynchronize(p->ev_pfb));
-    if (p->d_pfb_stage) {
-        HIP_TRY(hipFree(p->d_pfb_stage));
-        p->d_pfb_stage = nullptr;
-        p->pfb_stage_cap = 0;
-    }
-    HIP_TRY(hipMalloc(&p->d_pfb_stage, need));
-    p->pfb_stage_cap = need;
-    return SDRK_OK;
-}
-
 }  // namespace
-
-// The generic route of a PFB transform, for samples of in_elem bytes and the fold kernel that reads them (declared in
-// plan_internal.h: pfb_ci16_api.hip hands in its own).
-int sdrk_host::pfb_fold_route(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, size_t n_frames, size_t stride,
-                              void* d_out, int epilogue, hipStream_t stream) {
-    const size_t nfft = (size_t)p->nfft;
-    const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
-    size_t per = PFB_STAGE_BYTES / (nfft * sizeof(float2));   // one frame is at most 2^22 samples = 32 MiB
-    if (per < 1) per = 1;
-    if (per > n_frames) per = n_frames;
-    int st = pfb_stage_reserve(p, per * nfft * sizeof(float2));
-    if (st != SDRK_OK) return st;
-    // one staging per plan: a call on another stream waits for the last one's reads
-    if (p->pfb_busy && p->pfb_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, p->ev_pfb, 0));
-    // N = 65536: the form is chosen for the call, not for its chunks (plan_launch's call_frames), as in the int16 route
-    for (size_t f0 = 0; f0 < n_frames && st == SDRK_OK; f0 += per) {
-        const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
-        const hipError_t e = fold(static_cast<const char*>(d_in) + f0 * stride * in_elem, stride, nf, p->nfft, p->d_pfb_h, p->pfb_taps,
-                                  p->d_pfb_stage, p->num_cus, stream);
-        if (e != hipSuccess) {
-            st = fail(SDRK_ERR_HIP, "pfb fold launch failed: %s", hipGetErrorString(e));
-            break;
-        }
-        st = plan_launch(p, p->d_pfb_stage, nf, nfft, static_cast<char*>(d_out) + f0 * nfft * out_elem, epilogue, stream,
-                         nullptr, nullptr, nullptr, n_frames);
-    }
-    const hipError_t e = hipEventRecord(p->ev_pfb, stream);   // (also after a failed launch: earlier chunks are in flight)
-    p->pfb_stream = stream;
-    p->pfb_busy = true;
-    if (st == SDRK_OK && e != hipSuccess) st = fail(SDRK_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
-    return st;
-}
 
 // Which plans the PFB entry points serve: float32, rectangular window (the prototype is the window), taps set.
 int sdrk_host::check_pfb_plan(const sdrk_plan* p) {
@@ -112,32 +67,72 @@ int sdrk_host::check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frame
 
 namespace {
 
-// complex64 stream in, T * nfft samples per frame; float32 rows or complex64 out; always through the copy engines (every
-// sample is read T times: over PCIe it would cross T times)
-HostIo pfb_io(const sdrk_plan* p, int epilogue) {
-    HostIo io;
-    io.in_elem = sizeof(float2);
-    io.out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
-    io.epilogue = epilogue;
-    io.precision = 32;
-    io.in_span = (size_t)p->pfb_taps * (size_t)p->nfft;
-    io.launch = launch_pfb;
-    return io;
+// The generic route of a PFB transform, for samples of in_elem bytes and the fold kernel that reads them (kernels_pfb.h's
+// launch_pfb_fold or its int16 form).
+using PfbFoldFn = hipError_t (*)(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
+                                 void* d_out, int num_cus, hipStream_t stream);
+int pfb_fold_route(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, size_t n_frames, size_t stride, void* d_out,
+                   int epilogue, hipStream_t stream) {
+    const size_t nfft = (size_t)p->nfft;
+    const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+    size_t per = PFB_STAGE_BYTES / (nfft * sizeof(float2));   // one frame is at most 2^22 samples = 32 MiB
+    if (per < 1) per = 1;
+    if (per > n_frames) per = n_frames;
+    sdrk_host::Staging& sg = p->pfb;   // one staging per plan: a call on another stream waits for the last one's reads
+    int st = sg.reserve(0, per * nfft * sizeof(float2));
+    if (st == SDRK_OK) st = sg.enter(stream);
+    if (st != SDRK_OK) return st;
+    void* const d_stage = sg.buf[0].d;
+    // N = 65536: the form is chosen for the call, not for its chunks (plan_launch's call_frames), as in the int16 route
+    for (size_t f0 = 0; f0 < n_frames && st == SDRK_OK; f0 += per) {
+        const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
+        const hipError_t e = fold(static_cast<const char*>(d_in) + f0 * stride * in_elem, stride, nf, p->nfft, p->d_pfb_h, p->pfb_taps,
+                                  d_stage, p->num_cus, stream);
+        if (e != hipSuccess) {
+            st = fail(SDRK_ERR_HIP, "pfb fold launch failed: %s", hipGetErrorString(e));
+            break;
+        }
+        st = plan_launch(p, d_stage, nf, nfft, static_cast<char*>(d_out) + f0 * nfft * out_elem, epilogue, stream,
+                         nullptr, nullptr, nullptr, n_frames);
+    }
+    return sg.leave(stream, st);   // (also after a failed launch: earlier chunks are in flight)
+}
+
+// One PFB transform of the plan on a raw stream of in_elem-byte samples: the folding N = 4096 kernel `flagship`, else the
+// generic route with `fold`.
+template <class Flagship>
+int launch_pfb_any(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, Flagship flagship, size_t n_frames, size_t stride,
+                   void* d_out, int epilogue, hipStream_t stream) {
+    if (n_frames == 0) return SDRK_OK;
+    if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
+    if (p->nfft != 4096 || p->blu_inner) return pfb_fold_route(p, d_in, in_elem, fold, n_frames, stride, d_out, epilogue, stream);
+    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
+    const hipError_t e = flagship(a, p->d_pfb_h, p->pfb_taps, p->pfb_assign);
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "pfb kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
+// The numpy boundary of a PFB mode: T * nfft samples of in_elem bytes per frame in; float32 rows or complex64 out; always
+// through the copy engines (every sample is read T times: over PCIe it would cross T times)
+int exec_host_pfb(size_t in_elem, LaunchFn launch, int epilogue, sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride,
+                  void* out) {
+    int st = check_pfb_exec(p, iq, n_frames, frame_stride, out);
+    if (st != SDRK_OK) return st;
+    const size_t span = (size_t)p->pfb_taps * (size_t)p->nfft;
+    return exec_host(p, iq, n_frames, frame_stride, out, frames_io(in_elem, span, launch, epilogue));
 }
 
 }  // namespace
 
-// One PFB transform of the plan on a raw complex64 stream: a LaunchFn (the transform of the numpy boundary and of
-// pfb_groups_api.hip's generic route too; declared in plan_internal.h).
+// The LaunchFns of the two PFB modes (the transforms of the numpy boundary and of integrate_api.hip's generic route too;
+// declared in plan_internal.h).
 int sdrk_host::launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
-    if (n_frames == 0) return SDRK_OK;
-    if (p->pfb_taps < 1 || !p->d_pfb_h) return fail(SDRK_ERR_INVALID, "no prototype filter set: call sdrk_plan_set_pfb first");
-    if (p->nfft != 4096 || p->blu_inner)
-        return pfb_fold_route(p, d_in, sizeof(float2), sdrk::launch_pfb_fold, n_frames, stride, d_out, epilogue, stream);
-    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
-    const hipError_t e = sdrk::launch_pfb4096(a, p->d_pfb_h, p->pfb_taps, p->pfb_assign);
-    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "pfb kernel launch failed: %s", hipGetErrorString(e));
-    return SDRK_OK;
+    return launch_pfb_any(p, d_in, sizeof(float2), sdrk::launch_pfb_fold, sdrk::launch_pfb4096, n_frames, stride, d_out, epilogue, stream);
+}
+
+int sdrk_host::launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue,
+                               hipStream_t stream) {
+    return launch_pfb_any(p, d_in, 4, sdrk::launch_pfb_fold_i16, sdrk::launch_pfb4096_i16, n_frames, stride, d_out, epilogue, stream);
 }
 
 extern "C" {
@@ -150,8 +145,9 @@ int sdrk_plan_set_pfb(sdrk_plan* p, int taps, const float* h) {
     HIP_TRY(hipSetDevice(p->device));
     // not with work in flight, says the header; make it safe all the same for work on the plan's own stream and staging
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->pfb_busy) HIP_TRY(hipEventSynchronize(p->ev_pfb));
-    if (p->int_busy) HIP_TRY(hipEventSynchronize(p->ev_int));   // sdrk_exec_*_pfb_integrated reads the prototype too
+    st = p->pfb.wait();
+    if (st == SDRK_OK) st = p->integ.wait();   // sdrk_exec_*_pfb_integrated reads the prototype too
+    if (st != SDRK_OK) return st;
     const size_t bytes = (size_t)taps * (size_t)p->nfft * sizeof(float);
     p->pfb_taps = 0;
     if (p->d_pfb_h) {
@@ -168,33 +164,39 @@ int sdrk_plan_set_pfb(sdrk_plan* p, int taps, const float* h) {
 int sdrk_plan_pfb_taps(const sdrk_plan* p) { return p ? p->pfb_taps : fail(SDRK_ERR_INVALID, "plan is NULL"); }
 
 int sdrk_exec_device_pfb(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, float* d_out_db, void* stream) {
-    int st = check_pfb_exec(p, d_iq, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    return launch_pfb(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD,
-                      stream ? static_cast<hipStream_t>(stream) : p->stream);
+    return exec_device_frames(check_pfb_exec, launch_pfb, p, d_iq, n_frames, frame_stride, d_out_db, stream);
 }
 
 int sdrk_exec_device_pfb_timed_each(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride, float* d_out_db,
                                     int launches, float* each_ms) {
-    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
-    int st = check_pfb_exec(p, d_iq, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK) return st;
-    st = timed_each(p, launches, each_ms,
-                    [&] { return launch_pfb(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
-    return st == SDRK_OK ? fused_check(p) : st;
+    return exec_device_frames_timed_each(check_pfb_exec, launch_pfb, p, d_iq, n_frames, frame_stride, d_out_db, launches, each_ms);
 }
 
 int sdrk_exec_host_pfb(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, float* out_db) {
-    int st = check_pfb_exec(p, iq, n_frames, frame_stride, out_db);
-    if (st != SDRK_OK) return st;
-    return exec_host(p, iq, n_frames, frame_stride, out_db, pfb_io(p, sdrk::EPI_LOGPSD));
+    return exec_host_pfb(sizeof(float2), launch_pfb, sdrk::EPI_LOGPSD, p, iq, n_frames, frame_stride, out_db);
 }
 
 int sdrk_exec_fft_host_pfb(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out_c64) {
-    int st = check_pfb_exec(p, iq, n_frames, frame_stride, out_c64);
-    if (st != SDRK_OK) return st;
-    return exec_host(p, iq, n_frames, frame_stride, out_c64, pfb_io(p, sdrk::EPI_COMPLEX));
+    return exec_host_pfb(sizeof(float2), launch_pfb, sdrk::EPI_COMPLEX, p, iq, n_frames, frame_stride, out_c64);
+}
+
+int sdrk_exec_device_pfb_ci16(sdrk_plan* p, const void* d_iq_ci16, size_t n_frames, size_t frame_stride, float* d_out_db,
+                              void* stream) {
+    return exec_device_frames(check_pfb_exec, launch_pfb_ci16, p, d_iq_ci16, n_frames, frame_stride, d_out_db, stream);
+}
+
+int sdrk_exec_device_pfb_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t n_frames, size_t frame_stride,
+                                         float* d_out_db, int launches, float* each_ms) {
+    return exec_device_frames_timed_each(check_pfb_exec, launch_pfb_ci16, p, d_iq_ci16, n_frames, frame_stride, d_out_db, launches,
+                                         each_ms);
+}
+
+int sdrk_exec_host_pfb_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_frames, size_t frame_stride, float* out_db) {
+    return exec_host_pfb(4, launch_pfb_ci16, sdrk::EPI_LOGPSD, p, iq_ci16, n_frames, frame_stride, out_db);
+}
+
+int sdrk_exec_fft_host_pfb_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_frames, size_t frame_stride, void* out_c64) {
+    return exec_host_pfb(4, launch_pfb_ci16, sdrk::EPI_COMPLEX, p, iq_ci16, n_frames, frame_stride, out_c64);
 }
 
 }  // extern "C"

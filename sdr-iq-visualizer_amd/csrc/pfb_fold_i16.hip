@@ -1,6 +1,6 @@
 // pfb_fold_i16.hip — pfb_fold.hip's fold reading interleaved little-endian int16 I,Q (4 bytes per sample), for every length
 // without a folding transform of its own: T blocks of nfft samples under T * nfft coefficients -> one folded frame of nfft
-// complex64, packed, straight into the plan's PFB staging (pfb_ci16_api.hip) — one pass, no widened copy of the stream.
+// complex64, packed, straight into the plan's PFB staging (pfb_api.hip) — one pass, no widened copy of the stream.
 // x[n] = float32(I[n]) + i float32(Q[n]) exactly, then the arithmetic of pfb_fold_kernel (kernels_pfb.h).
 #include "kernels_pfb.h"
 #include "pfb_fold_body.h"

@@ -27,6 +27,24 @@ struct HostSlot {
     void* user_out = nullptr;
     size_t out_bytes = 0;
 };
+
+// Plan-owned device staging that calls on any stream share: growing buffers under one ordering.  `ev` follows the last work
+// enqueued on the buffers (on stream `last`; busy: there may be such work).  A call reserves what it needs, enters on its
+// stream, enqueues its work and leaves; the buffers only grow, and never under work that still uses them.
+struct Staging {
+    hipEvent_t ev = nullptr;
+    hipStream_t last = nullptr;
+    bool busy = false;
+    struct Buf {
+        void* d = nullptr;
+        size_t cap = 0;
+    } buf[2];                                 // (the integrated calls keep two under one ordering)
+    int reserve(int i, size_t need);          // buf[i] of at least `need` bytes; the host waits for work in flight before it reallocates
+    int wait();                               // the host waits for the work in flight
+    int enter(hipStream_t stream);            // `stream` waits for the last user if that was another stream
+    int leave(hipStream_t stream, int st);    // the event behind this call's work, also after a failed launch; -> st or the record's failure
+    void release();                           // plan destruction
+};
 }  // namespace sdrk_host
 
 struct sdrk_plan {
@@ -88,34 +106,19 @@ struct sdrk_plan {
     double* d_window64 = nullptr;   // nfft doubles, or nullptr for rectangular
     double* d_tw64 = nullptr;       // W_4096^m, m < 4096, complex128 (interleaved)
     void* d_scratch64 = nullptr;    // two-pass lengths: scratch_frames * nfft complex128
-    // int16 input (ci16_api.hip) at the lengths without an int16-reading kernel: complex64 staging the frames are widened
-    // into, at most 64 MiB, only grows; ev_ci16 follows the last work enqueued on it (on ci16_stream)
-    void* d_ci16 = nullptr;
-    size_t ci16_cap = 0;
-    hipEvent_t ev_ci16 = nullptr;
-    hipStream_t ci16_stream = nullptr;
-    bool ci16_busy = false;
-    // integrated spectra (integrate_api.hip): d_int_state = two carry rows + the partial rows of split groups; d_int_stage =
-    // complex64 spectra of the lengths without a fused kernel, at most 64 MiB; both only grow; ev_int follows the last work
-    // enqueued on them (on int_stream)
-    void* d_int_state = nullptr;
-    size_t int_state_cap = 0;
-    void* d_int_stage = nullptr;
-    size_t int_stage_cap = 0;
-    hipEvent_t ev_int = nullptr;
-    hipStream_t int_stream = nullptr;
-    bool int_busy = false;
+    // int16 input (ci16_api.hip) at the lengths without an int16-reading kernel: buf[0] = complex64 staging the frames are
+    // widened into, at most 64 MiB
+    sdrk_host::Staging ci16;
+    // integrated spectra (integrate_api.hip): buf[0] = two carry rows + the partial rows of split groups; buf[1] = complex64
+    // spectra of the lengths without a fused kernel, at most 64 MiB
+    sdrk_host::Staging integ;
     // polyphase filter bank (pfb_api.hip): d_pfb_h = the prototype, pfb_taps * nfft float32 (sdrk_plan_set_pfb; 0 taps = none);
-    // pfb_assign = pfb4096_kernel's frame assignment (kernels_pfb.h); d_pfb_stage = folded complex64 frames of the lengths
-    // without a folding transform, at most 64 MiB, only grows; ev_pfb follows the last work enqueued on it (on pfb_stream)
+    // pfb_assign = pfb4096_kernel's frame assignment (kernels_pfb.h); pfb.buf[0] = folded complex64 frames of the lengths
+    // without a folding transform, at most 64 MiB
     float* d_pfb_h = nullptr;
     int pfb_taps = 0;
     int pfb_assign = 0;
-    void* d_pfb_stage = nullptr;
-    size_t pfb_stage_cap = 0;
-    hipEvent_t ev_pfb = nullptr;
-    hipStream_t pfb_stream = nullptr;
-    bool pfb_busy = false;
+    sdrk_host::Staging pfb;
 };
 
 namespace sdrk_host {
@@ -160,6 +163,48 @@ struct PinnedRanges {
 PinnedRanges& pinned_ranges();
 
 int grow(int device, void** buf, size_t* cap, size_t need);   // device staging that only ever grows
+
+inline int Staging::wait() {
+    if (busy) {
+        HIP_TRY(hipEventSynchronize(ev));
+        busy = false;
+    }
+    return SDRK_OK;
+}
+
+inline int Staging::reserve(int i, size_t need) {
+    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    Buf& b = buf[i];
+    if (need <= b.cap) return SDRK_OK;
+    if (int st = wait(); st != SDRK_OK) return st;
+    if (b.d) {
+        HIP_TRY(hipFree(b.d));
+        b.d = nullptr;
+        b.cap = 0;
+    }
+    HIP_TRY(hipMalloc(&b.d, need));
+    b.cap = need;
+    return SDRK_OK;
+}
+
+inline int Staging::enter(hipStream_t stream) {
+    if (busy && last != stream) HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
+    return SDRK_OK;
+}
+
+inline int Staging::leave(hipStream_t stream, int st) {
+    const hipError_t e = hipEventRecord(ev, stream);
+    last = stream;
+    busy = true;
+    if (st == SDRK_OK && e != hipSuccess) st = fail(SDRK_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
+    return st;
+}
+
+inline void Staging::release() {
+    for (Buf& b : buf)
+        if (b.d) (void)hipFree(b.d);
+    if (ev) (void)hipEventDestroy(ev);
+}
 
 // ---- sdrk_plan.hip: argument checks, the launch dispatcher, the fused N = 65536 gate ----
 int check_precision(const sdrk_plan* p, int precision);
@@ -248,29 +293,58 @@ hipError_t stage_chunk_in(sdrk_plan* p, HostSlot& s, const void* pinned_src, siz
 // the small mapped call, the zero-copy chunks and the three-slot pipeline of sdrk_exec_host, for any element sizes
 int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io);
 
+// The per-frame entry points of a mode (sample format x front end), behind their names — the shape integrate_call.h gives
+// the integrated ones.  `check` is the mode's argument check, `launch` its transform.
+using CheckFn = int (*)(const sdrk_plan*, const void* in, size_t n_frames, size_t frame_stride, const void* out);
+int check_exec_f32(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out);   // check_exec_args, float32 (sdrk_plan.hip)
+int launch_f32(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t s);   // plan_launch as a LaunchFn (sdrk_host_pipeline.hip)
+
+inline int exec_device_frames(CheckFn check, LaunchFn launch, sdrk_plan* p, const void* d_in, size_t n_frames, size_t frame_stride,
+                              float* d_out_db, void* stream) {
+    int st = check(p, d_in, n_frames, frame_stride, d_out_db);
+    if (st != SDRK_OK || n_frames == 0) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    return launch(p, d_in, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, stream ? static_cast<hipStream_t>(stream) : p->stream);
+}
+
+inline int exec_device_frames_timed_each(CheckFn check, LaunchFn launch, sdrk_plan* p, const void* d_in, size_t n_frames,
+                                         size_t frame_stride, float* d_out_db, int launches, float* each_ms) {
+    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
+    int st = check(p, d_in, n_frames, frame_stride, d_out_db);
+    if (st != SDRK_OK) return st;
+    st = timed_each(p, launches, each_ms,
+                    [&] { return launch(p, d_in, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
+    return st == SDRK_OK ? fused_check(p) : st;
+}
+
+// The HostIo of a float32 mode: samples of in_elem bytes, a frame reading in_span of them (0: nfft), float32 rows (EPI_LOGPSD)
+// or complex64 out.  Through the copy engines unless the caller sets a zero-copy range.
+inline HostIo frames_io(size_t in_elem, size_t in_span, LaunchFn launch, int epilogue) {
+    HostIo io;
+    io.in_elem = in_elem;
+    io.out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+    io.epilogue = epilogue;
+    io.precision = 32;
+    io.in_span = in_span;
+    io.launch = launch;
+    return io;
+}
+
 // ---- ci16_api.hip ----
 // One transform of a float32 plan on int16 I,Q input (4 bytes per sample), the ci16 form of plan_launch: a LaunchFn.
 int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 
 // ---- pfb_api.hip ----
-// One polyphase-filter-bank transform of a float32 plan on a raw complex64 stream (taps * nfft samples per frame): a LaunchFn.
-// N = 4096 is one launch; every other length folds into d_pfb_stage and runs the plan's transform on that.
+// One polyphase-filter-bank transform of a float32 plan on a raw complex64 stream (taps * nfft samples per frame), and the
+// same on interleaved int16 I,Q (4 bytes per sample): LaunchFns.  N = 4096 is one launch; every other length folds chunks of
+// frames into the plan's PFB staging, at most 64 MiB, and runs the plan's transform on that.
 int launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
-// Its generic route for samples of in_elem bytes: chunks of frames folded by `fold` (kernels_pfb.h's launch_pfb_fold or its
-// int16 form) into d_pfb_stage, at most 64 MiB, each followed by plan_launch; ev_pfb behind the last.
-using PfbFoldFn = hipError_t (*)(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
-                                 void* d_out, int num_cus, hipStream_t stream);
-int pfb_fold_route(sdrk_plan* p, const void* d_in, size_t in_elem, PfbFoldFn fold, size_t n_frames, size_t stride, void* d_out,
-                   int epilogue, hipStream_t stream);
+int launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 // What every PFB entry point refuses: float64 or windowed plans; for any transform, per frame or integrated, also a plan
 // with no prototype set (check_pfb_ready); and for a per-frame one zero frames, NULL pointers, stride 0 with more than one
 // frame (the integrated calls leave those to integrate_call.h).
 int check_pfb_plan(const sdrk_plan* p);
 int check_pfb_ready(const sdrk_plan* p);
 int check_pfb_exec(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out);
-
-// ---- pfb_ci16_api.hip ----
-// The same on interleaved int16 I,Q (4 bytes per sample): a LaunchFn.
-int launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 
 }  // namespace sdrk_host

@@ -256,22 +256,18 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     return fused_check(p);
 }
 
-namespace {
-
+// plan_launch as a LaunchFn (declared in plan_internal.h)
 int launch_f32(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t s) {
     return plan_launch(p, d_in, n_frames, stride, d_out, epilogue, s);
 }
 
+namespace {
+
 // the float32 numpy boundary: complex64 in; float32 rows or complex64 out; the single-pass kernels (nfft <= 16384) may read and
 // write pinned host memory themselves
 HostIo f32_io(int epilogue) {
-    HostIo io;
-    io.in_elem = sizeof(float2);
-    io.out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
-    io.epilogue = epilogue;
-    io.precision = 32;
+    HostIo io = frames_io(sizeof(float2), 0, launch_f32, epilogue);
     io.zero_copy_max_nfft = 16384;
-    io.launch = launch_f32;
     return io;
 }
 

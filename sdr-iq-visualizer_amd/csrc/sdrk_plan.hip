@@ -260,6 +260,10 @@ int check_exec_args(const sdrk_plan* p, const void* in, size_t n_frames, size_t 
     return SDRK_OK;
 }
 
+int check_exec_f32(const sdrk_plan* p, const void* in, size_t n_frames, size_t frame_stride, const void* out) {
+    return check_exec_args(p, in, n_frames, frame_stride, out, 32);
+}
+
 }  // namespace sdrk_host
 
 extern "C" {
@@ -503,14 +507,10 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_in) (void)hipFree(p->d_in);
     if (p->d_out) (void)hipFree(p->d_out);
     if (p->d_feat) (void)hipFree(p->d_feat);
-    if (p->d_ci16) (void)hipFree(p->d_ci16);
-    if (p->ev_ci16) (void)hipEventDestroy(p->ev_ci16);
-    if (p->d_int_state) (void)hipFree(p->d_int_state);
-    if (p->d_int_stage) (void)hipFree(p->d_int_stage);
-    if (p->ev_int) (void)hipEventDestroy(p->ev_int);
+    p->ci16.release();
+    p->integ.release();
     if (p->d_pfb_h) (void)hipFree(p->d_pfb_h);
-    if (p->d_pfb_stage) (void)hipFree(p->d_pfb_stage);
-    if (p->ev_pfb) (void)hipEventDestroy(p->ev_pfb);
+    p->pfb.release();
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {
@@ -536,11 +536,7 @@ int sdrk_plan_device(const sdrk_plan* p) { return p ? p->device : fail(SDRK_ERR_
 
 int sdrk_exec_device(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride,
                      float* d_out_db, void* stream) {
-    int st = check_exec_args(p, d_iq, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK || n_frames == 0) return st;
-    HIP_TRY(hipSetDevice(p->device));
-    return plan_launch(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD,
-                       stream ? static_cast<hipStream_t>(stream) : p->stream);
+    return exec_device_frames(check_exec_f32, launch_f32, p, d_iq, n_frames, frame_stride, d_out_db, stream);
 }
 
 int sdrk_plan_sync(sdrk_plan* p) {
@@ -569,12 +565,7 @@ int sdrk_exec_device_timed(sdrk_plan* p, const void* d_iq, size_t n_frames, size
 
 int sdrk_exec_device_timed_each(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t frame_stride,
                                 float* d_out_db, int launches, float* each_ms) {
-    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
-    int st = check_exec_args(p, d_iq, n_frames, frame_stride, d_out_db);
-    if (st != SDRK_OK) return st;
-    st = timed_each(p, launches, each_ms,
-                    [&] { return plan_launch(p, d_iq, n_frames, frame_stride, d_out_db, sdrk::EPI_LOGPSD, p->stream); });
-    return st == SDRK_OK ? fused_check(p) : st;
+    return exec_device_frames_timed_each(check_exec_f32, launch_f32, p, d_iq, n_frames, frame_stride, d_out_db, launches, each_ms);
 }
 
 }  // extern "C"

@@ -42,7 +42,7 @@ from __future__ import annotations
 import hashlib
 import threading
 import time
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -151,6 +151,44 @@ def pfb_prototype(nfft: int, taps: int, window: WindowArg = "hann") -> np.ndarra
             raise ValueError(f"window must have shape ({n},), got {w.shape}")
     m = np.arange(n, dtype=np.float64)
     return (np.sinc((m - (n - 1) / 2.0) / nfft) * w).astype(np.float32)
+
+
+class _Mode(NamedTuple):
+    """One corner of sample format x front end, and the C entry points that serve it (include/sdrk.h)."""
+    ci16: bool                  # int16 I,Q pairs in (else complex64)
+    pfb: bool                   # frames folded from taps * nfft samples by the plan's polyphase filter bank
+    host_db: str                # per frame: host arrays, dB rows
+    host_fft: str               # ... complex spectra
+    device: str                 # ... device pointers
+    timed_each: str             # ... timed launches
+    int_host: str               # one row per k frames: host arrays
+    int_device: str             # ... device pointers
+    int_timed_each: str         # ... timed launches
+
+    def stream(self, iq) -> np.ndarray:
+        """One contiguous stream as the entry points read it: ``(n,)`` complex64, or checked ``(n, 2)`` int16."""
+        return _as_ci16(iq, stream=True) if self.ci16 else _as_c64(iq).reshape(-1)
+
+
+class _Integ(NamedTuple):
+    """What a call that returns one row per ``k`` frames adds to the per-frame one."""
+    k: int
+    detector: str
+    out: str
+    scale: float
+
+
+_C64 = _Mode(False, False, "sdrk_exec_host", "sdrk_exec_fft_host", "sdrk_exec_device", "sdrk_exec_device_timed_each",
+             "sdrk_exec_host_integrated", "sdrk_exec_device_integrated", "sdrk_exec_device_integrated_timed_each")
+_CI16 = _Mode(True, False, "sdrk_exec_host_ci16", "sdrk_exec_fft_host_ci16", "sdrk_exec_device_ci16",
+              "sdrk_exec_device_ci16_timed_each", "sdrk_exec_host_integrated_ci16", "sdrk_exec_device_integrated_ci16",
+              "sdrk_exec_device_integrated_ci16_timed_each")
+_PFB = _Mode(False, True, "sdrk_exec_host_pfb", "sdrk_exec_fft_host_pfb", "sdrk_exec_device_pfb",
+             "sdrk_exec_device_pfb_timed_each", "sdrk_exec_host_pfb_integrated", "sdrk_exec_device_pfb_integrated",
+             "sdrk_exec_device_pfb_integrated_timed_each")
+_PFB_CI16 = _Mode(True, True, "sdrk_exec_host_pfb_ci16", "sdrk_exec_fft_host_pfb_ci16", "sdrk_exec_device_pfb_ci16",
+                  "sdrk_exec_device_pfb_ci16_timed_each", "sdrk_exec_host_pfb_integrated_ci16",
+                  "sdrk_exec_device_pfb_integrated_ci16", "sdrk_exec_device_pfb_integrated_ci16_timed_each")
 
 
 class SpectrumPlan:
@@ -310,6 +348,87 @@ class SpectrumPlan:
             self._run_host(self._exec_host_fn(), x, rows, hop, out)
         return out
 
+    # -- the shared bodies of the modes of _Mode: each public method below is a call into one of these ------------------
+    def _ready(self, m: _Mode, what: str, integrated: bool = False) -> int:
+        """The readiness check of mode ``m`` -> the samples a frame spans: ``nfft``, or ``taps * nfft`` behind the filter
+        bank.  ``what`` names the caller to the user of a double plan (the filter bank names itself)."""
+        if not m.pfb:
+            self._float32_only(what)
+            return self.nfft
+        span = self._pfb_ready()
+        if integrated and self._wkey != "rect":
+            raise ValueError("the polyphase filter bank needs a plan with the rectangular window: the prototype is the window")
+        return span
+
+    def _n_frames(self, span: int, n_samples: int, hop: Optional[int]) -> int:
+        """Full frames of ``span`` samples, ``hop`` apart (default ``nfft``), in a stream of ``n_samples``."""
+        hop = self.nfft if hop is None else int(hop)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        return 0 if int(n_samples) < span else 1 + (int(n_samples) - span) // hop
+
+    def _n_groups(self, span: int, n_samples: int, k: int, hop: Optional[int]) -> int:
+        """Whole groups of ``k`` among those frames."""
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        return self._n_frames(span, n_samples, hop) // int(k)
+
+    def _host_rows(self, m: _Mode, iq, hop: Optional[int], out: Optional[np.ndarray] = None, *, spectra: bool = False,
+                   what: str = "") -> np.ndarray:
+        """Per-frame rows over one contiguous stream: float32 dB rows (into ``out`` when given), or complex64 ``spectra``."""
+        span = self._ready(m, what)
+        x = m.stream(iq)
+        rows = self._n_frames(span, x.shape[0], hop)
+        shape = (rows, self.nfft)
+        res = np.empty(shape, dtype=np.complex64) if spectra else self._out_array(out, shape, np.float32)
+        if rows:
+            fn = getattr(lib(), m.host_fft if spectra else m.host_db)
+            self._run_host(fn, x, rows, self.nfft if hop is None else int(hop), res)
+        return res
+
+    def _host_integrated(self, m: _Mode, iq, hop: Optional[int], i: _Integ, *, what: str = "") -> np.ndarray:
+        """One float32 row per ``i.k`` frames of one contiguous stream, ``(groups, nfft)``."""
+        span = self._ready(m, what, integrated=True)
+        det, form = self._int_codes(i.detector, i.out)
+        x = m.stream(iq)
+        groups = self._n_groups(span, x.shape[0], i.k, hop)
+        res = np.empty((groups, self.nfft), dtype=np.float32)
+        if groups:
+            with self._lock:
+                check(getattr(lib(), m.int_host)(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups), c_size_t(int(i.k)),
+                                                 c_size_t(self.nfft if hop is None else int(hop)), det, form, c_float(i.scale),
+                                                 res.ctypes.data_as(c_void_p)))
+        return res
+
+    def _device_args(self, m: _Mode, d_iq: int, n: int, d_out: int, frame_stride: Optional[int], i: Optional[_Integ],
+                     what: str) -> list:
+        """The C arguments of a device call of mode ``m`` between the plan and the stream (or the launch count), behind its
+        checks; ``i``: the parameters of a call that returns one row per ``i.k`` frames."""
+        self._ready(m, what, i is not None)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        if i is None:
+            return [c_void_p(d_iq), c_size_t(n), c_size_t(stride), c_void_p(d_out)]
+        det, form = self._int_codes(i.detector, i.out)
+        if int(i.k) < 1 or int(n) < 1:
+            raise ValueError("k and n_groups must be >= 1")
+        if stride < 1:
+            raise ValueError("frame_stride must be >= 1")
+        return [c_void_p(d_iq), c_size_t(n), c_size_t(int(i.k)), c_size_t(stride), det, form, c_float(i.scale), c_void_p(d_out)]
+
+    def _exec_device(self, m: _Mode, d_iq: int, n: int, d_out: int, frame_stride: Optional[int], stream: int,
+                     i: Optional[_Integ] = None, *, what: str = "") -> None:
+        args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
+        with self._lock:
+            check(getattr(lib(), m.int_device if i else m.device)(self.handle, *args, c_void_p(stream) if stream else None))
+
+    def _exec_device_timed_each(self, m: _Mode, d_iq: int, n: int, d_out: int, launches: int, frame_stride: Optional[int],
+                                i: Optional[_Integ] = None, *, what: str = "") -> list:
+        args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(getattr(lib(), m.int_timed_each if i else m.timed_each)(self.handle, *args, int(launches), ms))
+        return [float(v) for v in ms]
+
     # -- int16 I,Q input (float32 plans; same bits as the complex64 calls on the widened samples) --------------
     def _frames_ci16(self, iq):
         x = _as_ci16(iq, self.nfft)
@@ -335,37 +454,18 @@ class SpectrumPlan:
 
     def stft_db_ci16(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Spectrogram rows over one contiguous int16 I,Q stream ``(n_samples, 2)``; rows as ``stft_db``."""
-        x = _as_ci16(iq, stream=True)
-        self._float32_only("ci16 input")
-        hop = self.nfft if hop is None else int(hop)
-        if hop < 1:
-            raise ValueError("hop must be >= 1")
-        rows = 0 if x.shape[0] < self.nfft else 1 + (x.shape[0] - self.nfft) // hop
-        out = self._out_array(out, (rows, self.nfft), np.float32)
-        if rows:
-            self._run_host(lib().sdrk_exec_host_ci16, x, rows, hop, out)
-        return out
+        return self._host_rows(_CI16, iq, hop, out, what="ci16 input")
 
     def exec_device_ci16(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                          stream: int = 0) -> None:
         """Device pointers: int16 I,Q in (4 bytes per sample) / float32 rows out, asynchronous on ``stream`` (0: the
         plan's stream); any number of frames."""
-        self._float32_only("ci16 input")
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        with self._lock:
-            check(lib().sdrk_exec_device_ci16(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                              c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._exec_device(_CI16, d_iq, n_frames, d_out, frame_stride, stream, what="ci16 input")
 
     def exec_device_ci16_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
                                     frame_stride: Optional[int] = None) -> list:
         """``exec_device_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        self._float32_only("ci16 input")
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                                         c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_CI16, d_iq, n_frames, d_out, launches, frame_stride, what="ci16 input")
 
     def exec_device_ci16_timed(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
                                frame_stride: Optional[int] = None) -> float:
@@ -412,13 +512,7 @@ class SpectrumPlan:
     def integrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
         """Rows ``integrate`` returns for a stream of ``n_samples``: the ``1 + (n - nfft)//hop`` full frames in whole
         groups of ``k``; trailing frames that do not fill a group are dropped (as ``mlab.psd`` drops a partial segment)."""
-        hop = self.nfft if hop is None else int(hop)
-        if int(k) < 1:
-            raise ValueError("k must be >= 1")
-        if hop < 1:
-            raise ValueError("hop must be >= 1")
-        frames = 0 if n_samples < self.nfft else 1 + (int(n_samples) - self.nfft) // hop
-        return frames // int(k)
+        return self._n_groups(self.nfft, n_samples, k, hop)
 
     def integrate(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
                   scale: float = 1.0) -> np.ndarray:
@@ -427,44 +521,20 @@ class SpectrumPlan:
         ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``).  Frame f covers samples
         ``[f*hop, f*hop + nfft)``.  The reduction runs inside the transform on the GPU; the stream goes through in
         chunks, in device memory that does not depend on its length."""
-        self._float32_only("integrate")
-        det, form = self._int_codes(detector, out)
-        x = _as_c64(iq).reshape(-1)
-        hop = self.nfft if hop is None else int(hop)
-        groups = self.integrated_groups(x.shape[0], k, hop)
-        res = np.empty((groups, self.nfft), dtype=np.float32)
-        if groups:
-            with self._lock:
-                check(lib().sdrk_exec_host_integrated(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
-                                                      c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
-                                                      res.ctypes.data_as(c_void_p)))
-        return res
+        return self._host_integrated(_C64, iq, hop, _Integ(k, detector, out, scale), what="integrate")
 
     def exec_device_integrated(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
                                detector: str = "mean", out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
         """Device pointers: complex64 in, ``n_groups`` float32 rows out (one per ``k`` frames), asynchronous on
         ``stream`` (0: the plan's stream); any number of frames."""
-        self._float32_only("integrate")
-        det, form = self._int_codes(detector, out)
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        with self._lock:
-            check(lib().sdrk_exec_device_integrated(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
-                                                    c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
-                                                    c_void_p(stream) if stream else None))
+        self._exec_device(_C64, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale), what="integrate")
 
     def exec_device_integrated_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
                                           frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
                                           scale: float = 1.0) -> list:
         """``exec_device_integrated`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        self._float32_only("integrate")
-        det, form = self._int_codes(detector, out)
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_integrated_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
-                                                               c_size_t(int(k)), c_size_t(stride), det, form,
-                                                               c_float(scale), c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_C64, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale), what="integrate")
 
     # ... from int16 I,Q: the bits of the three above on the widened samples, from half the input bytes
     def integrate_ci16(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
@@ -472,45 +542,22 @@ class SpectrumPlan:
         """``integrate`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``integrate`` on
         ``float32(I) + 1j*float32(Q)``; no scale is applied to the samples.  At nfft = 4096 the int16 samples are read
         inside the reducing transform."""
-        x = _as_ci16(iq, stream=True)
-        self._float32_only("integrate_ci16")
-        det, form = self._int_codes(detector, out)
-        hop = self.nfft if hop is None else int(hop)
-        groups = self.integrated_groups(x.shape[0], k, hop)
-        res = np.empty((groups, self.nfft), dtype=np.float32)
-        if groups:
-            with self._lock:
-                check(lib().sdrk_exec_host_integrated_ci16(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
-                                                           c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
-                                                           res.ctypes.data_as(c_void_p)))
-        return res
+        return self._host_integrated(_CI16, iq, hop, _Integ(k, detector, out, scale), what="integrate_ci16")
 
     def exec_device_integrated_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
                                     frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
                                     scale: float = 1.0, stream: int = 0) -> None:
         """Device pointers: int16 I,Q in (4 bytes per sample, frame starts 4-byte aligned), ``n_groups`` float32 rows out,
         asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
-        self._float32_only("integrate_ci16")
-        det, form = self._int_codes(detector, out)
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        with self._lock:
-            check(lib().sdrk_exec_device_integrated_ci16(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
-                                                         c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
-                                                         c_void_p(stream) if stream else None))
+        self._exec_device(_CI16, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale),
+                          what="integrate_ci16")
 
     def exec_device_integrated_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
                                                frame_stride: Optional[int] = None, detector: str = "mean",
                                                out: str = "db", scale: float = 1.0) -> list:
         """``exec_device_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        self._float32_only("integrate_ci16")
-        det, form = self._int_codes(detector, out)
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_integrated_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
-                                                                    c_size_t(int(k)), c_size_t(stride), det, form,
-                                                                    c_float(scale), c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_CI16, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale), what="integrate_ci16")
 
     # -- polyphase filter bank: T blocks folded under a prototype in front of the transform (float32, rectangular plans) ----
     def set_pfb(self, h) -> int:
@@ -539,71 +586,34 @@ class SpectrumPlan:
     def pfb_frames(self, n_samples: int, hop: Optional[int] = None) -> int:
         """Rows ``pfb_db`` returns for a stream of ``n_samples``: frame r covers samples ``[r*hop, r*hop + taps*nfft)``,
         so ``1 + (n_samples - taps*nfft) // hop`` (0 if the stream is shorter than one span)."""
-        span = self._pfb_ready()
-        hop = self.nfft if hop is None else int(hop)
-        if hop < 1:
-            raise ValueError("hop must be >= 1")
-        return 0 if int(n_samples) < span else 1 + (int(n_samples) - span) // hop
+        return self._n_frames(self._pfb_ready(), n_samples, hop)
 
     def pfb_db(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
         """float32 dB rows ``(pfb_frames, nfft)`` of the polyphase filter bank over one contiguous complex64 stream: the
         plan's ``spectrum_db`` of the folded frames ``sum_t h[t*nfft + n] * x[r*hop + t*nfft + n]``, bit for bit what
         numpy's float32 fold followed by ``spectrum_db`` gives; the fold runs inside the transform on the GPU."""
-        self._pfb_ready()
-        x = _as_c64(iq).reshape(-1)
-        hop = self.nfft if hop is None else int(hop)
-        rows = self.pfb_frames(x.shape[0], hop)
-        out = self._out_array(out, (rows, self.nfft), np.float32)
-        if rows:
-            self._run_host(lib().sdrk_exec_host_pfb, x, rows, hop, out)
-        return out
+        return self._host_rows(_PFB, iq, hop, out)
 
     def pfb_fft(self, iq, hop: Optional[int] = None) -> np.ndarray:
         """complex64 spectra ``(pfb_frames, nfft)`` of the folded frames (fftshifted if the plan shifts), no log."""
-        self._pfb_ready()
-        x = _as_c64(iq).reshape(-1)
-        hop = self.nfft if hop is None else int(hop)
-        rows = self.pfb_frames(x.shape[0], hop)
-        out = np.empty((rows, self.nfft), dtype=np.complex64)
-        if rows:
-            self._run_host(lib().sdrk_exec_fft_host_pfb, x, rows, hop, out)
-        return out
+        return self._host_rows(_PFB, iq, hop, spectra=True)
 
     def exec_device_pfb(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                         stream: int = 0) -> None:
         """Device pointers: the raw complex64 stream in (``(n_frames-1)*frame_stride + taps*nfft`` samples) / float32 rows
         out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
-        self._pfb_ready()
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                             c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._exec_device(_PFB, d_iq, n_frames, d_out, frame_stride, stream)
 
     def exec_device_pfb_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
                                    frame_stride: Optional[int] = None) -> list:
         """``exec_device_pfb`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        self._pfb_ready()
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                                        c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_PFB, d_iq, n_frames, d_out, launches, frame_stride)
 
     # ... integrated: one row per k folded frames (the spectrometer form of the filter bank)
-    def _pfb_int_ready(self, detector: str, out: str):
-        span = self._pfb_ready()
-        if self._wkey != "rect":
-            raise ValueError("the polyphase filter bank needs a plan with the rectangular window: the prototype is the window")
-        det, form = self._int_codes(detector, out)
-        return span, det, form
-
     def pfb_integrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
         """Rows ``pfb_integrate`` returns for a stream of ``n_samples``: the ``pfb_frames`` full frames in whole groups of
         ``k``; trailing frames that do not fill a group are dropped."""
-        if int(k) < 1:
-            raise ValueError("k must be >= 1")
-        return self.pfb_frames(n_samples, hop) // int(k)
+        return self._n_groups(self._pfb_ready(), n_samples, k, hop)
 
     def pfb_integrate(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
                       scale: float = 1.0) -> np.ndarray:
@@ -612,134 +622,63 @@ class SpectrumPlan:
         frame of ``pfb_db``, as ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``) — bit for bit
         ``integrate`` on the packed folded frames.  Fold, transform and reduction run in one kernel at nfft = 4096; the
         stream goes through in chunks, in device memory that does not depend on its length."""
-        _, det, form = self._pfb_int_ready(detector, out)
-        x = _as_c64(iq).reshape(-1)
-        hop = self.nfft if hop is None else int(hop)
-        groups = self.pfb_integrated_groups(x.shape[0], k, hop)
-        res = np.empty((groups, self.nfft), dtype=np.float32)
-        if groups:
-            with self._lock:
-                check(lib().sdrk_exec_host_pfb_integrated(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
-                                                          c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
-                                                          res.ctypes.data_as(c_void_p)))
-        return res
-
-    def _pfb_int_device_args(self, n_groups: int, k: int, frame_stride: Optional[int], detector: str, out: str):
-        _, det, form = self._pfb_int_ready(detector, out)
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        if int(k) < 1 or int(n_groups) < 1:
-            raise ValueError("k and n_groups must be >= 1")
-        if stride < 1:
-            raise ValueError("frame_stride must be >= 1")
-        return stride, det, form
+        return self._host_integrated(_PFB, iq, hop, _Integ(k, detector, out, scale))
 
     def exec_device_pfb_integrated(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
                                    frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
                                    scale: float = 1.0, stream: int = 0) -> None:
         """Device pointers: the raw complex64 stream in (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples),
         ``n_groups`` float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
-        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_integrated(self.handle, c_void_p(d_iq), c_size_t(n_groups), c_size_t(int(k)),
-                                                        c_size_t(stride), det, form, c_float(scale), c_void_p(d_out),
-                                                        c_void_p(stream) if stream else None))
+        self._exec_device(_PFB, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale))
 
     def exec_device_pfb_integrated_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
                                               frame_stride: Optional[int] = None, detector: str = "mean",
                                               out: str = "db", scale: float = 1.0) -> list:
         """``exec_device_pfb_integrated`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_integrated_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
-                                                                   c_size_t(int(k)), c_size_t(stride), det, form,
-                                                                   c_float(scale), c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_PFB, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale))
 
     # ... from int16 I,Q: the bits of the seven above on the widened samples, from half the input bytes
     def pfb_db_ci16(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
         """``pfb_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``pfb_db`` on
         ``float32(I) + 1j*float32(Q)``; no scale is applied to the samples.  The int16 samples are read by the folding
         kernel itself (4 bytes per sample over the link and from device memory)."""
-        x = _as_ci16(iq, stream=True)
-        self._pfb_ready()
-        hop = self.nfft if hop is None else int(hop)
-        rows = self.pfb_frames(x.shape[0], hop)
-        out = self._out_array(out, (rows, self.nfft), np.float32)
-        if rows:
-            self._run_host(lib().sdrk_exec_host_pfb_ci16, x, rows, hop, out)
-        return out
+        return self._host_rows(_PFB_CI16, iq, hop, out)
 
     def pfb_fft_ci16(self, iq, hop: Optional[int] = None) -> np.ndarray:
         """``pfb_fft`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
-        x = _as_ci16(iq, stream=True)
-        self._pfb_ready()
-        hop = self.nfft if hop is None else int(hop)
-        rows = self.pfb_frames(x.shape[0], hop)
-        out = np.empty((rows, self.nfft), dtype=np.complex64)
-        if rows:
-            self._run_host(lib().sdrk_exec_fft_host_pfb_ci16, x, rows, hop, out)
-        return out
+        return self._host_rows(_PFB_CI16, iq, hop, spectra=True)
 
     def exec_device_pfb_ci16(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                              stream: int = 0) -> None:
         """Device pointers: the raw int16 I,Q stream in (``(n_frames-1)*frame_stride + taps*nfft`` samples of 4 bytes, frame
         starts 4-byte aligned) / float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
-        self._pfb_ready()
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_ci16(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                                  c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._exec_device(_PFB_CI16, d_iq, n_frames, d_out, frame_stride, stream)
 
     def exec_device_pfb_ci16_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
                                         frame_stride: Optional[int] = None) -> list:
         """``exec_device_pfb_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        self._pfb_ready()
-        stride = self.nfft if frame_stride is None else int(frame_stride)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_frames), c_size_t(stride),
-                                                             c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_PFB_CI16, d_iq, n_frames, d_out, launches, frame_stride)
 
     def pfb_integrate_ci16(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
                            scale: float = 1.0) -> np.ndarray:
         """``pfb_integrate`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to ``pfb_integrate`` on
         ``float32(I) + 1j*float32(Q)``.  At nfft = 4096 the int16 samples are read inside the folding, reducing transform."""
-        x = _as_ci16(iq, stream=True)
-        _, det, form = self._pfb_int_ready(detector, out)
-        hop = self.nfft if hop is None else int(hop)
-        groups = self.pfb_integrated_groups(x.shape[0], k, hop)
-        res = np.empty((groups, self.nfft), dtype=np.float32)
-        if groups:
-            with self._lock:
-                check(lib().sdrk_exec_host_pfb_integrated_ci16(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups),
-                                                               c_size_t(int(k)), c_size_t(hop), det, form, c_float(scale),
-                                                               res.ctypes.data_as(c_void_p)))
-        return res
+        return self._host_integrated(_PFB_CI16, iq, hop, _Integ(k, detector, out, scale))
 
     def exec_device_pfb_integrated_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *,
                                         frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
                                         scale: float = 1.0, stream: int = 0) -> None:
         """Device pointers: the raw int16 I,Q stream in (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples of 4 bytes),
         ``n_groups`` float32 rows out, asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
-        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_integrated_ci16(self.handle, c_void_p(d_iq), c_size_t(n_groups),
-                                                             c_size_t(int(k)), c_size_t(stride), det, form, c_float(scale),
-                                                             c_void_p(d_out), c_void_p(stream) if stream else None))
+        self._exec_device(_PFB_CI16, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale))
 
     def exec_device_pfb_integrated_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
                                                    frame_stride: Optional[int] = None, detector: str = "mean",
                                                    out: str = "db", scale: float = 1.0) -> list:
         """``exec_device_pfb_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
-        stride, det, form = self._pfb_int_device_args(n_groups, k, frame_stride, detector, out)
-        ms = (c_float * int(launches))()
-        with self._lock:
-            check(lib().sdrk_exec_device_pfb_integrated_ci16_timed_each(self.handle, c_void_p(d_iq), c_size_t(n_groups),
-                                                                        c_size_t(int(k)), c_size_t(stride), det, form,
-                                                                        c_float(scale), c_void_p(d_out), int(launches), ms))
-        return [float(v) for v in ms]
+        return self._exec_device_timed_each(_PFB_CI16, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale))
 
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
@@ -749,33 +688,24 @@ class SpectrumPlan:
             return float(np.sum(np.hanning(self.nfft) ** 2))
         return float(np.sum(np.frombuffer(self._wkey[1], dtype=np.float32).astype(np.float64) ** 2))
 
+    def _welch_streamed(self, m: _Mode, what: str, iq, sample_rate: float, hop: Optional[int]) -> np.ndarray:
+        self._float32_only(what)
+        x = m.stream(iq)
+        rows = self._n_frames(self.nfft, x.shape[0], hop)
+        if not rows:
+            raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {self.nfft}-sample segment")
+        scale = 1.0 / (float(sample_rate) * self.window_power())
+        return self._host_integrated(m, x, hop, _Integ(rows, "mean", "power", scale), what=what)[0]
+
     def welch_psd_streamed(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
         """``welch_psd`` through the integrated path: one group of all full segments, mean, linear power.  No
         ``max_batch`` limit, and the stream is not staged whole on the device."""
-        self._float32_only("welch_psd_streamed")
-        x = _as_c64(iq).reshape(-1)
-        hop = self.nfft if hop is None else int(hop)
-        if hop < 1:
-            raise ValueError("hop must be >= 1")
-        if x.shape[0] < self.nfft:
-            raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {self.nfft}-sample segment")
-        rows = 1 + (x.shape[0] - self.nfft) // hop
-        scale = 1.0 / (float(sample_rate) * self.window_power())
-        return self.integrate(x, rows, hop, "mean", "power", scale)[0]
+        return self._welch_streamed(_C64, "welch_psd_streamed", iq, sample_rate, hop)
 
     def welch_psd_streamed_ci16(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
         """``welch_psd_streamed`` over an int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples (in
         units of the integer samples: no scale is applied to them)."""
-        x = _as_ci16(iq, stream=True)
-        self._float32_only("welch_psd_streamed_ci16")
-        hop = self.nfft if hop is None else int(hop)
-        if hop < 1:
-            raise ValueError("hop must be >= 1")
-        if x.shape[0] < self.nfft:
-            raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {self.nfft}-sample segment")
-        rows = 1 + (x.shape[0] - self.nfft) // hop
-        scale = 1.0 / (float(sample_rate) * self.window_power())
-        return self.integrate_ci16(x, rows, hop, "mean", "power", scale)[0]
+        return self._welch_streamed(_CI16, "welch_psd_streamed_ci16", iq, sample_rate, hop)
 
     # -- device pointers (bench / pipelines that keep data resident) -------------
     def exec_device(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
@@ -1062,6 +992,18 @@ def _cached_pfb_plan(nfft: int, taps: int, prototype, eps: float, shift: bool, d
     return plan
 
 
+def _pfb_integrated_db(m: _Mode, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device) -> np.ndarray:
+    """The arguments are checked before a plan is made for the prototype."""
+    x = m.stream(iq) if m.ci16 else iq
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    if hop is not None and int(hop) < 1:
+        raise ValueError("hop must be >= 1")
+    SpectrumPlan._int_codes(detector, "db")
+    plan = _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device)
+    return plan._host_integrated(m, x, hop, _Integ(k, detector, "db", 1.0))
+
+
 def pfb_db(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12, shift: bool = True,
            device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
     """Polyphase-filter-bank dB rows ``(rows, nfft)`` over one contiguous complex64 stream: ``taps`` blocks of ``nfft``
@@ -1075,12 +1017,7 @@ def pfb_integrated_db(iq, nfft: int, taps: int, k: int, hop: Optional[int] = Non
                       eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
     """dB rows of a polyphase-filter-bank spectrometer: one row per ``k`` folded frames of ``iq``, the mean / max / min
     power per bin (``SpectrumPlan.pfb_integrate``); prototype and plan cache as for ``pfb_db``."""
-    if int(k) < 1:
-        raise ValueError("k must be >= 1")
-    if hop is not None and int(hop) < 1:
-        raise ValueError("hop must be >= 1")
-    SpectrumPlan._int_codes(detector, "db")
-    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_integrate(iq, k, hop, detector, "db")
+    return _pfb_integrated_db(_PFB, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device)
 
 
 def pfb_db_ci16(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12,
@@ -1095,13 +1032,7 @@ def pfb_integrated_db_ci16(iq, nfft: int, taps: int, k: int, hop: Optional[int] 
                            prototype=None, *, eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
     """``pfb_integrated_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on the
     widened samples, from half the input bytes."""
-    x = _as_ci16(iq, stream=True)
-    if int(k) < 1:
-        raise ValueError("k must be >= 1")
-    if hop is not None and int(hop) < 1:
-        raise ValueError("hop must be >= 1")
-    SpectrumPlan._int_codes(detector, "db")
-    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_integrate_ci16(x, k, hop, detector, "db")
+    return _pfb_integrated_db(_PFB_CI16, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

@@ -1,5 +1,5 @@
 // tests/fake_kgroup_ci16_kernels.cpp — stand-in for the int16 integrate kernel of csrc/kernels_kgroup_ci16.h, for the host-only
-// sanitizer build of csrc/kgroup_ci16_api.hip (with the stand-in runtime of tests/fake_hip, and beside fake_integrate_kernels.cpp
+// sanitizer build of csrc/integrate_api.hip (with the stand-in runtime of tests/fake_hip, and beside fake_integrate_kernels.cpp
 // and fake_ci16_kernels.cpp, which serve the staged lengths of the same calls).  It keeps the real kernel's contract — units
 // from integrate_split.h, the frames [f0, f1) of a launch, Kahan / max / min state, carry rows in and out, partial rows — on
 // fake_integrate_kernels.cpp's checkable "transform" of the widened samples: the spectrum of a frame is (I + 1, Q - 1) at

@@ -1,6 +1,6 @@
 // tests/fake_pfb_ci16_kernels.cpp — stand-ins for the three int16 polyphase-filter-bank launchers of csrc/kernels_pfb.h
 // (launch_pfb4096_i16, launch_pfb_fold_i16, launch_pfb4096_i16_groups), for the host-only sanitizer build of
-// csrc/pfb_ci16_api.hip beside fake_pfb_kernels.cpp, fake_pfb_groups_kernels.cpp and fake_integrate_kernels.cpp (with the
+// csrc/pfb_api.hip and csrc/integrate_api.hip beside fake_pfb_kernels.cpp, fake_pfb_groups_kernels.cpp and fake_integrate_kernels.cpp (with the
 // stand-in runtime of tests/fake_hip).  Each widens the int16 pairs of the launch into complex64 on the host and hands them to
 // the complex64 stand-in, whose values the drivers know — so the byte offsets the host code computes for 4-byte samples
 // (chunks, overlap, strides) are what is under test.  The widened copy lives until the enqueued work has run.

@@ -1,5 +1,5 @@
 // tests/fake_pfb_groups_kernels.cpp — stand-in for launch_pfb4096_groups (csrc/kernels_pfb.h), for the host-only sanitizer build
-// of csrc/pfb_groups_api.hip beside fake_pfb_kernels.cpp and fake_integrate_kernels.cpp (with the stand-in runtime of
+// of csrc/integrate_api.hip beside fake_pfb_kernels.cpp and fake_integrate_kernels.cpp (with the stand-in runtime of
 // tests/fake_hip).  A "launch" enqueues a host function on the stream it was given.  It keeps the real kernel's contract — units
 // from integrate_split.h, the frames [f0, f1) of a launch, Kahan / max / min state, carry rows in and out, partial rows — on the
 // composition of the other stand-ins: the real float32 fold of fake_pfb_kernels.cpp, fake_kernels.cpp's EPI_COMPLEX "spectrum"

@@ -1,5 +1,5 @@
 // tests/host_api_integrate_ci16_stress.cpp — drives the host side of the int16 integrated-spectrum entry points
-// (csrc/kgroup_ci16_api.hip on csrc/integrate_call.h, csrc/ci16_api.hip's launch_ci16 and the staging slots of
+// (csrc/integrate_api.hip on csrc/integrate_call.h, csrc/ci16_api.hip's launch_ci16 and the staging slots of
 // csrc/sdrk_host_pipeline.hip; built with the other host files by g++ against the stand-in runtime of tests/fake_hip and the
 // stand-in kernels of tests/fake_kgroup_ci16_kernels.cpp, fake_integrate_kernels.cpp and fake_ci16_kernels.cpp) for the
 // sanitizer legs of tests/test_host_sanitizers_integrate_ci16.py.

@@ -1,5 +1,5 @@
 // tests/host_api_pfb_ci16_stress.cpp — drives the host side of the int16 polyphase-filter-bank entry points
-// (csrc/pfb_ci16_api.hip on top of csrc/pfb_api.hip's generic route, csrc/integrate_call.h and the staging slots of
+// (csrc/pfb_api.hip and csrc/integrate_api.hip on top of csrc/integrate_call.h and the staging slots of
 // csrc/sdrk_host_pipeline.hip; built with the other host files by g++ against the stand-in runtime of tests/fake_hip and the
 // stand-in kernels of tests/fake_pfb_ci16_kernels.cpp beside the existing ones) for the sanitizer legs of
 // tests/test_host_sanitizers_pfb_ci16.py.  A program of its own: nothing is loaded into Python, nothing is preloaded.

@@ -1,5 +1,5 @@
 // tests/host_api_pfb_integrate_stress.cpp — drives the host side of the integrated polyphase-filter-bank entry points
-// (csrc/pfb_groups_api.hip on top of csrc/integrate_call.h, csrc/pfb_api.hip and the staging slots of
+// (csrc/integrate_api.hip on top of csrc/integrate_call.h, csrc/pfb_api.hip and the staging slots of
 // csrc/sdrk_host_pipeline.hip; built with the other host files by g++ against the stand-in runtime of tests/fake_hip and the
 // stand-in kernels of tests/fake_pfb_groups_kernels.cpp, fake_pfb_kernels.cpp and fake_integrate_kernels.cpp) for the sanitizer
 // legs of tests/test_host_sanitizers_pfb_integrate.py.

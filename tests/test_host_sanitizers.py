@@ -14,7 +14,7 @@ import threading
 import numpy as np
 import pytest
 
-from tests.host_sources import host_sources
+from tests.host_sources import build_drivers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -50,31 +50,11 @@ def test_copy_pool_under_sanitizers(stress_binaries, san, helpers):
 
 
 @pytest.fixture(scope="module")
-def host_api_binaries(tmp_path_factory):
-    """csrc/sdrk_*.hip without sdrk_f64.hip — the 2 000 lines of host C++ behind the float32 C ABI — compiled with g++ against
+def host_api_binaries():
+    """The host side of csrc/ (tests/host_sources.py) — with the 2 000 lines of host C++ behind the float32 C ABI — compiled with g++ against
     the stand-in runtime of tests/fake_hip (streams are threads, events are tickets, device memory is malloc: asynchrony and
     bounds are real, the spectrum is not) and linked with the driver tests/host_api_stress.cpp, once per sanitizer."""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not available")
-    out = tmp_path_factory.mktemp("san_api")
-    srcs = [*(("-x c++", src) for src in host_sources(f64=False)),
-            ("", os.path.join(HERE, "fake_hip", "fake_kernels.cpp")), ("", os.path.join(HERE, "host_api_stress.cpp"))]
-    built = {}
-    for name, flags in (("tsan", ["-fsanitize=thread"]),
-                        ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
-        common = [gxx, "-O1", "-g", "-std=c++17", "-pthread", "-I", os.path.join(HERE, "fake_hip"), *flags]
-        objs = []
-        for i, (lang, src) in enumerate(srcs):
-            obj = str(out / f"{name}_{i}.o")
-            r = subprocess.run(common + lang.split() + ["-c", src, "-o", obj], capture_output=True, text=True)
-            assert r.returncode == 0, r.stderr[-3000:]
-            objs.append(obj)
-        exe = str(out / f"host_api_{name}")
-        r = subprocess.run(common + objs + ["-ldl", "-o", exe], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        built[name] = exe
-    return built
+    return build_drivers("host_api_stress.cpp")
 
 
 @pytest.mark.parametrize("san", ["tsan", "asan_ubsan"])

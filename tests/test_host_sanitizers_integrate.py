@@ -1,6 +1,6 @@
 """Sanitizer legs for the host side of the integrated-spectrum entry points (CPU).
 
-csrc/integrate_api.hip and the host files csrc/sdrk_*.hip (whose staging slots and copy streams the host entry shares) compiled
+csrc/integrate_api.hip and the other host files of csrc/ (tests/host_sources.py; whose staging slots and copy streams the host entry shares) compiled
 with g++ against the stand-in runtime of tests/fake_hip and the stand-in kernels of tests/fake_integrate_kernels.cpp (and
 fake_f64_kernels.cpp: the driver also hands an f64 plan to the entry points), driven by tests/host_api_integrate_stress.cpp
 under ThreadSanitizer and under AddressSanitizer + UBSan with leak checking: the device and host entries at the fused and the
@@ -8,41 +8,16 @@ staged lengths, groups and slices carried across chunk and staging boundaries, p
 growing under work in flight, two streams on one plan, and the refusals — three threads on their own plans, every output
 element checked."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-from tests.host_sources import CSRC, host_sources
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests.host_sources import build_drivers
 
 
 @pytest.fixture(scope="module")
-def integrate_binaries(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not available")
-    out = tmp_path_factory.mktemp("san_integrate")
-    srcs = [*(("-x c++", src) for src in host_sources(f64=True)), ("-x c++", os.path.join(CSRC, "integrate_api.hip")),
-            ("", os.path.join(HERE, "fake_hip", "fake_kernels.cpp")), ("", os.path.join(HERE, "fake_f64_kernels.cpp")),
-            ("", os.path.join(HERE, "fake_integrate_kernels.cpp")),
-            ("", os.path.join(HERE, "host_api_integrate_stress.cpp"))]
-    built = {}
-    for name, flags in (("tsan", ["-fsanitize=thread"]),
-                        ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
-        common = [gxx, "-O1", "-g", "-std=c++17", "-pthread", "-I", os.path.join(HERE, "fake_hip"), *flags]
-        objs = []
-        for i, (lang, src) in enumerate(srcs):
-            obj = str(out / f"{name}_{i}.o")
-            r = subprocess.run(common + lang.split() + ["-c", src, "-o", obj], capture_output=True, text=True)
-            assert r.returncode == 0, r.stderr[-3000:]
-            objs.append(obj)
-        exe = str(out / f"host_api_integrate_{name}")
-        r = subprocess.run(common + objs + ["-ldl", "-o", exe], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        built[name] = exe
-    return built
+def integrate_binaries():
+    return build_drivers("host_api_integrate_stress.cpp")
 
 
 @pytest.mark.parametrize("san", ["tsan", "asan_ubsan"])

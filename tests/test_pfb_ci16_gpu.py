@@ -15,6 +15,7 @@ import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan, pfb_prototype
+from tests.test_integrate_ci16_gpu import run_child
 from tests.test_pfb_gpu import DevBuf, fold32, prototype, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -308,3 +309,55 @@ def test_cli_psd_pfb_integrate_on_a_ci16_recording(tmp_path, capsys):
         assert same_bits(z["pfb_db"], pkg.pfb_db(wide, n, taps))
         assert same_bits(z["pfb_integrated_db"], pkg.pfb_integrated_db(wide, n, taps, k))
         assert same_bits(z["integrated_db"], pkg.integrated_db(wide, n, k))
+
+
+# ---- one plan's three stagings (int16 unpack, PFB fold, integrate) used in turn and with work in flight ---------------------------
+CHILD_STAGINGS = r"""
+import torch, numpy as np
+from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
+N, T, K = 128, 2, 3            # below every fused and every int16-reading kernel: each call goes through its staging
+rng = np.random.default_rng(20)
+x = rng.integers(-32768, 32768, size=(4096, 2), dtype=np.int64).astype(np.int16)
+h = rng.standard_normal(T * N).astype(np.float32)
+x_int, x_pfb = x[:4 * K * N], x[:(6 - 1) * 64 + T * N]
+xt_int, xt_pfb = torch.from_numpy(x_int).cuda(), torch.from_numpy(x_pfb).cuda()
+side = torch.cuda.Stream()
+torch.cuda.current_stream().synchronize()
+
+def plan():
+    p = SpectrumPlan(N)
+    p.set_pfb(h)
+    return p
+
+def device_pair(p):
+    a = torch.empty((4, N), dtype=torch.float32, device="cuda")
+    b = torch.empty((6, N), dtype=torch.float32, device="cuda")
+    torch.cuda.current_stream().synchronize()
+    p.exec_device_integrated_ci16(xt_int.data_ptr(), 4, K, a.data_ptr(), detector="max")               # the plan's stream
+    p.exec_device_pfb_ci16(xt_pfb.data_ptr(), 6, b.data_ptr(), frame_stride=64, stream=side.cuda_stream)   # no sync between
+    side.synchronize(); p.sync()
+    return a.cpu().numpy(), b.cpu().numpy()
+
+calls = [lambda p: p.integrate_ci16(x[:2 * K * N], K),                       # 2 groups
+         lambda p: p.pfb_integrate_ci16(x[:(5 * K - 1) * 64 + T * N], K, 64),   # 5 groups at hop 64: the stagings grow
+         device_pair,
+         lambda p: p.stft_db_ci16(x, 32)]
+with plan() as one:
+    got = [c(one) for c in calls]
+for i, c in enumerate(calls):
+    with plan() as fresh:
+        want = c(fresh)
+    for g, w in zip(*((got[i], want) if isinstance(want, tuple) else ((got[i],), (want,)))):
+        assert g.shape == w.shape and g.shape[0] > 0 and np.array_equal(g, w), i
+print("stagings ok")
+"""
+
+
+def test_one_plans_stagings_in_turn_and_in_flight_give_a_fresh_plans_rows():
+    """nfft = 128, T = 2, K = 3 (a fresh process: torch first, one HIP runtime).  On ONE plan: integrate_ci16 over 2 groups,
+    pfb_integrate_ci16 over 5 groups at hop 64 (the stagings grow), exec_device_integrated_ci16 on the plan's stream and
+    exec_device_pfb_ci16 on a second stream with no sync between them, stft_db_ci16 at hop 32 — each equal to the same call
+    on a fresh plan.  This checks the bits that come through stagings that were used before, grew and are used again; the two
+    calls in flight use different stagings (int16 unpack and integrate against the PFB fold), so it does not prove the ordering
+    of two streams on ONE staging — the stand-in runtime does, under ThreadSanitizer (tests/test_host_sanitizers_*.py)."""
+    run_child(CHILD_STAGINGS, "stagings ok")
