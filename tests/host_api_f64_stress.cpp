@@ -6,47 +6,16 @@
 // pipeline from pageable and from pinned caller arrays, overlapped frames, ragged last chunks, the two-pass lengths' scratch —
 // must deliver 3 re - im + (k & 1023) for every element (complex epilogue: (re + 1, im - 1)), from two threads on two plans at
 // once; and plans of one precision must be refused by the other precision's entry points.  Exit code 0 = every check passed.
-#include "../include/sdrk.h"
-
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <random>
-#include <thread>
-#include <vector>
-
-static std::atomic<int> g_bad{0};
-#define CHECK(cond)                                                                          \
-    do {                                                                                     \
-        if (!(cond)) {                                                                       \
-            if (g_bad.fetch_add(1) < 20) fprintf(stderr, "CHECK failed %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, sdrk_last_error()); \
-        }                                                                                    \
-    } while (0)
-
-static void fill(double* x, size_t n_samples, unsigned seed) {
-    std::mt19937 rng(seed);
-    for (size_t i = 0; i < 2 * n_samples; ++i) x[i] = (double)((int)(rng() & 0xFFF) - 2048) + 0.25;
-}
+#include "host_stress.h"
 
 // One call of each epilogue over (n_frames, stride) of nfft, from pageable or pinned (library-allocated) arrays.
 static void one_case(sdrk_plan* p, int nfft, size_t n_frames, size_t stride, bool pinned, unsigned seed) {
     const size_t in_samples = (n_frames - 1) * stride + (size_t)nfft, rows = n_frames * (size_t)nfft;
-    std::vector<double> in_v, db_v, c_v;
-    double *in = nullptr, *db = nullptr, *cx = nullptr;
-    if (pinned) {
-        void *a = nullptr, *b = nullptr, *c = nullptr;
-        CHECK(sdrk_host_alloc(in_samples * 16, &a) == SDRK_OK);
-        CHECK(sdrk_host_alloc(rows * 8, &b) == SDRK_OK);
-        CHECK(sdrk_host_alloc(rows * 16, &c) == SDRK_OK);
-        in = static_cast<double*>(a), db = static_cast<double*>(b), cx = static_cast<double*>(c);
-        if (!in || !db || !cx) return;
-    } else {
-        in_v.resize(2 * in_samples), db_v.resize(rows), c_v.resize(2 * rows);
-        in = in_v.data(), db = db_v.data(), cx = c_v.data();
-    }
-    fill(in, in_samples, seed);
-    CHECK(sdrk_exec_host_f64(p, in, n_frames, stride, db) == SDRK_OK);
-    CHECK(sdrk_exec_fft_host_f64(p, in, n_frames, stride, cx) == SDRK_OK);
+    Buf<double> in(2 * in_samples, pinned), db(rows, pinned), cx(2 * rows, pinned);
+    if (!in.data() || !db.data() || !cx.data()) return;
+    fill_wide(in.data(), in_samples, seed);
+    CHECK(sdrk_exec_host_f64(p, in.data(), n_frames, stride, db.data()) == SDRK_OK);
+    CHECK(sdrk_exec_fft_host_f64(p, in.data(), n_frames, stride, cx.data()) == SDRK_OK);
     int bad = 0;
     for (size_t f = 0; f < n_frames; ++f)
         for (size_t k = 0; k < (size_t)nfft; ++k) {
@@ -54,12 +23,8 @@ static void one_case(sdrk_plan* p, int nfft, size_t n_frames, size_t stride, boo
             bad += db[f * nfft + k] != 3.0 * re - im + (double)(k & 1023);
             bad += cx[2 * (f * nfft + k)] != re + 1.0 || cx[2 * (f * nfft + k) + 1] != im - 1.0;
         }
+    g_compared += 3 * rows;
     CHECK(bad == 0);
-    if (pinned) {
-        CHECK(sdrk_host_free(in) == SDRK_OK);
-        CHECK(sdrk_host_free(db) == SDRK_OK);
-        CHECK(sdrk_host_free(cx) == SDRK_OK);
-    }
 }
 
 static void worker(int t, int iters) {
@@ -98,20 +63,20 @@ static void refusals() {
     CHECK(sdrk_plan_precision(p32) == 32);
     std::vector<double> in(2 * 4 * 4096, 1.0), out(2 * 4 * 4096);
     std::vector<float> out32(4 * 4096);
-    CHECK(sdrk_exec_host(p64, in.data(), 2, 4096, out32.data()) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_fft_host(p64, in.data(), 2, 4096, out.data()) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_device(p64, in.data(), 2, 4096, out32.data(), nullptr) == SDRK_ERR_INVALID);
-    CHECK(sdrk_welch_psd_host(p64, in.data(), 2, 4096, 1.0f, out32.data()) == SDRK_ERR_INVALID);
+    REFUSED(sdrk_exec_host(p64, in.data(), 2, 4096, out32.data()));
+    REFUSED(sdrk_exec_fft_host(p64, in.data(), 2, 4096, out.data()));
+    REFUSED(sdrk_exec_device(p64, in.data(), 2, 4096, out32.data(), nullptr));
+    REFUSED(sdrk_welch_psd_host(p64, in.data(), 2, 4096, 1.0f, out32.data()));
     float ms[2];
-    CHECK(sdrk_exec_device_timed_each(p64, in.data(), 2, 4096, out32.data(), 2, ms) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_host_f64(p32, in.data(), 2, 4096, out.data()) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_fft_host_f64(p32, in.data(), 2, 4096, out.data()) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_device_f64(p32, in.data(), 2, 4096, out.data(), nullptr) == SDRK_ERR_INVALID);
-    CHECK(sdrk_exec_device_f64_timed_each(p32, in.data(), 2, 4096, out.data(), 2, ms) == SDRK_ERR_INVALID);
+    REFUSED(sdrk_exec_device_timed_each(p64, in.data(), 2, 4096, out32.data(), 2, ms));
+    REFUSED(sdrk_exec_host_f64(p32, in.data(), 2, 4096, out.data()));
+    REFUSED(sdrk_exec_fft_host_f64(p32, in.data(), 2, 4096, out.data()));
+    REFUSED(sdrk_exec_device_f64(p32, in.data(), 2, 4096, out.data(), nullptr));
+    REFUSED(sdrk_exec_device_f64_timed_each(p32, in.data(), 2, 4096, out.data(), 2, ms));
     sdrk_waterfall* wf = nullptr;
     CHECK(sdrk_waterfall_create(0, 4096, 4, &wf) == SDRK_OK);
-    CHECK(sdrk_waterfall_append_iq(wf, p64, in.data(), 2, 4096) == SDRK_ERR_INVALID);
-    CHECK(sdrk_waterfall_append_iq_device(wf, p64, in.data(), 2, 4096) == SDRK_ERR_INVALID);
+    REFUSED(sdrk_waterfall_append_iq(wf, p64, in.data(), 2, 4096));
+    REFUSED(sdrk_waterfall_append_iq_device(wf, p64, in.data(), 2, 4096));
     CHECK(sdrk_waterfall_destroy(wf) == SDRK_OK);
     // the refused plans still work
     CHECK(sdrk_exec_host_f64(p64, in.data(), 2, 4096, out.data()) == SDRK_OK && out[5] == 3.0 - 1.0 + 5.0);
@@ -120,11 +85,5 @@ static void refusals() {
 }
 
 int main(int argc, char** argv) {
-    const int threads = argc > 1 ? atoi(argv[1]) : 2, iters = argc > 2 ? atoi(argv[2]) : 1;
-    refusals();
-    std::vector<std::thread> ts;
-    for (int t = 0; t < threads; ++t) ts.emplace_back(worker, t, iters);
-    for (auto& t : ts) t.join();
-    printf("sdrk %d f64 threads=%d bad=%d\n", sdrk_version(), threads, g_bad.load());
-    return g_bad.load() ? 1 : 0;
+    return run_stress("f64", argc > 1 ? atoi(argv[1]) : 2, argc > 2 ? atoi(argv[2]) : 1, refusals, worker);
 }

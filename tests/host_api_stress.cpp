@@ -11,24 +11,10 @@
 //
 // Reference sites this answers: the reference mutates shared state from its reader thread and from Flask request threads
 // without synchronisation (app/sdr/streamer.py:19-21,100-101; app/dashboard/callbacks.py:19,96).
-#include "../include/sdrk.h"
+#include "host_stress.h"   // CHECK and its counter; this program has threads and a last line of its own
 
-#include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <random>
-#include <thread>
-#include <vector>
-
-static std::atomic<int> g_bad{0};
-#define CHECK(cond)                                                                          \
-    do {                                                                                     \
-        if (!(cond)) {                                                                       \
-            if (g_bad.fetch_add(1) < 20) fprintf(stderr, "CHECK failed %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, sdrk_last_error()); \
-        }                                                                                    \
-    } while (0)
 
 struct c64 { float re, im; };
 
@@ -292,7 +278,6 @@ static void placement_and_misc() {
     CHECK(sdrk_host_link_probe(0, (size_t)4 << 20, &a, &b, &c) == SDRK_OK);
 }
 
-#include <hip/hip_runtime.h>   // the stand-in (tests/fake_hip): fakehip::cus()
 namespace sdrk { extern std::atomic<int> g_fake_fused_fail, g_fake_fused_launches; }
 
 // The default nfft = 65536 plan on a device whose CUs make whole sets: the persistent launch from 512 frames, the two tiled

@@ -1,5 +1,6 @@
-"""How the host side of the C ABI is built for the sanitizer legs (test_host_sanitizers*.py): which files it is made of, and
-one g++ build of them per sanitizer and pytest process, which every driver links."""
+"""How the host side of the C ABI is built for the sanitizer legs (test_host_sanitizers.py, test_host_sanitizers_f64.py,
+test_host_sanitizers_modes.py): which files it is made of, one g++ build of them per sanitizer and pytest process, and each
+driver (a stand-alone program on tests/host_stress.h) linked against it once per sanitizer, whichever tests ask for it."""
 import functools
 import glob
 import os
@@ -55,6 +56,7 @@ def _common_objects(san):
     return out, tuple(objs)
 
 
+@functools.lru_cache(maxsize=None)
 def build_driver(san, driver):
     """tests/<driver> (a stand-alone program) compiled under sanitizer `san` ("tsan" / "asan_ubsan") and linked with the host
     side against the stand-in runtime of tests/fake_hip -> the path of the program."""

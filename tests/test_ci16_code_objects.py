@@ -1,54 +1,14 @@
 """What the compiler made of the int16-input kernels, read from the gfx950 code objects inside the built libsdrk.so (no GPU needed;
-the extraction of tests/test_code_objects.py): the N = 4096 ci16 kernel keeps the complex64 flagship's budgets and really reads
+the extraction of tests/code_objects.py): the N = 4096 ci16 kernel keeps the complex64 flagship's budgets and really reads
 4 bytes per sample, and neither the ci16 forms of fft_lds.hip nor the widening copy spill."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-from sdr_iq_visualizer_amd import _ffi
-
-LLVM = "/opt/rocm/lib/llvm/bin"
+from tests.code_objects import OBJDUMP, code_objects, kernels, no_scratch as _no_scratch  # noqa: F401  (the fixtures)
 
 
-@pytest.fixture(scope="module")
-def code_objects(tmp_path_factory):
-    lib = _ffi.library_path()
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objdump", "llvm-readelf")]
-    if not (os.path.exists(lib) and all(os.path.exists(t) for t in tools)):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path_factory.mktemp("co_ci16")
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([tools[0], "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
-    return sorted(work.glob("libsdrk.so.*gfx950*"))
-
-
-def _notes(code_objects):
-    rows, cur = [], None
-    for co in code_objects:
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        for ln in notes.splitlines():
-            m = re.match(r"\s*\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size):\s*(\S+)", ln)
-            if not m:
-                continue
-            if m.group(1) == "name":
-                if not m.group(2).startswith("_Z"):
-                    continue
-                cur = {"name": m.group(2)}
-                rows.append(cur)
-            elif cur is not None:
-                cur[m.group(1)] = int(m.group(2))
-    return {r["name"]: r for r in rows if "vgpr_count" in r}
-
-
-def _no_scratch(k):
-    return k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k.get("sgpr_spill_count", 0) == 0
-
-
-def test_ci16_flagship_keeps_the_complex64_kernels_budgets(code_objects):
-    by = _notes(code_objects)
+def test_ci16_flagship_keeps_the_complex64_kernels_budgets(kernels):  # noqa: F811
+    by = kernels
     hits = [k for n, k in by.items() if "fft4096_ci16_kernelILb" in n]
     assert len(hits) == 8, sorted(n for n in by if "ci16" in n)          # window on / off x both epilogues x both load forms
     for k in hits:
@@ -59,8 +19,8 @@ def test_ci16_flagship_keeps_the_complex64_kernels_budgets(code_objects):
     assert len([n for n in by if "fft4096_kernelILb" in n]) == 4
 
 
-def test_ci16_fft_lds_forms_and_the_unpack_kernel_do_not_spill(code_objects):
-    by = _notes(code_objects)
+def test_ci16_fft_lds_forms_and_the_unpack_kernel_do_not_spill(kernels):  # noqa: F811
+    by = kernels
     # fft_lds_kernel<LOG2N, HAS_WINDOW, EPILOGUE, STAGED = false, CI16 = true>: LOG2N 8 ... 14 without 12, four forms each
     lds = {n: k for n, k in by.items() if re.search(r"fft_lds_kernelILi\d+ELb[01]ELi[01]ELb0ELb1EE", n)}
     lengths = sorted({int(re.search(r"fft_lds_kernelILi(\d+)E", n).group(1)) for n in lds})
@@ -74,13 +34,13 @@ def test_ci16_fft_lds_forms_and_the_unpack_kernel_do_not_spill(code_objects):
     assert _no_scratch(unpack[0]) and _no_scratch(synth[0])
 
 
-def test_ci16_kernels_read_four_bytes_per_sample(code_objects):
+def test_ci16_kernels_read_four_bytes_per_sample(code_objects):  # noqa: F811
     """The input loads of the N = 4096 ci16 kernel are dword loads (16 per thread and frame; direct form) or dwordx4 loads (4 per
     thread and frame; wide form), never dwordx2 as in the complex64 kernel, whose every buffer load is one; the widening copy
     keeps its 16-byte accesses although its rows are only 4-byte aligned."""
     loads = {}
     for co in code_objects:
-        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout
+        dis = subprocess.run([OBJDUMP, "-d", str(co)], check=True, capture_output=True, text=True).stdout
         cur = None
         for ln in dis.splitlines():
             m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)

@@ -17,21 +17,12 @@ import sdr_iq_visualizer_amd as pkg
 from oracle import cpu_ref
 from sdr_iq_visualizer_amd import _ffi, sigmf_io, synth
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
+from tests.gpu_helpers import DevBuf, same_bits, widen
 from tests.parity import assert_db_parity, assert_db_parity_deep
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def widen(x):
-    return (x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)).astype(np.complex64)
-
-
-def same_bits(a, b):
-    """Equal as bit patterns (array_equal on the values would call two NaNs different and -0.0 / 0.0 the same)."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def input_frames(n, seed, count=None):
@@ -179,27 +170,6 @@ def test_stft_with_half_and_odd_hops(n):
 
 
 # ---- the device route ------------------------------------------------------------------------------------------------
-class DevBuf:
-    def __init__(self, nbytes):
-        self.p = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().sdrk_dev_alloc(0, nbytes, ctypes.byref(self.p)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _ffi.lib().sdrk_dev_free(0, self.p)
-
-    def get(self, shape, dtype, offset=0):
-        a = np.empty(shape, dtype)
-        _ffi.check(_ffi.lib().sdrk_memcpy_d2h(0, a.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.p.value + offset), a.nbytes))
-        return a
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().sdrk_memcpy_h2d(0, self.p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))
-
-
 @pytest.mark.parametrize("n,first,n_frames", [(4096, 0, 9), (4096, (1 << 33) + 5, 3), (1024, 17, 33), (65536, 2, 3), (1000, 1, 4)])
 def test_device_generator_equals_the_numpy_int16_form(n, first, n_frames):
     with DevBuf(n_frames * n * 4) as d:

@@ -2,47 +2,15 @@
 budgets that the occupancy the kernels are designed for depends on, and no scratch — a kernel that silently starts spilling (as the
 complex-output row pass did when complex values became aligned register pairs, round 5) loses its fourth wave per SIMD or pays scratch
 traffic, and nothing else in the CPU suite would notice."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-from sdr_iq_visualizer_amd import _ffi
-
-LLVM = "/opt/rocm/lib/llvm/bin"
+from tests.code_objects import OBJDUMP, code_objects, kernels  # noqa: F401  (the fixtures)
 
 
-def _kernels(tmp_path):
-    lib = _ffi.library_path()
-    if not (os.path.exists(lib) and os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path / "co"
-    work.mkdir()
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
-    rows, cur = [], None
-    for co in sorted(work.glob("libsdrk.so.*gfx950*")):
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        for ln in notes.splitlines():
-            m = re.match(r"\s*\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size|max_flat_workgroup_size):\s*(\S+)", ln)
-            if not m:
-                continue
-            if m.group(1) == "name":
-                if not m.group(2).startswith("_Z"):      # argument names share the key
-                    continue
-                cur = {"name": m.group(2)}
-                rows.append(cur)
-            elif cur is not None:
-                cur[m.group(1)] = int(m.group(2))
-    return [r for r in rows if "vgpr_count" in r]
-
-
-def test_kernels_fit_their_register_budgets_and_do_not_spill(tmp_path):
-    ks = _kernels(tmp_path)
-    assert len(ks) >= 130                                           # every template instantiation the plans can pick
-    by = {k["name"]: k for k in ks}
+def test_kernels_fit_their_register_budgets_and_do_not_spill(kernels):  # noqa: F811
+    by = kernels
+    assert len(by) >= 130                                           # every template instantiation the plans can pick
     spilling = {n: (k["private_segment_fixed_size"], k["vgpr_spill_count"]) for n, k in by.items()
                 if k["private_segment_fixed_size"] or k["vgpr_spill_count"]}   # (SGPRs spilled into VGPR lanes cost no memory)
     assert not spilling, spilling
@@ -68,18 +36,11 @@ def test_kernels_fit_their_register_budgets_and_do_not_spill(tmp_path):
         assert k["vgpr_count"] <= 256
 
 
-def test_transform_kernels_use_packed_complex_arithmetic_and_the_feature_kernel_does_not(tmp_path):
+def test_transform_kernels_use_packed_complex_arithmetic_and_the_feature_kernel_does_not(code_objects):  # noqa: F811
     """cplx.h: packed register pairs everywhere except the issue-bound, four-waves-per-SIMD feature kernel (DESIGN_APPENDIX.md A.13)."""
-    lib = _ffi.library_path()
-    if not os.path.exists(os.path.join(LLVM, "llvm-objdump")) or not os.path.exists(lib):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path / "co"
-    work.mkdir()
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
     counts = {}
-    for co in sorted(work.glob("libsdrk.so.*gfx950*")):
-        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout
+    for co in code_objects:
+        dis = subprocess.run([OBJDUMP, "-d", str(co)], check=True, capture_output=True, text=True).stdout
         cur = None
         for ln in dis.splitlines():
             m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)

@@ -2,49 +2,12 @@
 code objects inside the built libsdrk.so (no GPU needed; notes only, nothing is disassembled): six instantiations, each within
 the budget of three workgroups per CU — at most 168 VGPRs, a third of the LDS, no scratch, no spilled VGPR — and, with a
 prefetch of 16 words where the complex64 kernel holds 32, fewer registers than that kernel."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-from sdr_iq_visualizer_amd import _ffi
-
-LLVM = "/opt/rocm/lib/llvm/bin"
-FIELDS = "name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size"
+from tests.code_objects import kernels  # noqa: F401  (the fixture)
 
 
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    """{mangled name: its note fields} of every kernel in the library."""
-    lib = _ffi.library_path()
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objdump", "llvm-readelf")]
-    if not (os.path.exists(lib) and all(os.path.exists(t) for t in tools)):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path_factory.mktemp("co_integrate_ci16")
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([tools[0], "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
-    rows, cur, lds = [], None, None      # (the notes list a kernel's fields alphabetically: the LDS size comes before its name)
-    for co in sorted(work.glob("libsdrk.so.*gfx950*")):
-        notes = subprocess.run([tools[1], "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        for ln in notes.splitlines():
-            m = re.match(rf"\s*\.({FIELDS}):\s*(\S+)", ln)
-            if not m:
-                continue
-            if m.group(1) == "group_segment_fixed_size":
-                lds = int(m.group(2))
-            elif m.group(1) == "name":
-                if not m.group(2).startswith("_Z"):
-                    continue
-                cur = {"name": m.group(2), "group_segment_fixed_size": lds}
-                rows.append(cur)
-            elif cur is not None:
-                cur[m.group(1)] = int(m.group(2))
-    return {r["name"]: r for r in rows if "vgpr_count" in r}
-
-
-def test_the_six_kernels_fit_three_workgroups_per_cu(kernels):
+def test_the_six_kernels_fit_three_workgroups_per_cu(kernels):  # noqa: F811
     hits = {n: k for n, k in kernels.items() if "fft4096_kgroup_ci16_kernelILb" in n}
     assert len(hits) == 6, sorted(hits)                                    # window on / off x mean / max / min
     assert sorted(re.search(r"ILb([01])ELi([012])EE", n).groups() for n in hits) == [(w, d) for w in "01" for d in "012"]
@@ -60,7 +23,7 @@ def test_the_six_kernels_fit_three_workgroups_per_cu(kernels):
     assert hold < mean, (hold, mean)
 
 
-def test_fewer_registers_than_the_complex64_kernel(kernels):
+def test_fewer_registers_than_the_complex64_kernel(kernels):  # noqa: F811
     new = [k["vgpr_count"] for n, k in kernels.items() if "fft4096_kgroup_ci16_kernelILb" in n]
     c64 = [k["vgpr_count"] for n, k in kernels.items() if "fft4096_integrate_kernelILb" in n]
     assert len(new) == 6 and len(c64) == 6
@@ -68,7 +31,7 @@ def test_fewer_registers_than_the_complex64_kernel(kernels):
     assert max(new) < max(c64), (new, c64)
 
 
-def test_the_names_stay_out_of_the_other_kernels_counts(kernels):
+def test_the_names_stay_out_of_the_other_kernels_counts(kernels):  # noqa: F811
     """The suite counts kernels by substrings of their mangled names; the new ones must fall under none of them."""
     for n in kernels:
         if "kgroup_ci16" in n:

@@ -8,9 +8,6 @@ array_equal on the bit patterns against that call, except the absolute checks ag
 keep the pair from being wrong together.  Inputs are random 12-bit int16 pairs with a tone."""
 import ctypes
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,11 +16,12 @@ import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
-from tests.parity import REL_TOL, assert_db_parity_deep, mag_from_db
+from tests.gpu_helpers import (DevBuf, Pair, check_amplitude, ref_power, ref_reduced, run_child, same_bits_f32 as same_bits,
+                               stream16_noise_tone as stream16, widen_flat as widen)
+from tests.parity import assert_db_parity_deep
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DETECTORS = ("mean", "max", "min")
 FORMS = ("db", "power")
 EPS = 1e-12
@@ -31,108 +29,7 @@ HOST_CHUNK = 16 << 20      # plan_internal.h HOST_CHUNK_BYTES
 INT_STAGE = 64 << 20       # integrate_call.h INT_STAGE_BYTES
 
 
-class DevBuf:
-    def __init__(self, nbytes):
-        self.p = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().sdrk_dev_alloc(0, max(int(nbytes), 8), ctypes.byref(self.p)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _ffi.lib().sdrk_dev_free(0, self.p)
-
-    def get(self, shape, dtype):
-        a = np.empty(shape, dtype)
-        _ffi.check(_ffi.lib().sdrk_memcpy_d2h(0, a.ctypes.data_as(ctypes.c_void_p), self.p, a.nbytes))
-        return a
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().sdrk_memcpy_h2d(0, self.p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def widen(iq):
-    """(n, 2) int16 -> (n,) complex64, exactly."""
-    return np.ascontiguousarray(iq).astype(np.float32).view(np.complex64).reshape(-1)
-
-
-def stream16(seed, n, frames, hop, tone_db=30.0):
-    """(L, 2) int16: 12-bit noise plus an off-bin tone `tone_db` above the noise's per-bin level, L = the span of the frames."""
-    rng = np.random.default_rng(seed)
-    L = (frames - 1) * hop + n
-    noise = 200.0
-    x = (rng.standard_normal(L) + 1j * rng.standard_normal(L)) * (noise / np.sqrt(2))
-    amp = min(noise * 10 ** (tone_db / 20) / np.sqrt(n), 1200.0)
-    x += amp * np.exp(2j * np.pi * (0.1234 + 0.37 / n) * np.arange(L))
-    out = np.empty((L, 2), np.int16)
-    out[:, 0] = np.clip(np.rint(x.real), -2048, 2047)
-    out[:, 1] = np.clip(np.rint(x.imag), -2048, 2047)
-    return out
-
-
-class Pair:
-    """The int16 stream and its widened form resident on the device, and one output buffer: both device entries of a plan."""
-
-    def __init__(self, iq, max_rows, nfft):
-        self.d16, self.d64, self.out = DevBuf(iq.nbytes), DevBuf(iq.nbytes * 2), DevBuf(max_rows * nfft * 4)
-        self.d16.put(iq)
-        self.d64.put(widen(iq))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for d in (self.d16, self.d64, self.out):
-            d.__exit__()
-
-    def ci16(self, plan, groups, k, hop, det, form="db", scale=1.0):
-        self.out.put(np.full((groups, plan.nfft), np.nan, np.float32))       # (the complex64 call's rows are not left there)
-        plan.exec_device_integrated_ci16(self.d16.p.value, groups, k, self.out.p.value, frame_stride=hop, detector=det,
-                                         out=form, scale=scale)
-        plan.sync()
-        return self.out.get((groups, plan.nfft), np.float32)
-
-    def c64(self, plan, groups, k, hop, det, form="db", scale=1.0):
-        plan.exec_device_integrated(self.d64.p.value, groups, k, self.out.p.value, frame_stride=hop, detector=det, out=form,
-                                    scale=scale)
-        plan.sync()
-        return self.out.get((groups, plan.nfft), np.float32)
-
-
-# ---- the reference expressions of tests/test_integrate_gpu.py (copied: that file stays as it is) ---------------------------
-def window_of(kind, n):
-    return np.hanning(n) if kind == "hann" else np.ones(n)
-
-
-def ref_power(x, n, frames, hop, window, shift):
-    """float64 |fft(w x_f)|^2, shape (frames, n), in the plan's bin order."""
-    idx = (np.arange(frames) * hop)[:, None] + np.arange(n)[None, :]
-    p = np.abs(np.fft.fft(x[idx].astype(np.complex128) * window_of(window, n), axis=-1)) ** 2
-    return np.fft.fftshift(p, axes=-1) if shift else p
-
-
-def ref_reduced(p, groups, k, detector):
-    g = p[: groups * k].reshape(groups, k, -1)
-    return {"mean": g.mean(axis=1), "max": g.max(axis=1), "min": g.min(axis=1)}[detector]
-
-
-def check_amplitude(got, out_form, p, groups, k, detector, what):
-    r = ref_reduced(p, groups, k, detector)
-    s_g = np.sqrt(p[: groups * k].reshape(groups, -1).max(axis=1))
-    if out_form == "db":
-        a_got, a_ref = mag_from_db(got), np.sqrt(r) + EPS
-    else:
-        a_got, a_ref = np.sqrt(got.astype(np.float64)), np.sqrt(r)
-    err = np.abs(a_got - a_ref).max(axis=1) / s_g
-    print(f"{what}: amplitude error {err.max():.2e} of S_g")
-    assert np.all(err <= REL_TOL), (what, float(err.max()))
-
-
+# ---- the samples in float64, for the reference expressions of tests/gpu_helpers.py ------------------------------------------
 def x64_of(iq):
     return iq[:, 0].astype(np.float64) + 1j * iq[:, 1].astype(np.float64)
 
@@ -174,22 +71,16 @@ def test_one_group_of_64_frames_is_split_and_finalized():
 
 CHILD_8_CUS = r"""
 import ctypes, numpy as np
-import tests.test_integrate_ci16_gpu as t
+import tests.gpu_helpers as h
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
 n, k, groups = 4096, 7, 30
-iq = t.stream16(8, n, groups * k, n)
-with t.Pair(iq, groups, n) as d, SpectrumPlan(n, window="hann") as plan:
-    for det in t.DETECTORS:
-        for form in t.FORMS:
-            assert t.same_bits(d.ci16(plan, groups, k, n, det, form, 0.5), d.c64(plan, groups, k, n, det, form, 0.5)), (det, form)
+iq = h.stream16_noise_tone(8, n, groups * k, n)
+with h.Pair(iq, groups, n) as d, SpectrumPlan(n, window="hann") as plan:
+    for det in h.DETECTORS:
+        for form in h.FORMS:
+            assert h.same_bits_f32(d.ci16(plan, groups, k, n, det, form, 0.5), d.c64(plan, groups, k, n, det, form, 0.5)), (det, form)
 print("8 cus ok")
 """
-
-
-def run_child(code, marker, **env):
-    r = subprocess.run([sys.executable, "-c", code], cwd=REPO, capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, PYTHONPATH=REPO, **env))
-    assert r.returncode == 0 and marker in r.stdout, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
 
 
 def test_30_groups_on_the_24_workgroups_of_an_8_cu_grid():
@@ -281,22 +172,22 @@ def test_module_functions_match_their_complex64_counterparts():
 
 CHILD_STREAM = r"""
 import torch, numpy as np
-import tests.test_integrate_ci16_gpu as t
+import tests.gpu_helpers as h
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
 for n, k, groups in ((4096, 5, 40), (4096, 64, 1), (1024, 9, 30), (64, 4, 100)):
-    iq = t.stream16(n + k, n, groups * k, n)
+    iq = h.stream16_noise_tone(n + k, n, groups * k, n)
     xt = torch.from_numpy(iq).cuda()
     a = torch.empty((groups, n), dtype=torch.float32, device="cuda")
     b = torch.empty((groups, n), dtype=torch.float32, device="cuda")
     s = torch.cuda.Stream()
     torch.cuda.current_stream().synchronize()
     with SpectrumPlan(n, window="hann") as plan:
-        for det in t.DETECTORS:
+        for det in h.DETECTORS:
             plan.exec_device_integrated_ci16(xt.data_ptr(), groups, k, a.data_ptr(), detector=det, stream=s.cuda_stream)
             plan.exec_device_integrated_ci16(xt.data_ptr(), groups, k, b.data_ptr(), detector=det)   # the plan's: ordered behind it
             s.synchronize(); plan.sync()
-            ref = plan.integrate(t.widen(iq), k, n, det)
-            assert t.same_bits(a.cpu().numpy(), ref) and t.same_bits(b.cpu().numpy(), ref), (n, k, det)
+            ref = plan.integrate(h.widen_flat(iq), k, n, det)
+            assert h.same_bits_f32(a.cpu().numpy(), ref) and h.same_bits_f32(b.cpu().numpy(), ref), (n, k, det)
 print("caller stream ok")
 """
 

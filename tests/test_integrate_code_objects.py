@@ -1,17 +1,13 @@
 """What the compiler made of the integrated-spectrum kernels, read from the gfx950 code objects inside the built libsdrk.so (no
-GPU needed; the extraction of tests/test_code_objects.py): the N = 4096 kernel with its 16 or 32 accumulators still fits three
+GPU needed; the extraction of tests/code_objects.py): the N = 4096 kernel with its 16 or 32 accumulators still fits three
 workgroups per CU — at most 168 VGPRs, a third of the LDS, no scratch — and the scalar unit of the new kernels does nothing
 to memory but load from it."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
+from tests.code_objects import OBJDUMP, code_objects, kernels, no_scratch as _no_scratch  # noqa: F401  (the fixtures)
 
-from sdr_iq_visualizer_amd import _ffi
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 # Everything the scalar unit may do in these kernels, as an allow-list: arithmetic / logic / compares / moves (typed suffix),
 # loads, and program control.  Anything else on the scalar unit — any way of writing memory from it included — fails the test.
 SCALAR_ALU = re.compile(r"^s_\w+_(?:b32|b64|i32|u32|i64|u64|b16|i16|u16)$")
@@ -19,44 +15,8 @@ SCALAR_LOAD = re.compile(r"^s_(?:buffer_)?load_dword(?:x\d+)?$")
 SCALAR_CONTROL = re.compile(r"^s_(?:waitcnt\w*|barrier|branch|cbranch_\w+|endpgm|nop|code_end|sleep|setprio|sendmsg\w*)$")
 
 
-@pytest.fixture(scope="module")
-def code_objects(tmp_path_factory):
-    lib = _ffi.library_path()
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objdump", "llvm-readelf")]
-    if not (os.path.exists(lib) and all(os.path.exists(t) for t in tools)):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path_factory.mktemp("co_integrate")
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([tools[0], "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
-    return sorted(work.glob("libsdrk.so.*gfx950*"))
-
-
-def _notes(code_objects):
-    rows, cur, lds = [], None, None      # (the notes list a kernel's fields alphabetically: the LDS size comes before its name)
-    for co in code_objects:
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        for ln in notes.splitlines():
-            m = re.match(r"\s*\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size):\s*(\S+)", ln)
-            if not m:
-                continue
-            if m.group(1) == "group_segment_fixed_size":
-                lds = int(m.group(2))
-            elif m.group(1) == "name":
-                if not m.group(2).startswith("_Z"):
-                    continue
-                cur = {"name": m.group(2), "group_segment_fixed_size": lds}
-                rows.append(cur)
-            elif cur is not None:
-                cur[m.group(1)] = int(m.group(2))
-    return {r["name"]: r for r in rows if "vgpr_count" in r}
-
-
-def _no_scratch(k):
-    return k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k.get("sgpr_spill_count", 0) == 0
-
-
-def test_the_4096_kernel_fits_three_workgroups_per_cu(code_objects):
-    by = _notes(code_objects)
+def test_the_4096_kernel_fits_three_workgroups_per_cu(kernels):  # noqa: F811
+    by = kernels
     hits = {n: k for n, k in by.items() if "fft4096_integrate_kernelILb" in n}
     assert len(hits) == 6, sorted(hits)                                    # window on / off x mean / max / min
     for n, k in hits.items():
@@ -75,18 +35,18 @@ def test_the_4096_kernel_fits_three_workgroups_per_cu(code_objects):
     assert len([n for n in by if "fft4096_kernelILb" in n]) == 4
 
 
-def test_the_generic_route_and_finalize_do_not_spill(code_objects):
-    by = _notes(code_objects)
+def test_the_generic_route_and_finalize_do_not_spill(kernels):  # noqa: F811
+    by = kernels
     rows = [k for n, k in by.items() if "integrate_rows_kernel" in n]
     fin = [k for n, k in by.items() if "integrate_finalize_kernel" in n]
     assert len(rows) == 3 and len(fin) == 1
     assert all(_no_scratch(k) for k in rows + fin)
 
 
-def test_the_scalar_unit_only_computes_loads_and_branches(code_objects):
+def test_the_scalar_unit_only_computes_loads_and_branches(code_objects):  # noqa: F811
     kernels, seen = set(), set()
     for co in code_objects:
-        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout
+        dis = subprocess.run([OBJDUMP, "-d", str(co)], check=True, capture_output=True, text=True).stdout
         cur = None
         for ln in dis.splitlines():
             m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)

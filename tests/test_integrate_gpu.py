@@ -21,7 +21,8 @@ from oracle import cpu_ref
 from sdr_iq_visualizer_amd import _ffi, cli
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
-from tests.parity import REL_TOL, assert_db_parity, assert_db_parity_deep, mag_from_db
+from tests.gpu_helpers import DevBuf, check_amplitude, ref_power, ref_reduced, same_bits_u32 as same_bits, stream_noise_tone as stream
+from tests.parity import assert_db_parity, assert_db_parity_deep
 
 pytestmark = pytest.mark.gpu
 
@@ -30,58 +31,8 @@ DETECTORS = ("mean", "max", "min")
 EPS = 1e-12
 
 
-class DevBuf:
-    def __init__(self, nbytes):
-        self.p = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().sdrk_dev_alloc(0, max(int(nbytes), 8), ctypes.byref(self.p)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _ffi.lib().sdrk_dev_free(0, self.p)
-
-    def get(self, shape, dtype):
-        a = np.empty(shape, dtype)
-        _ffi.check(_ffi.lib().sdrk_memcpy_d2h(0, a.ctypes.data_as(ctypes.c_void_p), self.p, a.nbytes))
-        return a
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().sdrk_memcpy_h2d(0, self.p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def window_of(kind, n):
-    return np.hanning(n) if kind == "hann" else np.ones(n)
-
-
 def hop_of(kind, n):
     return {"packed": n, "half": n // 2, "gapped": n + n // 3 + 1}[kind]
-
-
-def stream(rng, n, frames, hop, tone_db=30.0, noise=1.0):
-    """Complex64 noise plus a tone `tone_db` above the noise's per-bin level (an off-bin frequency)."""
-    L = (frames - 1) * hop + n
-    x = (rng.standard_normal(L) + 1j * rng.standard_normal(L)) * (noise / np.sqrt(2))
-    amp = noise * 10 ** (tone_db / 20) / np.sqrt(n)
-    x += amp * np.exp(2j * np.pi * (0.1234 + 0.37 / n) * np.arange(L))
-    return x.astype(np.complex64)
-
-
-def ref_power(x, n, frames, hop, window, shift):
-    """float64 |fft(w x_f)|^2, shape (frames, n), in the plan's bin order."""
-    idx = (np.arange(frames) * hop)[:, None] + np.arange(n)[None, :]
-    p = np.abs(np.fft.fft(x[idx].astype(np.complex128) * window_of(window, n), axis=-1)) ** 2
-    return np.fft.fftshift(p, axes=-1) if shift else p
-
-
-def ref_reduced(p, groups, k, detector):
-    g = p[: groups * k].reshape(groups, k, -1)
-    return {"mean": g.mean(axis=1), "max": g.max(axis=1), "min": g.min(axis=1)}[detector]
 
 
 def device_integrate(plan, x, groups, k, hop, detector, out="db", scale=1.0):
@@ -91,18 +42,6 @@ def device_integrate(plan, x, groups, k, hop, detector, out="db", scale=1.0):
                                     scale=scale)
         plan.sync()
         return d_out.get((groups, plan.nfft), np.float32)
-
-
-def check_amplitude(got, out_form, p, groups, k, detector, what):
-    r = ref_reduced(p, groups, k, detector)
-    s_g = np.sqrt(p[: groups * k].reshape(groups, -1).max(axis=1))
-    if out_form == "db":
-        a_got, a_ref = mag_from_db(got), np.sqrt(r) + EPS
-    else:
-        a_got, a_ref = np.sqrt(got.astype(np.float64)), np.sqrt(r)
-    err = np.abs(a_got - a_ref).max(axis=1) / s_g
-    print(f"{what}: amplitude error {err.max():.2e} of S_g")
-    assert np.all(err <= REL_TOL), (what, float(err.max()))
 
 
 # (n, k, groups, hop, window, shift)

@@ -1,15 +1,11 @@
 """What the compiler made of the int16 polyphase-filter-bank kernels, read from the ELF notes of the gfx950 code objects inside
-the built libsdrk.so (no GPU needed; the extraction of tests/test_pfb_code_objects.py): pfb4096_i16_kernel (both epilogues),
+the built libsdrk.so (no GPU needed; the extraction of tests/code_objects.py): pfb4096_i16_kernel (both epilogues),
 pfb4096_i16_groups_kernel (three detectors) and pfb_fold_i16_kernel exist under those names, keep the budgets of their
 complex64 forms — at most 168 VGPRs, no scratch, no spills, the same LDS — and leave every count the existing code-object
 tests assert as it was.  No disassembly is searched."""
 import re
 
-from tests.test_pfb_integrate_code_objects import kernels  # noqa: F401  (the fixture)
-
-
-def _no_scratch(k):
-    return k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0
+from tests.code_objects import kernels, no_scratch_memory as _no_scratch  # noqa: F401  (the fixture)
 
 
 def test_the_per_frame_kernels_keep_three_workgroups_per_cu(kernels):  # noqa: F811

@@ -15,8 +15,8 @@ import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan, pfb_prototype
-from tests.test_integrate_ci16_gpu import run_child
-from tests.test_pfb_gpu import DevBuf, fold32, prototype, same_bits
+from tests.gpu_helpers import (DevBuf, fold32, held_during, prototype, run_child, same_bits, stream16_planted as stream16,
+                               widen_flat as widen)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +26,6 @@ G3 = N4K + N4K // 3 + 1          # an odd, gapped hop
 DETECTORS = ("mean", "max", "min")
 FORMS = ("db", "power")
 SCALE = 0.37
-
-PLANTED = np.array([[-32768, 32767], [32767, -32768], [-1, 0], [0, -1], [-32768, -32768], [32767, 32767], [-1, 1], [1, -1],
-                    [0, 0], [-2, 255], [255, -256], [-256, 256]], dtype=np.int16)
-
-
-def stream16(seed, n_samples):
-    """int16 (n_samples, 2) over the full range; the planted pairs at the start, at the end and scattered."""
-    rng = np.random.default_rng(seed)
-    x = rng.integers(-32768, 32768, size=(n_samples, 2), dtype=np.int64).astype(np.int16)
-    m = min(len(PLANTED), n_samples)
-    x[:m] = PLANTED[:m]
-    x[n_samples - m:] = PLANTED[:m][::-1]
-    if n_samples > 4 * len(PLANTED):
-        at = rng.integers(0, n_samples, size=n_samples // 16)
-        x[at] = PLANTED[rng.integers(0, len(PLANTED), size=at.shape[0])]
-    return x
-
-
-def widen(x16):
-    return np.ascontiguousarray(x16.astype(np.float32)).view(np.complex64).reshape(-1)
-
 
 def test_the_inputs_hold_what_the_checks_rely_on():
     x = stream16(1, 4096)
@@ -172,15 +151,6 @@ def test_other_lengths_integrated_have_the_complex64_bits(n, taps, k, groups, ho
 
 
 # ---- the numpy boundary ------------------------------------------------------------------------------------------------------
-def _held_during(call, warm):
-    free0, free1, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    warm()                                                  # (first call: the runtime's own allocations)
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free0), ctypes.byref(total)))
-    res = call()
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free1), ctypes.byref(total)))
-    return res, int(free0.value) - int(free1.value)
-
-
 @pytest.mark.parametrize("frames,hop", [(3000, N4K), (6000, N4K // 2)])
 def test_host_entries_return_the_device_entries_bits_in_bounded_memory(frames, hop):
     """~49 MB of int16 input at T = 4.  The boundary aims at a quarter of the call per chunk (at most 16 MiB) and at most
@@ -193,7 +163,7 @@ def test_host_entries_return_the_device_entries_bits_in_bounded_memory(frames, h
     with SpectrumPlan(N4K, eps=EPS) as plan:
         plan.set_pfb(pfb_prototype(N4K, taps))
         dev = dev_rows(plan, x16, frames, hop, ci16=True)
-        host, held = _held_during(lambda: plan.pfb_db_ci16(x16, hop), lambda: plan.pfb_db_ci16(x16[: taps * N4K]))
+        host, held = held_during(lambda: plan.pfb_db_ci16(x16, hop), lambda: plan.pfb_db_ci16(x16[: taps * N4K]))
         print(f"frames={frames} hop={hop}: device memory taken by the host call {held / 2**20:.1f} MiB")
         assert held <= 192 << 20, held
         assert same_bits(host, dev)
@@ -209,7 +179,7 @@ def test_host_entries_return_the_device_entries_bits_in_bounded_memory(frames, h
         groups = frames // k
         for det in ("mean", "max"):
             dev_i = dev_int_rows(plan, x16, groups, k, hop, det, "db", ci16=True)
-            host_i, held = _held_during(lambda: plan.pfb_integrate_ci16(x16, k, hop, det, "db", SCALE),
+            host_i, held = held_during(lambda: plan.pfb_integrate_ci16(x16, k, hop, det, "db", SCALE),
                                         lambda: plan.pfb_integrate_ci16(x16[: (k - 1) * hop + taps * N4K], k, hop, det))
             assert held <= 192 << 20, held
             assert same_bits(host_i, dev_i), det

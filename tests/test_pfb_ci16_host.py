@@ -9,19 +9,12 @@ import pytest
 import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, spectrum
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
+from tests.host_helpers import bare_plan
 
 NEW = ("sdrk_exec_device_pfb_ci16", "sdrk_exec_device_pfb_ci16_timed_each", "sdrk_exec_host_pfb_ci16",
        "sdrk_exec_fft_host_pfb_ci16", "sdrk_exec_device_pfb_integrated_ci16", "sdrk_exec_device_pfb_integrated_ci16_timed_each",
        "sdrk_exec_host_pfb_integrated_ci16")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sdrk.h")
-
-
-def bare_plan(nfft, taps=0, wkey="rect", double=False):
-    """A SpectrumPlan object without a device behind it: what the argument checks look at."""
-    p = object.__new__(SpectrumPlan)
-    p.nfft, p.pfb_taps, p._wkey, p._double = nfft, taps, wkey, double
-    p._handle = _ffi.c_void_p()
-    return p
 
 
 def test_header_and_table_declare_the_seven_with_their_counterparts_argument_lists():

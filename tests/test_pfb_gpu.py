@@ -17,75 +17,16 @@ import json
 import numpy as np
 import pytest
 
-from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io, spectrum, synth
+from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io, spectrum
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan, pfb_prototype
+from tests.gpu_helpers import DevBuf, fold32, held_during, prototype, ref64, same_bits, stream_synth_tone as stream
 from tests.parity import REL_TOL, mag_from_db
 
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-12
 N4K = 4096
-
-
-class DevBuf:
-    def __init__(self, nbytes):
-        self.p = ctypes.c_void_p()
-        _ffi.check(_ffi.lib().sdrk_dev_alloc(0, max(int(nbytes), 8), ctypes.byref(self.p)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _ffi.lib().sdrk_dev_free(0, self.p)
-
-    def get(self, shape, dtype):
-        a = np.empty(shape, dtype)
-        _ffi.check(_ffi.lib().sdrk_memcpy_d2h(0, a.ctypes.data_as(ctypes.c_void_p), self.p, a.nbytes))
-        return a
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().sdrk_memcpy_h2d(0, self.p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def stream(seed, n_samples, tone_bin_of_4096=611.3):
-    """complex64: synth.py's 12-bit integer noise plus a tone of amplitude 700, rounded to integers."""
-    x = synth.synth_iq(seed, 0, 1, n_samples)[0].astype(np.complex128)
-    t = 700.0 * np.exp(2j * np.pi * (tone_bin_of_4096 / 4096.0) * np.arange(n_samples))
-    return (x + np.round(t.real) + 1j * np.round(t.imag)).astype(np.complex64)
-
-
-def prototype(kind, n, taps, seed):
-    if kind == "default":
-        return pfb_prototype(n, taps)
-    return np.random.default_rng(seed).standard_normal(taps * n).astype(np.float32)
-
-
-def fold32(x, h, n, taps, frames, hop):
-    """numpy's float32 fold, on float32 pairs (complex-times-real in numpy has zero-sign quirks): complex64 (frames, n)."""
-    xr = x.view(np.float32).reshape(-1, 2)
-    idx = (np.arange(frames) * hop)[:, None] + np.arange(n)[None, :]
-    acc = xr[idx] * h[:n][None, :, None]
-    for t in range(1, taps):
-        acc = acc + xr[idx + t * n] * h[t * n:(t + 1) * n][None, :, None]
-    assert acc.dtype == np.float32
-    return np.ascontiguousarray(acc).view(np.complex64)[..., 0]
-
-
-def ref64(x, h, n, taps, frames, hop, shift):
-    """float64 fold and FFT of the same complex64 samples: complex128 (frames, n) in the plan's bin order."""
-    idx = (np.arange(frames) * hop)[:, None] + np.arange(n)[None, :]
-    xd, hd = x.astype(np.complex128), h.astype(np.float64)
-    y = np.zeros((frames, n), dtype=np.complex128)
-    for t in range(taps):
-        y += xd[idx + t * n] * hd[t * n:(t + 1) * n][None, :]
-    Y = np.fft.fft(y, axis=-1)
-    return np.fft.fftshift(Y, axes=-1) if shift else Y
 
 
 def device_rows(plan, x, frames, hop, pfb):
@@ -171,15 +112,6 @@ def test_n4096_rows_do_not_depend_on_the_frame_assignment(assign, monkeypatch):
         assert same_bits(got, want), (assign, frames, hop)
 
 
-def _held_during(plan, call, warm):
-    free0, free1, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    warm()                                                  # (first call: the runtime's own allocations)
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free0), ctypes.byref(total)))
-    res = call()
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free1), ctypes.byref(total)))
-    return res, int(free0.value) - int(free1.value)
-
-
 @pytest.mark.parametrize("frames,hop", [(3000, N4K), (6000, N4K // 2)])
 def test_host_entry_returns_the_device_entrys_bits_in_bounded_memory(frames, hop):
     """~98 MB of input at T = 4 through the chunked numpy boundary, overlap across every chunk boundary, from a pageable and
@@ -191,7 +123,7 @@ def test_host_entry_returns_the_device_entrys_bits_in_bounded_memory(frames, hop
     with SpectrumPlan(N4K, eps=EPS) as plan:
         plan.set_pfb(h)
         dev = device_rows(plan, x, frames, hop, pfb=True)
-        host, held = _held_during(plan, lambda: plan.pfb_db(x, hop), lambda: plan.pfb_db(x[: taps * N4K]))
+        host, held = held_during(lambda: plan.pfb_db(x, hop), lambda: plan.pfb_db(x[: taps * N4K]))
         print(f"frames={frames} hop={hop}: device memory taken by the host call {held / 2**20:.1f} MiB")
         assert held <= 192 << 20, held
         assert same_bits(host, dev)

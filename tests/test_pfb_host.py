@@ -5,15 +5,8 @@ import pytest
 
 import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, spectrum
-from sdr_iq_visualizer_amd.spectrum import SpectrumPlan, pfb_prototype
-
-
-def bare_plan(nfft, taps=0, wkey="rect", double=False):
-    """A SpectrumPlan object without a device behind it: what the argument checks look at."""
-    p = object.__new__(SpectrumPlan)
-    p.nfft, p.pfb_taps, p._wkey, p._double = nfft, taps, wkey, double
-    p._handle = _ffi.c_void_p()
-    return p
+from sdr_iq_visualizer_amd.spectrum import pfb_prototype
+from tests.host_helpers import bare_plan
 
 
 @pytest.mark.parametrize("nfft,taps", [(64, 1), (64, 16), (1000, 3), (4096, 4), (4096, 32)])

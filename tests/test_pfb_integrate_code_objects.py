@@ -1,52 +1,14 @@
 """What the compiler made of the integrated polyphase-filter-bank kernel, read from the ELF notes of the gfx950 code objects
-inside the built libsdrk.so (no GPU needed; the extraction of tests/test_pfb_code_objects.py): pfb4096_groups_kernel in its
+inside the built libsdrk.so (no GPU needed; the extraction of tests/code_objects.py): pfb4096_groups_kernel in its
 three detectors keeps the budgets of three workgroups per CU — at most 168 VGPRs, a third of the LDS, no scratch.  The mean
 keeps its 16 compensation terms per thread in LDS (the 16 KiB the windowed kernels keep the window in), so its LDS figure is
 theirs and the hold detectors' is the window-less one.  No disassembly is searched."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-from sdr_iq_visualizer_amd import _ffi
-
-LLVM = "/opt/rocm/lib/llvm/bin"
-FIELDS = r"name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size"
+from tests.code_objects import kernels  # noqa: F401  (the fixture)
 
 
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    lib = _ffi.library_path()
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objdump", "llvm-readelf")]
-    if not (os.path.exists(lib) and all(os.path.exists(t) for t in tools)):
-        pytest.skip("needs the built library and the ROCm LLVM tools")
-    work = tmp_path_factory.mktemp("co_pfb_integrate")
-    shutil.copy(lib, work / "libsdrk.so")
-    subprocess.run([tools[0], "--offloading", "libsdrk.so"], cwd=work, check=True, capture_output=True)
-    # a kernel's keys come sorted: .group_segment_fixed_size stands BEFORE its .name, the other figures after it
-    rows, cur, lds = [], None, None
-    for co in sorted(work.glob("libsdrk.so.*gfx950*")):
-        notes = subprocess.run([tools[1], "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        for ln in notes.splitlines():
-            m = re.match(r"\s*\.(" + FIELDS + r"):\s*(\S+)", ln)
-            if not m:
-                continue
-            if m.group(1) == "group_segment_fixed_size":
-                lds = int(m.group(2))
-            elif m.group(1) == "name":
-                if not m.group(2).startswith("_Z"):
-                    continue
-                cur = {"name": m.group(2), "group_segment_fixed_size": lds}
-                lds = None
-                rows.append(cur)
-            elif cur is not None:
-                cur[m.group(1)] = int(m.group(2))
-    return {r["name"]: r for r in rows if "vgpr_count" in r}
-
-
-def test_the_three_detectors_keep_three_workgroups_per_cu(kernels):
+def test_the_three_detectors_keep_three_workgroups_per_cu(kernels):  # noqa: F811
     hits = {re.search(r"pfb4096_groups_kernelILi(\d)EE", n).group(1): k for n, k in kernels.items() if "pfb4096_groups_kernel" in n}
     assert sorted(hits) == ["0", "1", "2"], sorted(n for n in kernels if "pfb" in n)      # mean / max / min, nothing else
     assert len([n for n in kernels if "pfb4096_groups_kernel" in n]) == 3
@@ -60,7 +22,7 @@ def test_the_three_detectors_keep_three_workgroups_per_cu(kernels):
     assert max(hits["1"]["vgpr_count"], hits["2"]["vgpr_count"]) <= hits["0"]["vgpr_count"], hits
 
 
-def test_the_name_stays_out_of_the_existing_counts(kernels):
+def test_the_name_stays_out_of_the_existing_counts(kernels):  # noqa: F811
     new = [n for n in kernels if "pfb4096_groups_kernel" in n]
     assert new
     for n in new:

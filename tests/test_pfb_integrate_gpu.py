@@ -21,8 +21,8 @@ import pytest
 from sdr_iq_visualizer_amd import _ffi, cli, sigmf_io, spectrum
 from sdr_iq_visualizer_amd.hostmem import pinned_empty
 from sdr_iq_visualizer_amd.spectrum import SpectrumPlan, pfb_prototype
+from tests.gpu_helpers import DevBuf, fold32, held_during, prototype, ref64, same_bits, stream_synth_tone as stream
 from tests.parity import REL_TOL
-from tests.test_pfb_gpu import DevBuf, fold32, prototype, ref64, same_bits, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -105,15 +105,6 @@ def test_other_lengths_bits_of_integrate_on_the_folded_frames(n, taps, k, groups
                seed=n % 1000 + taps, bound=False)
 
 
-def _held_during(call, warm):
-    free0, free1, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    warm()                                                  # (first call: the runtime's own allocations)
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free0), ctypes.byref(total)))
-    res = call()
-    _ffi.check(_ffi.lib().sdrk_dev_mem_info(0, ctypes.byref(free1), ctypes.byref(total)))
-    return res, int(free0.value) - int(free1.value)
-
-
 def _long_stream(n_samples):
     return np.tile(stream(5, 64 * N4K + 1), n_samples // (64 * N4K + 1) + 1)[:n_samples]
 
@@ -133,7 +124,7 @@ def test_host_entry_returns_the_device_entrys_bits_in_bounded_memory(frames, hop
         xp[...] = x
         for det, form in (("mean", "db"), ("max", "power")):
             dev = device_rows(plan, x, groups, k, hop, det, form, pfb=True)
-            host, held = _held_during(lambda: plan.pfb_integrate(x, k, hop, det, form, SCALE),
+            host, held = held_during(lambda: plan.pfb_integrate(x, k, hop, det, form, SCALE),
                                       lambda: plan.pfb_integrate(x[: (k - 1) * hop + taps * N4K], k, hop, det, form, SCALE))
             print(f"frames={frames} hop={hop} {det}/{form}: device memory taken by the host call {held / 2**20:.1f} MiB")
             assert held <= 192 << 20, held

@@ -7,15 +7,7 @@ import pytest
 
 import sdr_iq_visualizer_amd as pkg
 from sdr_iq_visualizer_amd import _ffi, spectrum
-from sdr_iq_visualizer_amd.spectrum import SpectrumPlan
-
-
-def bare_plan(nfft, taps=0, wkey="rect", double=False):
-    """A SpectrumPlan object without a device behind it: what the argument checks look at."""
-    p = object.__new__(SpectrumPlan)
-    p.nfft, p.pfb_taps, p._wkey, p._double = nfft, taps, wkey, double
-    p._handle = ctypes.c_void_p()
-    return p
+from tests.host_helpers import bare_plan
 
 
 def test_frame_and_group_arithmetic():
