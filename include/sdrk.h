@@ -405,6 +405,71 @@ int sdrk_exec_device_pfb_integrated_ci16_timed_each(sdrk_plan* plan, const void*
 int sdrk_exec_host_pfb_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                        int detector, int out_form, float scale, float* out);
 
+/* ---- spectral kurtosis: per-bin SK and mean power over K frames in one pass ------------
+ * What a spectrometer accumulates beside the power: the sum of squared powers, and from both the spectral kurtosis estimator of
+ * Nita & Gary, the usual per-channel interference flag of monitoring receivers and radio-astronomy back ends.  Frames and
+ * groups are cut exactly as for sdrk_exec_device_integrated (frame f at sample f*frame_stride, any stride >= 1; group g is the
+ * frames [g*k_frames, (g+1)*k_frames)); the PFB forms cut and fold them as sdrk_exec_device_pfb_integrated does.  With
+ * p_f[k] = |fft(w*x_f)[k]|^2 and M = k_frames,
+ *     S1 = sum_f p_f        S2 = sum_f p_f^2        SK = (M+1)/(M-1) * (M*S2/S1^2 - 1)
+ * Gaussian noise gives SK = 1 with variance 4M^2/((M-1)(M+2)(M+3)) whatever its level; a CW carrier drives SK towards 0, pulsed
+ * or bursty interference well above 1.
+ * Output: per group TWO planes of nfft float32, d_out[n_groups][2][nfft], in the plan's shift order.  Plane 0 is the group's
+ * mean power R = S1/K through the epilogue of the integrated section (SDRK_INT_OUT_DB: 20*log10(sqrt(R) + eps);
+ * SDRK_INT_OUT_POWER: scale * R).  Plane 1 is SK, dimensionless; out_form and scale do not touch it.
+ * Sums: S1 and S2 are plain float32 running sums in frame order, S1 += p and S2 = fmaf(p, p, S2) with p = fmaf(re, re, im*im) as
+ * the integrating kernels form it.  No floating-point atomics.  A group that was cut into slices (few groups on a large device)
+ * has its slices' sums added in slice order in float64 and rounded to float32 once.  SK is then one float32 expression of S1, S2
+ * and M — IEEE division, no fast reciprocal — that every route shares.  S1 == 0 (a dead bin; also S1^2 below the float32 range,
+ * mean |X| under roughly 1e-10) gives SK = 0, never NaN: a bin without power is as non-Gaussian as a carrier.
+ * Accuracy of plane 0: it is NOT the compensated mean of SDRK_DET_MEAN.  Its relative power error may grow as K * 2^-24 on bins
+ * whose power hardly changes from frame to frame; callers who need the 1e-5 amplitude bound at large K take SDRK_DET_MEAN.
+ * Overflow: S2 (and S1^2) leave float32 where p^2 does, |X| above about 4e9; that is not guarded.
+ * Determinism: the same input gives the same bits, from the device entry and the host entry alike, however the host call is
+ * chunked.  The int16 forms return the bits of the complex64 forms on float32(I) + i*float32(Q); the PFB forms the bits of the
+ * complex64 form on the packed folded frames wherever both take the same route (every nfft but 4096).
+ * Refusals, each SDRK_ERR_INVALID with a message: k_frames < 2 (the estimator divides by M - 1); everything the integrated
+ * entry points refuse apart from the detector (an f64 plan, an unknown out_form, n_groups = 0 or the product out of range,
+ * frame_stride = 0, NULL pointers); for the PFB forms a windowed plan or one without a prototype.  A plan that has refused
+ * still works.
+ * N = 4096 keeps both sums in the transform's registers: 8 + 8/K bytes per sample through device memory from complex64,
+ * 4 + 8/K from int16, where reducing per-frame rows afterwards moves 12.  Other lengths reduce the plan's complex spectra from
+ * staging of at most 64 MiB.  The PFB forms fold and transform through the per-frame PFB route into that staging at every
+ * nfft, 4096 included: there is no folding SK kernel.  Not provided: double precision, the generalised estimator for
+ * pre-accumulated spectra, waterfall appends. */
+/* device in / device out (d_out: n_groups * 2 * nfft float32), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_sk(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                        int out_form, float scale, float* d_out, void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` calls (bench harness) */
+int sdrk_exec_device_sk_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                   int out_form, float scale, float* d_out, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
+int sdrk_exec_host_sk(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride, int out_form,
+                      float scale, float* out);
+/* the same three from int16 I,Q (4 bytes per sample, frame starts 4-byte aligned) */
+int sdrk_exec_device_sk_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                             int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_sk_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                        size_t frame_stride, int out_form, float scale, float* d_out, int launches,
+                                        float* each_ms);
+int sdrk_exec_host_sk_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                           int out_form, float scale, float* out);
+/* behind the plan's polyphase filter bank (float32 rectangular plans with a prototype set; a frame covers T*nfft samples) */
+int sdrk_exec_device_pfb_sk(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                            int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_pfb_sk_timed_each(sdrk_plan* plan, const void* d_iq_c64, size_t n_groups, size_t k_frames,
+                                       size_t frame_stride, int out_form, float scale, float* d_out, int launches,
+                                       float* each_ms);
+int sdrk_exec_host_pfb_sk(sdrk_plan* plan, const void* iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                          int out_form, float scale, float* out);
+int sdrk_exec_device_pfb_sk_ci16(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                 int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_pfb_sk_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, size_t n_groups, size_t k_frames,
+                                            size_t frame_stride, int out_form, float scale, float* d_out, int launches,
+                                            float* each_ms);
+int sdrk_exec_host_pfb_sk_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                               int out_form, float scale, float* out);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

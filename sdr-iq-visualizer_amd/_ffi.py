@@ -177,6 +177,19 @@ SYMBOLS = [
                                                                 c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_pfb_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
                                                    c_void_p]),
+    # spectral kurtosis: per group two planes, the mean power and SK from the sums of p and p^2 (no detector argument)
+    ("sdrk_exec_device_sk", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_sk_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_sk", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    ("sdrk_exec_device_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_sk_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    ("sdrk_exec_device_pfb_sk", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_sk_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_sk", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    ("sdrk_exec_device_pfb_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_sk_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
 ]
 
 _lib = None

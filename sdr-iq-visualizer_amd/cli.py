@@ -1,6 +1,6 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
-    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K] [--pfb T] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk]] [--pfb T] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
@@ -33,6 +33,10 @@ def main(argv=None) -> int:
     p.add_argument("--integrate", type=_positive, default=0, metavar="K",
                    help="also write one dB row per K frames of --nfft samples (integrated_db)")
     p.add_argument("--detector", choices=["mean", "max", "min"], default="mean", help="what --integrate keeps per bin")
+    p.add_argument("--sk", action="store_true",
+                   help="with --integrate K (K >= 2): also write the spectral kurtosis per bin and group (array sk) and the mean "
+                        "power it was formed beside (sk_mean_db), behind the filter bank with --pfb T; the report counts the "
+                        "bins outside the 3-sigma band of Gaussian noise")
     p.add_argument("--pfb", type=_positive, default=0, metavar="T",
                    help="also write polyphase-filter-bank dB rows: T blocks of --nfft samples folded under the default "
                         "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db); with --integrate K also one "
@@ -48,6 +52,8 @@ def main(argv=None) -> int:
     s.add_argument("--center-freq", type=float, default=2_400_000_000)
     s.add_argument("--seed", type=int, default=1234)
     args = ap.parse_args(argv)
+    if args.cmd == "psd" and args.sk and args.integrate < 2:
+        ap.error("--sk needs --integrate K with K >= 2")
 
     from . import sigmf_io, synth
     if args.cmd == "synth":
@@ -118,6 +124,20 @@ def main(argv=None) -> int:
                                                   device=args.device)
             results["pfb_integrated_db"] = rows
             report["pfb_integrated_rows"] = int(rows.shape[0])
+    if args.sk:   # (behind the filter bank with --pfb; an int16 recording goes in as it is)
+        x = np.ascontiguousarray(raw16) if raw16 is not None else samples
+        if args.pfb:
+            mean_db, sk = spectrum.pfb_spectral_kurtosis(x, args.nfft, args.pfb, args.integrate, device=args.device)
+        elif raw16 is not None:
+            mean_db, sk = spectrum.spectral_kurtosis_ci16(x, args.nfft, args.integrate, window=args.window, device=args.device)
+        else:
+            mean_db, sk = spectrum.spectral_kurtosis(x, args.nfft, args.integrate, window=args.window, device=args.device)
+        lo, hi = spectrum.sk_limits(args.integrate)
+        results["sk"] = sk
+        results["sk_mean_db"] = mean_db
+        report["sk_rows"] = int(sk.shape[0])
+        report["sk_limits"] = [lo, hi]
+        report["sk_flagged_fraction"] = float(np.mean((sk < lo) | (sk > hi))) if sk.size else 0.0
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out

@@ -12,6 +12,11 @@
 // (fft4096_integrate.hip, fft4096_kgroup_ci16.hip, pfb4096_groups.hip, pfb4096_i16_groups.hip) and the per-frame transform of
 // the other lengths (plan_launch, ci16_api.hip's launch_ci16, pfb_api.hip's launch_pfb / launch_pfb_ci16, which keep their own
 // stagings and orderings).  The PFB entries refuse a plan without a prototype first (check_pfb_ready).
+//
+// The spectral-kurtosis entry points (sdrk_exec_*_sk, _sk_ci16, _pfb_sk, _pfb_sk_ci16) are the same call with the kernels of
+// kernels_sk.h behind it: per group two planes, the mean power and the estimator from S1 = sum p and S2 = sum p^2.  N = 4096
+// keeps the sums inside the transform (sk4096.hip); every other length, and the filter bank at every length (N = 4096 too: fold
+// and transform through launch_pfb / launch_pfb_ci16, no folding SK kernel), reduces staged spectra with sk_rows.hip.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -21,6 +26,7 @@
 #include "kernels_integrate.h"
 #include "kernels_kgroup_ci16.h"
 #include "kernels_pfb.h"
+#include "kernels_sk.h"
 #include "plan_internal.h"
 
 using namespace sdrk_host;
@@ -42,6 +48,21 @@ IntIo c64_io() { return int_io(sizeof(float2), sdrk::launch_fft4096_integrate, l
 IntIo ci16_io() { return int_io(4, sdrk::launch_fft4096_kgroup_ci16, launch_ci16); }
 IntIo pfb_io(const sdrk_plan* p) { return int_io(sizeof(float2), sdrk::launch_pfb4096_groups, launch_pfb, p); }
 IntIo pfb_ci16_io(const sdrk_plan* p) { return int_io(4, sdrk::launch_pfb4096_i16_groups, launch_pfb_ci16, p); }
+
+// spectral kurtosis: the mode's IntIo with the SK kernels behind it (fused: the N = 4096 kernel, or none)
+IntIo sk_io(IntIo io, FusedFn fused) {
+    io.fused = fused;
+    io.rows = sdrk::launch_sk_rows;
+    io.finalize = sdrk::launch_sk_finalize;
+    io.planes = 2;
+    io.min_k = 2;
+    return io;
+}
+
+IntIo sk_c64_io() { return sk_io(c64_io(), sdrk::launch_sk4096); }
+IntIo sk_ci16_io() { return sk_io(ci16_io(), sdrk::launch_sk4096_i16); }
+IntIo sk_pfb_io(const sdrk_plan* p) { return sk_io(pfb_io(p), nullptr); }
+IntIo sk_pfb_ci16_io(const sdrk_plan* p) { return sk_io(pfb_ci16_io(p), nullptr); }
 
 }  // namespace
 
@@ -120,5 +141,35 @@ int sdrk_exec_host_pfb_integrated_ci16(sdrk_plan* p, const void* iq_ci16, size_t
     if (int st = check_pfb_ready(p); st != SDRK_OK) return st;
     return exec_host_integrated(pfb_ci16_io(p), p, iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }
+
+// ---- spectral kurtosis: two planes per group (the detector of the shared call is the mean's, and is not read) ----
+
+#define SDRK_SK_ENTRIES(SUFFIX, IO, READY)                                                                                        \
+    int sdrk_exec_device_##SUFFIX(sdrk_plan* p, const void* d_iq, size_t n_groups, size_t k_frames, size_t frame_stride,          \
+                                  int out_form, float scale, float* d_out, void* stream) {                                       \
+        READY;                                                                                                                    \
+        return exec_device_integrated(IO, p, d_iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale, d_out, stream); \
+    }                                                                                                                             \
+    int sdrk_exec_device_##SUFFIX##_timed_each(sdrk_plan* p, const void* d_iq, size_t n_groups, size_t k_frames,                  \
+                                               size_t frame_stride, int out_form, float scale, float* d_out, int launches,       \
+                                               float* each_ms) {                                                                  \
+        READY;                                                                                                                    \
+        return exec_device_integrated_timed_each(IO, p, d_iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale,  \
+                                                 d_out, launches, each_ms);                                                       \
+    }                                                                                                                             \
+    int sdrk_exec_host_##SUFFIX(sdrk_plan* p, const void* iq, size_t n_groups, size_t k_frames, size_t frame_stride,              \
+                                int out_form, float scale, float* out) {                                                         \
+        READY;                                                                                                                    \
+        return exec_host_integrated(IO, p, iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale, out);           \
+    }
+#define SDRK_PFB_READY                                                                                                            \
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st
+
+SDRK_SK_ENTRIES(sk, sk_c64_io(), (void)0)
+SDRK_SK_ENTRIES(sk_ci16, sk_ci16_io(), (void)0)
+SDRK_SK_ENTRIES(pfb_sk, sk_pfb_io(p), SDRK_PFB_READY)
+SDRK_SK_ENTRIES(pfb_sk_ci16, sk_pfb_ci16_io(p), SDRK_PFB_READY)
+#undef SDRK_PFB_READY
+#undef SDRK_SK_ENTRIES
 
 }  // extern "C"

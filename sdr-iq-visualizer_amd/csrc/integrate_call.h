@@ -2,6 +2,8 @@
 // integrate_api.hip: complex64 or int16 I,Q samples, plain frames or frames folded by the plan's polyphase filter bank.  An
 // IntIo says what differs between them, the way HostIo (plan_internal.h) does for exec_host: the bytes per input sample, the
 // launcher of the N = 4096 kernel that reduces inside the transform, and the plan's own transform for every other length.
+// The spectral-kurtosis calls (sdrk_exec_*_sk*) are the same call with other kernels behind it: an IntIo also names the
+// reduction down the columns of staged spectra, the finalize of split groups, and how many planes of nfft floats a group gives.
 //
 // N = 4096 runs the fused kernel on the caller's samples: one launch, plus a finalize when the groups are too few to fill the
 // device and were cut into slices (integrate_split.h).  Every other length (chirp-z included) runs "the plan's own transform
@@ -25,6 +27,13 @@ struct IntIo {
     LaunchFn transform = nullptr;                                  // every other length: the plan's transform (EPI_COMPLEX)
     size_t in_span = 0;                                            // input samples a frame reads from its start (0: nfft;
                                                                    // the filter bank: taps * nfft)
+    // the reduction over staged spectra and the finalize of split groups; planes of nfft float32 per output group; the fewest
+    // frames a group may have (spectral kurtosis: launch_sk_rows, launch_sk_finalize, 2 planes, 2 frames; no fused kernel
+    // behind the filter bank: N = 4096 then takes the staged route)
+    hipError_t (*rows)(const sdrk::IntegrateArgs&) = sdrk::launch_integrate_rows;
+    decltype(&sdrk::launch_integrate_finalize) finalize = sdrk::launch_integrate_finalize;
+    size_t planes = 1;
+    size_t min_k = 1;
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -37,6 +46,7 @@ struct IntCall {
     float scale = 1.0f;
     sdrk::IntSplit sp{1, 1};
     bool fused = false;          // the N = 4096 kernel of io.fused
+    size_t group_floats = 0;     // float32 per output group: io.planes * nfft
     size_t stage_frames = 0;     // generic route: frames per staging chunk
     unsigned launches = 0;       // reduction launches so far: picks the carry rows
     hipStream_t stream = nullptr;
@@ -60,6 +70,15 @@ inline int check_int_args(const sdrk_plan* p, const void* in, size_t n_groups, s
     return SDRK_OK;
 }
 
+// ... of a call through `io`: the detector is the caller's where the mode has one
+inline int check_call_args(const IntIo& io, const sdrk_plan* p, const void* in, size_t n_groups, size_t k, size_t stride, int detector,
+                           int out_form, const void* out) {
+    int st = check_int_args(p, in, n_groups, k, stride, detector, out_form, out);
+    if (st == SDRK_OK && k < io.min_k)
+        return fail(SDRK_ERR_INVALID, "k_frames must be >= %zu: the spectral-kurtosis estimator divides by k_frames - 1", io.min_k);
+    return st;
+}
+
 inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups, size_t k, size_t stride, int detector,
                       int out_form, float scale, hipStream_t stream) {
     c.p = p;
@@ -72,7 +91,8 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
     c.scale = scale;
     c.stream = stream;
     const size_t nfft = (size_t)p->nfft;
-    c.fused = p->nfft == 4096 && !p->blu_inner;
+    c.fused = p->nfft == 4096 && !p->blu_inner && io.fused != nullptr;
+    c.group_floats = io.planes * nfft;
     // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel
     const size_t ways = c.fused ? 1 : (nfft + 255) / 256;
     c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
@@ -94,7 +114,7 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
 }
 
 // The frames [f0, f1) of the call, d_in at frame f0's first sample.  Rows of the groups that end in the range go to
-// d_out + (group - out_row0) * nfft (unsplit calls only).
+// d_out + (group - out_row0) * group_floats (unsplit calls only).
 inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float* d_out, size_t out_row0) {
     sdrk_plan* p = c.p;
     sdrk::IntegrateArgs a;
@@ -136,7 +156,7 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
             if (st != SDRK_OK) return st;
             a.d_in = d_stage;
             a.in_stride = (size_t)p->nfft;
-            e = sdrk::launch_integrate_rows(a);
+            e = c.io.rows(a);
         }
         if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate kernel launch failed: %s", hipGetErrorString(e));
     }
@@ -146,8 +166,8 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
 // Split calls: every group's partial rows -> its row.
 inline int call_finalize(IntCall& c, float* d_out) {
     if (c.sp.slices == 1) return SDRK_OK;
-    const hipError_t e = sdrk::launch_integrate_finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector,
-                                                         c.out_form, c.scale, c.p->eps, d_out, c.p->num_cus, c.stream);
+    const hipError_t e = c.io.finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector,
+                                     c.out_form, c.scale, c.p->eps, d_out, c.p->num_cus, c.stream);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate finalize launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;
 }
@@ -170,7 +190,7 @@ inline int device_call(const IntIo& io, sdrk_plan* p, const void* d_iq, size_t n
 
 inline int exec_device_integrated(const IntIo& io, sdrk_plan* p, const void* d_iq, size_t n_groups, size_t k_frames,
                                   size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream) {
-    int st = check_int_args(p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, d_out);
+    int st = check_call_args(io, p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, d_out);
     if (st != SDRK_OK) return st;
     HIP_TRY(hipSetDevice(p->device));
     return device_call(io, p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
@@ -181,7 +201,7 @@ inline int exec_device_integrated_timed_each(const IntIo& io, sdrk_plan* p, cons
                                              size_t frame_stride, int detector, int out_form, float scale, float* d_out,
                                              int launches, float* each_ms) {
     if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
-    int st = check_int_args(p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, d_out);
+    int st = check_call_args(io, p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, d_out);
     if (st != SDRK_OK) return st;
     st = timed_each(p, launches, each_ms, [&] {
         return device_call(io, p, d_iq, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out, p->stream);
@@ -195,7 +215,7 @@ inline int exec_device_integrated_timed_each(const IntIo& io, sdrk_plan* p, cons
 // H2D of chunk c + 1 runs beside the transform of chunk c; a slot is reused once its chunk's rows have arrived.
 inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, size_t n_groups, size_t k_frames,
                                 size_t frame_stride, int detector, int out_form, float scale, float* out) {
-    int st = check_int_args(p, iq, n_groups, k_frames, frame_stride, detector, out_form, out);
+    int st = check_call_args(io, p, iq, n_groups, k_frames, frame_stride, detector, out_form, out);
     if (st != SDRK_OK) return st;
     HIP_TRY(hipSetDevice(p->device));
     st = ensure_copy_streams(p);
@@ -204,19 +224,20 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     st = call_begin(c, io, p, n_groups, k_frames, frame_stride, detector, out_form, scale, p->stream);
     if (st != SDRK_OK) return st;
     const size_t nfft = (size_t)p->nfft, K = k_frames, n_frames = n_groups * K, elem = io.in_elem;
+    const size_t group_bytes = c.group_floats * sizeof(float);
     const size_t span = io.in_span ? io.in_span : nfft;   // a chunk carries its span - nfft samples of overlap
     const bool direct = c.sp.slices == 1;   // rows leave per chunk; split calls finalize once at the end
     // frames per chunk: bounded by the input bytes and, through the rows a chunk can complete, by the output bytes
     size_t per = HOST_CHUNK_BYTES / (frame_stride * elem);
-    size_t rows_cap = HOST_CHUNK_BYTES / (nfft * sizeof(float));
+    size_t rows_cap = HOST_CHUNK_BYTES / group_bytes;
     if (rows_cap < 1) rows_cap = 1;
     if (per / K >= rows_cap) per = rows_cap * K;
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
     const size_t chunk_in = ((per - 1) * frame_stride + span) * elem;
-    const size_t chunk_out = direct ? (per / K + 1) * nfft * sizeof(float) : 0;
+    const size_t chunk_out = direct ? (per / K + 1) * group_bytes : 0;
     const size_t in_bytes = ((n_frames - 1) * frame_stride + span) * elem;
-    const size_t out_bytes = n_groups * nfft * sizeof(float);
+    const size_t out_bytes = n_groups * group_bytes;
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
     auto retire = [&](HostSlot& s) -> int {
         if (!s.busy) return SDRK_OK;
@@ -231,7 +252,7 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
         HostSlot& s = p->slot[n % HOST_SLOTS];
         const size_t f1 = n_frames - f0 < per ? n_frames : f0 + per;
         const size_t cin = ((f1 - f0 - 1) * frame_stride + span) * elem;
-        const size_t row0 = f0 / K, rows = direct ? f1 / K - row0 : 0, cout = rows * nfft * sizeof(float);
+        const size_t row0 = f0 / K, rows = direct ? f1 / K - row0 : 0, cout = rows * group_bytes;
         st = retire(s);
         if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);
         if (st != SDRK_OK) return bail(st);
@@ -242,7 +263,7 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
             if (st != SDRK_OK) return bail(st);
             e = hipEventRecord(s.ev_k, p->stream);
         }
-        float* user_rows = out + row0 * nfft;
+        float* user_rows = out + row0 * c.group_floats;
         if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
         if (e == hipSuccess && cout)
             e = hipMemcpyAsync(out_pinned ? static_cast<void*>(user_rows) : s.h_out, s.d_out, cout, hipMemcpyDeviceToHost, p->s_d2h);

@@ -33,6 +33,11 @@ sinc) weights ``T*nfft`` consecutive samples, the ``T`` blocks are summed into `
 rounded one by one as numpy does on float32 arrays) and that frame is transformed, so that the bins are nearly rectangular
 channels instead of a window's main lobe and side lobes.  float32 plans with the rectangular window only.
 
+``spectral_kurtosis*`` (plan methods and module functions) return, per group of ``k`` frames, the mean power AND the spectral
+kurtosis estimator ``SK = (k+1)/(k-1) * (k*S2/S1^2 - 1)`` of Nita & Gary from the sums ``S1`` of the power and ``S2`` of its
+square, both accumulated inside the transform: 1 for Gaussian noise at any level, towards 0 on a carrier, well above 1 on
+pulsed interference (``sk_limits`` gives the usual thresholds).  ``detector="sk"`` is not a detector: the calls are their own.
+
 All arithmetic on samples happens on the GPU through ``libsdrk.so``; nothing in
 this module computes a spectrum with numpy, and every entry point raises if the
 library or a device is missing.
@@ -164,6 +169,9 @@ class _Mode(NamedTuple):
     int_host: str               # one row per k frames: host arrays
     int_device: str             # ... device pointers
     int_timed_each: str         # ... timed launches
+    sk_host: str                # mean power and spectral kurtosis per k frames: host arrays
+    sk_device: str              # ... device pointers
+    sk_timed_each: str          # ... timed launches
 
     def stream(self, iq) -> np.ndarray:
         """One contiguous stream as the entry points read it: ``(n,)`` complex64, or checked ``(n, 2)`` int16."""
@@ -176,19 +184,24 @@ class _Integ(NamedTuple):
     detector: str
     out: str
     scale: float
+    sk: bool = False            # the spectral-kurtosis call: two planes per group, k >= 2, no detector argument
 
 
 _C64 = _Mode(False, False, "sdrk_exec_host", "sdrk_exec_fft_host", "sdrk_exec_device", "sdrk_exec_device_timed_each",
-             "sdrk_exec_host_integrated", "sdrk_exec_device_integrated", "sdrk_exec_device_integrated_timed_each")
+             "sdrk_exec_host_integrated", "sdrk_exec_device_integrated", "sdrk_exec_device_integrated_timed_each",
+             "sdrk_exec_host_sk", "sdrk_exec_device_sk", "sdrk_exec_device_sk_timed_each")
 _CI16 = _Mode(True, False, "sdrk_exec_host_ci16", "sdrk_exec_fft_host_ci16", "sdrk_exec_device_ci16",
               "sdrk_exec_device_ci16_timed_each", "sdrk_exec_host_integrated_ci16", "sdrk_exec_device_integrated_ci16",
-              "sdrk_exec_device_integrated_ci16_timed_each")
+              "sdrk_exec_device_integrated_ci16_timed_each",
+              "sdrk_exec_host_sk_ci16", "sdrk_exec_device_sk_ci16", "sdrk_exec_device_sk_ci16_timed_each")
 _PFB = _Mode(False, True, "sdrk_exec_host_pfb", "sdrk_exec_fft_host_pfb", "sdrk_exec_device_pfb",
              "sdrk_exec_device_pfb_timed_each", "sdrk_exec_host_pfb_integrated", "sdrk_exec_device_pfb_integrated",
-             "sdrk_exec_device_pfb_integrated_timed_each")
+             "sdrk_exec_device_pfb_integrated_timed_each",
+             "sdrk_exec_host_pfb_sk", "sdrk_exec_device_pfb_sk", "sdrk_exec_device_pfb_sk_timed_each")
 _PFB_CI16 = _Mode(True, True, "sdrk_exec_host_pfb_ci16", "sdrk_exec_fft_host_pfb_ci16", "sdrk_exec_device_pfb_ci16",
                   "sdrk_exec_device_pfb_ci16_timed_each", "sdrk_exec_host_pfb_integrated_ci16",
-                  "sdrk_exec_device_pfb_integrated_ci16", "sdrk_exec_device_pfb_integrated_ci16_timed_each")
+                  "sdrk_exec_device_pfb_integrated_ci16", "sdrk_exec_device_pfb_integrated_ci16_timed_each",
+                  "sdrk_exec_host_pfb_sk_ci16", "sdrk_exec_device_pfb_sk_ci16", "sdrk_exec_device_pfb_sk_ci16_timed_each")
 
 
 class SpectrumPlan:
@@ -367,10 +380,10 @@ class SpectrumPlan:
             raise ValueError("hop must be >= 1")
         return 0 if int(n_samples) < span else 1 + (int(n_samples) - span) // hop
 
-    def _n_groups(self, span: int, n_samples: int, k: int, hop: Optional[int]) -> int:
+    def _n_groups(self, span: int, n_samples: int, k: int, hop: Optional[int], min_k: int = 1) -> int:
         """Whole groups of ``k`` among those frames."""
-        if int(k) < 1:
-            raise ValueError("k must be >= 1")
+        if int(k) < min_k:
+            raise ValueError(f"k must be >= {min_k}")
         return self._n_frames(span, n_samples, hop) // int(k)
 
     def _host_rows(self, m: _Mode, iq, hop: Optional[int], out: Optional[np.ndarray] = None, *, spectra: bool = False,
@@ -387,17 +400,18 @@ class SpectrumPlan:
         return res
 
     def _host_integrated(self, m: _Mode, iq, hop: Optional[int], i: _Integ, *, what: str = "") -> np.ndarray:
-        """One float32 row per ``i.k`` frames of one contiguous stream, ``(groups, nfft)``."""
+        """One float32 row per ``i.k`` frames of one contiguous stream, ``(groups, nfft)``; the spectral-kurtosis call: two,
+        ``(groups, 2, nfft)``."""
         span = self._ready(m, what, integrated=True)
-        det, form = self._int_codes(i.detector, i.out)
+        codes = self._int_codes(i.detector, i.out, i.sk)
         x = m.stream(iq)
-        groups = self._n_groups(span, x.shape[0], i.k, hop)
-        res = np.empty((groups, self.nfft), dtype=np.float32)
+        groups = self._n_groups(span, x.shape[0], i.k, hop, 2 if i.sk else 1)
+        res = np.empty((groups, 2, self.nfft) if i.sk else (groups, self.nfft), dtype=np.float32)
         if groups:
             with self._lock:
-                check(getattr(lib(), m.int_host)(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups), c_size_t(int(i.k)),
-                                                 c_size_t(self.nfft if hop is None else int(hop)), det, form, c_float(i.scale),
-                                                 res.ctypes.data_as(c_void_p)))
+                check(getattr(lib(), m.sk_host if i.sk else m.int_host)(
+                    self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups), c_size_t(int(i.k)),
+                    c_size_t(self.nfft if hop is None else int(hop)), *codes, c_float(i.scale), res.ctypes.data_as(c_void_p)))
         return res
 
     def _device_args(self, m: _Mode, d_iq: int, n: int, d_out: int, frame_stride: Optional[int], i: Optional[_Integ],
@@ -408,25 +422,29 @@ class SpectrumPlan:
         stride = self.nfft if frame_stride is None else int(frame_stride)
         if i is None:
             return [c_void_p(d_iq), c_size_t(n), c_size_t(stride), c_void_p(d_out)]
-        det, form = self._int_codes(i.detector, i.out)
+        codes = self._int_codes(i.detector, i.out, i.sk)
         if int(i.k) < 1 or int(n) < 1:
             raise ValueError("k and n_groups must be >= 1")
+        if i.sk and int(i.k) < 2:
+            raise ValueError("k must be >= 2: the spectral-kurtosis estimator divides by k - 1")
         if stride < 1:
             raise ValueError("frame_stride must be >= 1")
-        return [c_void_p(d_iq), c_size_t(n), c_size_t(int(i.k)), c_size_t(stride), det, form, c_float(i.scale), c_void_p(d_out)]
+        return [c_void_p(d_iq), c_size_t(n), c_size_t(int(i.k)), c_size_t(stride), *codes, c_float(i.scale), c_void_p(d_out)]
 
     def _exec_device(self, m: _Mode, d_iq: int, n: int, d_out: int, frame_stride: Optional[int], stream: int,
                      i: Optional[_Integ] = None, *, what: str = "") -> None:
         args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
         with self._lock:
-            check(getattr(lib(), m.int_device if i else m.device)(self.handle, *args, c_void_p(stream) if stream else None))
+            fn = m.device if i is None else (m.sk_device if i.sk else m.int_device)
+            check(getattr(lib(), fn)(self.handle, *args, c_void_p(stream) if stream else None))
 
     def _exec_device_timed_each(self, m: _Mode, d_iq: int, n: int, d_out: int, launches: int, frame_stride: Optional[int],
                                 i: Optional[_Integ] = None, *, what: str = "") -> list:
         args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
         ms = (c_float * int(launches))()
         with self._lock:
-            check(getattr(lib(), m.int_timed_each if i else m.timed_each)(self.handle, *args, int(launches), ms))
+            fn = m.timed_each if i is None else (m.sk_timed_each if i.sk else m.int_timed_each)
+            check(getattr(lib(), fn)(self.handle, *args, int(launches), ms))
         return [float(v) for v in ms]
 
     # -- int16 I,Q input (float32 plans; same bits as the complex64 calls on the widened samples) --------------
@@ -502,11 +520,14 @@ class SpectrumPlan:
 
     # -- integrated spectra: one row per k frames (float32 plans) ---------------------------------------------
     @staticmethod
-    def _int_codes(detector: str, out: str):
-        if detector not in _ffi.DETECTORS:
-            raise ValueError(f"detector must be one of {sorted(_ffi.DETECTORS)}, got {detector!r}")
+    def _int_codes(detector: str, out: str, sk: bool = False):
+        """The C codes between the stride and the scale: (detector, out_form), or for a spectral-kurtosis call (out_form,)."""
         if out not in _ffi.INT_OUT_FORMS:
             raise ValueError(f"out must be one of {sorted(_ffi.INT_OUT_FORMS)}, got {out!r}")
+        if sk:
+            return (_ffi.INT_OUT_FORMS[out],)
+        if detector not in _ffi.DETECTORS:
+            raise ValueError(f"detector must be one of {sorted(_ffi.DETECTORS)}, got {detector!r}")
         return _ffi.DETECTORS[detector], _ffi.INT_OUT_FORMS[out]
 
     def integrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
@@ -679,6 +700,87 @@ class SpectrumPlan:
         """``exec_device_pfb_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
         return self._exec_device_timed_each(_PFB_CI16, d_iq, n_groups, d_out, launches, frame_stride,
                                             _Integ(k, detector, out, scale))
+
+    # -- spectral kurtosis: mean power and SK per k frames, both sums kept inside the transform (float32 plans) ----------
+    def _host_sk(self, m: _Mode, iq, k: int, hop: Optional[int], out: str, scale: float, what: str = ""):
+        planes = self._host_integrated(m, iq, hop, _Integ(k, "mean", out, scale, True), what=what)
+        return planes[:, 0], planes[:, 1]
+
+    def spectral_kurtosis(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``(mean_rows, sk_rows)``: two ``(groups, nfft)`` float32 views of one array, one row each per ``k >= 2``
+        consecutive frames of one contiguous stream (frames and groups as for ``integrate``).  ``mean_rows`` is the group's
+        mean power ``S1/k`` as ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``); ``sk_rows`` is
+        the spectral kurtosis estimator ``(k+1)/(k-1) * (k*S2/S1^2 - 1)`` with ``S1 = sum p``, ``S2 = sum p^2`` over the
+        group's ``p = |fft(w*x_f)|^2``: 1 for Gaussian noise, towards 0 on a carrier, well above 1 on pulsed interference;
+        0 on a bin without power.  The sums are plain float32 sums kept inside the transform: ``mean_rows`` is not the
+        compensated mean of ``integrate`` (relative error up to ``k * 2^-24`` on near-constant bins)."""
+        return self._host_sk(_C64, iq, k, hop, out, scale, "spectral_kurtosis")
+
+    def spectral_kurtosis_ci16(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``spectral_kurtosis`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: bit-identical to it on
+        ``float32(I) + 1j*float32(Q)``, from half the input bytes."""
+        return self._host_sk(_CI16, iq, k, hop, out, scale, "spectral_kurtosis_ci16")
+
+    def pfb_spectral_kurtosis(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``spectral_kurtosis`` of the polyphase-filter-bank frames of ``pfb_db`` (``set_pfb`` first; rectangular float32
+        plans): fold and transform per frame, the sums down the columns of the staged spectra at every nfft."""
+        return self._host_sk(_PFB, iq, k, hop, out, scale)
+
+    def pfb_spectral_kurtosis_ci16(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``pfb_spectral_kurtosis`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the
+        widened samples."""
+        return self._host_sk(_PFB_CI16, iq, k, hop, out, scale)
+
+    def _exec_device_sk(self, m: _Mode, what: str, d_iq: int, n_groups: int, k: int, d_out: int, frame_stride, out: str,
+                        scale: float, stream: int = 0, launches: Optional[int] = None):
+        i = _Integ(k, "mean", out, scale, True)
+        if launches is None:
+            return self._exec_device(m, d_iq, n_groups, d_out, frame_stride, stream, i, what=what)
+        return self._exec_device_timed_each(m, d_iq, n_groups, d_out, launches, frame_stride, i, what=what)
+
+    def exec_device_sk(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                       out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: complex64 in, ``n_groups * 2 * nfft`` float32 out (per group the mean-power row, then the SK
+        row), asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        self._exec_device_sk(_C64, "spectral_kurtosis", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream)
+
+    def exec_device_sk_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                  frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_sk`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_C64, "spectral_kurtosis", d_iq, n_groups, k, d_out, frame_stride, out, scale,
+                                    launches=launches)
+
+    def exec_device_sk_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                            out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_sk`` from int16 I,Q (4 bytes per sample, frame starts 4-byte aligned)."""
+        self._exec_device_sk(_CI16, "spectral_kurtosis_ci16", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream)
+
+    def exec_device_sk_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                       frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_sk_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_CI16, "spectral_kurtosis_ci16", d_iq, n_groups, k, d_out, frame_stride, out, scale,
+                                    launches=launches)
+
+    def exec_device_pfb_sk(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                           out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_sk`` behind the filter bank: the raw complex64 stream in
+        (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples)."""
+        self._exec_device_sk(_PFB, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream)
+
+    def exec_device_pfb_sk_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                      frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_pfb_sk`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_PFB, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, launches=launches)
+
+    def exec_device_pfb_sk_ci16(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                                out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_pfb_sk`` from the raw int16 I,Q stream (4 bytes per sample)."""
+        self._exec_device_sk(_PFB_CI16, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream)
+
+    def exec_device_pfb_sk_ci16_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                           frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_pfb_sk_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_PFB_CI16, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, launches=launches)
 
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
@@ -1033,6 +1135,46 @@ def pfb_integrated_db_ci16(iq, nfft: int, taps: int, k: int, hop: Optional[int] 
     """``pfb_integrated_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on the
     widened samples, from half the input bytes."""
     return _pfb_integrated_db(_PFB_CI16, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device)
+
+
+def sk_limits(k: int, sigmas: float = 3.0):
+    """``(lo, hi) = 1 -/+ sigmas * sqrt(4k^2 / ((k-1)(k+2)(k+3)))``: the band around 1 in which the spectral kurtosis of
+    Gaussian noise over ``k`` frames lies (its standard deviation, Nita & Gary); bins outside are flagged as interference."""
+    k = int(k)
+    if k < 2:
+        raise ValueError("k must be >= 2")
+    sd = float(np.sqrt(4.0 * k * k / ((k - 1.0) * (k + 2.0) * (k + 3.0))))
+    return 1.0 - float(sigmas) * sd, 1.0 + float(sigmas) * sd
+
+
+def spectral_kurtosis(iq, nfft: int, k: int, hop: Optional[int] = None, window: WindowArg = None, *, out: str = "db",
+                      scale: float = 1.0, eps: float = 1e-12, shift: bool = True, device: int = 0):
+    """``(mean_rows, sk_rows)`` per ``k >= 2`` frames of ``iq``: the mean power and the spectral kurtosis estimator per bin,
+    both accumulated on the device in one pass (``SpectrumPlan.spectral_kurtosis``)."""
+    return _cached_plan(int(nfft), window, eps, shift, device).spectral_kurtosis(iq, k, hop, out, scale)
+
+
+def spectral_kurtosis_ci16(iq, nfft: int, k: int, hop: Optional[int] = None, window: WindowArg = None, *, out: str = "db",
+                           scale: float = 1.0, eps: float = 1e-12, shift: bool = True, device: int = 0):
+    """``spectral_kurtosis`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
+    x = _as_ci16(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).spectral_kurtosis_ci16(x, k, hop, out, scale)
+
+
+def pfb_spectral_kurtosis(iq, nfft: int, taps: int, k: int, hop: Optional[int] = None, prototype=None, *, out: str = "db",
+                          scale: float = 1.0, eps: float = 1e-12, shift: bool = True, device: int = 0):
+    """``spectral_kurtosis`` of the polyphase-filter-bank frames of ``pfb_db`` (complex64, or int16 I,Q ``(n_samples, 2)``);
+    prototype and plan cache as for ``pfb_db``.  The arguments are checked before a plan is made for the prototype."""
+    ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
+    m = _PFB_CI16 if ci16 else _PFB
+    x = m.stream(iq) if ci16 else iq
+    if int(k) < 2:
+        raise ValueError("k must be >= 2")
+    if hop is not None and int(hop) < 1:
+        raise ValueError("hop must be >= 1")
+    SpectrumPlan._int_codes("mean", out, True)
+    plan = _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device)
+    return plan._host_sk(m, x, k, hop, out, scale)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

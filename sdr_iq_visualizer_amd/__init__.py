@@ -29,7 +29,11 @@ from .spectrum import (  # noqa: E402
     pfb_integrated_db,
     pfb_integrated_db_ci16,
     pfb_prototype,
+    pfb_spectral_kurtosis,
     process_frame,
+    sk_limits,
+    spectral_kurtosis,
+    spectral_kurtosis_ci16,
     spectrum_db,
     spectrum_db_ci16,
     stft_db,
@@ -61,9 +65,13 @@ __all__ = [
     "pfb_integrated_db",
     "pfb_integrated_db_ci16",
     "pfb_prototype",
+    "pfb_spectral_kurtosis",
     "pinned_empty",
     "process_frame",
     "registered",
+    "sk_limits",
+    "spectral_kurtosis",
+    "spectral_kurtosis_ci16",
     "spectrum_db",
     "spectrum_db_ci16",
     "stft_db",
