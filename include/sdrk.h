@@ -470,6 +470,56 @@ int sdrk_exec_device_pfb_sk_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci
 int sdrk_exec_host_pfb_sk_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                int out_form, float scale, float* out);
 
+/* ---- two-channel cross-spectra: auto and cross power over K frames in one pass ----------
+ * What two coherent receive channels give that one cannot: the cross term, and from it coherence (a common signal under
+ * uncorrelated receiver noise) and the phase difference per bin (delay, direction, interferometry).
+ * Input: a stream of ELEMENTS.  Element n holds sample n of channel 0, then sample n of channel 1 — what a 2 x 2 front end
+ * delivers with both receive channels enabled, and what SigMF stores for core:num_channels = 2.  complex64 form: 4 float32
+ * I0 Q0 I1 Q1, 16 bytes.  int16 form (_ci16): 4 little-endian int16, 8 bytes, x = float32(I) + i*float32(Q) exactly.  The
+ * pointer is aligned to an element.  Frame f starts at ELEMENT f*frame_stride (any stride >= 1) and covers nfft elements;
+ * group g is the frames [g*k_frames, (g+1)*k_frames); the buffer holds (n_groups*k_frames - 1)*frame_stride + nfft elements.
+ * Sums: with A_f = fft(w*x0_f), B_f = fft(w*x1_f) (the plan's window, twiddles and shift order), A = (ar, ai), B = (br, bi)
+ * per bin,
+ *     paa = fmaf(ar, ar, ai*ai)      pbb = fmaf(br, br, bi*bi)          (as the integrating kernels form p)
+ *     cre = (ar*br) + (ai*bi)        cim = (ai*br) - (ar*bi)            (A * conj(B); every product rounded to float32 first)
+ * Saa, Sbb, Sre, Sim are plain float32 running sums of these in frame order.  No floating-point atomics.  A group that was cut
+ * into slices (few groups on a large device) has its slices' sums added in slice order in float64 and rounded to float32 once.
+ * Output: per group FOUR planes of nfft float32, d_out[n_groups][4][nfft], in the plan's shift order:
+ *     scale*Saa/K     scale*Sbb/K     scale*Sre/K     scale*Sim/K
+ * each formed as SDRK_INT_OUT_POWER forms its row from the mean.  There is no dB form and no out_form argument; the plan's eps
+ * is not used.  With the same scale and k_frames >= 2, planes 0 and 1 carry the bits of plane 0 of sdrk_exec_device_sk
+ * (SDRK_INT_OUT_POWER) on the de-interleaved channel, at every nfft.  Like that plane they are NOT the compensated mean of
+ * SDRK_DET_MEAN.
+ * Because the products are rounded on their own, swapping the channels returns the exact conjugate: planes 0 and 1 exchanged,
+ * plane 2 with the same bits, plane 3 negated (as values: a zero's sign may differ).  Two identical channels give plane 3 = 0.
+ * Determinism: the same input gives the same bits, from the device entry and the host entry alike, however the host call is
+ * chunked.  The int16 forms return the bits of the complex64 forms on the widened elements.
+ * Every float32 plan is served at every nfft, chirp-z lengths included, with the plan's window.  A prototype set with
+ * sdrk_plan_set_pfb is ignored.  k_frames = 1 is allowed.
+ * Refusals, each SDRK_ERR_INVALID with a message: an f64 plan, n_groups = 0 or k_frames = 0 or their product out of range,
+ * frame_stride = 0, NULL pointers.  A plan that has refused still works.
+ * N = 4096 transforms both channels of a frame in one kernel and keeps the four sums in its registers: 16 + 16/K bytes per
+ * element through device memory from complex64, 8 + 16/K from int16.  Other lengths de-interleave chunks of frames, run the
+ * plan's transform once per channel and reduce both spectra, in plan-owned staging of at most 64 MiB of spectra and 64 MiB of
+ * split samples however long the stream is.
+ * Not provided: filter-bank forms, double precision, more than two channels, waterfall appends. */
+/* device in / device out (d_out: n_groups * 4 * nfft float32), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_xspec(sdrk_plan* plan, const void* d_iq2_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
+                           float scale, float* d_out, void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` calls (bench harness) */
+int sdrk_exec_device_xspec_timed_each(sdrk_plan* plan, const void* d_iq2_c64, size_t n_groups, size_t k_frames,
+                                      size_t frame_stride, float scale, float* d_out, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked through pinned staging */
+int sdrk_exec_host_xspec(sdrk_plan* plan, const void* iq2_c64, size_t n_groups, size_t k_frames, size_t frame_stride, float scale,
+                         float* out);
+/* the same three from int16 elements (8 bytes per element) */
+int sdrk_exec_device_xspec_ci16(sdrk_plan* plan, const void* d_iq2_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                                float scale, float* d_out, void* stream);
+int sdrk_exec_device_xspec_ci16_timed_each(sdrk_plan* plan, const void* d_iq2_ci16, size_t n_groups, size_t k_frames,
+                                           size_t frame_stride, float scale, float* d_out, int launches, float* each_ms);
+int sdrk_exec_host_xspec_ci16(sdrk_plan* plan, const void* iq2_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
+                              float scale, float* out);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

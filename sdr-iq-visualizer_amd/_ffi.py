@@ -190,6 +190,13 @@ SYMBOLS = [
     ("sdrk_exec_device_pfb_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
     ("sdrk_exec_device_pfb_sk_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_pfb_sk_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    # two-channel cross-spectra: per group four planes from elements I0 Q0 I1 Q1 (no detector, no out_form)
+    ("sdrk_exec_device_xspec", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_xspec_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_xspec", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
+    ("sdrk_exec_device_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_xspec_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
 ]
 
 _lib = None

@@ -1,6 +1,6 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
-    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk]] [--pfb T] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross]] [--pfb T] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
@@ -37,6 +37,11 @@ def main(argv=None) -> int:
                    help="with --integrate K (K >= 2): also write the spectral kurtosis per bin and group (array sk) and the mean "
                         "power it was formed beside (sk_mean_db), behind the filter bank with --pfb T; the report counts the "
                         "bins outside the 3-sigma band of Gaussian noise")
+    p.add_argument("--cross", action="store_true",
+                   help="with --integrate K, on a two-channel cf32_le or ci16_le recording (core:num_channels = 2): also write "
+                        "the auto and cross power of the two channels per K frames (arrays cross_paa, cross_pbb, cross, coherence, "
+                        "phase); the report has the peak-coherence bin, its phase and the median coherence.  The other rows are "
+                        "then channel 0's")
     p.add_argument("--pfb", type=_positive, default=0, metavar="T",
                    help="also write polyphase-filter-bank dB rows: T blocks of --nfft samples folded under the default "
                         "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db); with --integrate K also one "
@@ -54,6 +59,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.cmd == "psd" and args.sk and args.integrate < 2:
         ap.error("--sk needs --integrate K with K >= 2")
+    if args.cmd == "psd" and args.cross and args.integrate < 1:
+        ap.error("--cross needs --integrate K")
 
     from . import sigmf_io, synth
     if args.cmd == "synth":
@@ -67,6 +74,17 @@ def main(argv=None) -> int:
     # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
     # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
     samples, meta = sigmf_io.read_sigmf(args.path, native=True)
+    pair = None
+    if args.cross:   # both channels as they are stored (element n: sample n of channel 0, then of channel 1); the rest: channel 0
+        g = meta.get("global", {})
+        if int(g.get("core:num_channels", 1)) != 2 or g.get("core:datatype", "cf32_le") not in ("cf32_le", "ci16_le") \
+                or args.path.endswith(".zip"):
+            print(f"--cross needs a two-channel cf32_le or ci16_le recording (core:num_channels = 2, not zipped); this one has "
+                  f"core:num_channels = {g.get('core:num_channels', 1)}, core:datatype = {g.get('core:datatype', 'cf32_le')!r}",
+                  file=sys.stderr)
+            return 2
+        pair, _ = sigmf_io.read_sigmf_channels(args.path)
+        samples = np.ascontiguousarray(pair[:, 0])
     raw16 = samples if samples.dtype == np.int16 else None
     n_samples = int(samples.shape[0])
     if n_samples < args.nfft:
@@ -138,9 +156,26 @@ def main(argv=None) -> int:
         report["sk_rows"] = int(sk.shape[0])
         report["sk_limits"] = [lo, hi]
         report["sk_flagged_fraction"] = float(np.mean((sk < lo) | (sk > hi))) if sk.size else 0.0
+    if pair is not None:
+        plan = spectrum._cached_plan(args.nfft, args.window, 1e-12, True, args.device)
+        xs = (plan.cross_spectrum_ci16 if pair.dtype == np.int16 else plan.cross_spectrum)(pair, args.integrate)
+        coh, phase = xs.coherence, xs.phase
+        results.update(cross_paa=xs.paa, cross_pbb=xs.pbb, cross=xs.cross, coherence=coh, phase=phase)
+        report["cross_rows"] = int(coh.shape[0])
+        if coh.size:
+            g, b = np.unravel_index(int(np.argmax(coh)), coh.shape)
+            report["cross_peak_coherence"] = float(coh[g, b])
+            report["cross_peak_row"] = int(g)
+            report["cross_peak_freq_hz"] = float(freqs[b])
+            report["cross_peak_phase_rad"] = float(phase[g, b])
+            report["cross_median_coherence"] = float(np.median(coh))
+        else:
+            print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no cross-spectrum row", file=sys.stderr)
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out
+    if args.cross:
+        report["wrote"] = [args.out] if args.out else []
     print(json.dumps(report))
     return 0
 

@@ -17,6 +17,12 @@
 // kernels_sk.h behind it: per group two planes, the mean power and the estimator from S1 = sum p and S2 = sum p^2.  N = 4096
 // keeps the sums inside the transform (sk4096.hip); every other length, and the filter bank at every length (N = 4096 too: fold
 // and transform through launch_pfb / launch_pfb_ci16, no folding SK kernel), reduces staged spectra with sk_rows.hip.
+//
+// The two-channel cross-spectrum entry points (sdrk_exec_*_xspec, _xspec_ci16) are the same call on a stream of elements (sample
+// n of channel 0, then of channel 1: 16 bytes from complex64, 8 from int16) with the kernels of kernels_xspec.h behind it: per
+// group four planes from four sums per bin.  N = 4096 transforms both channels inside one kernel (xspec4096.hip); every other
+// length de-interleaves, runs the plan's transform once per channel and reduces both staged spectra (xspec_rows.hip).  The
+// interleaved layout is what lets the chunking of exec_host_integrated serve as it is: a chunk of elements holds both channels.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -27,6 +33,7 @@
 #include "kernels_kgroup_ci16.h"
 #include "kernels_pfb.h"
 #include "kernels_sk.h"
+#include "kernels_xspec.h"
 #include "plan_internal.h"
 
 using namespace sdrk_host;
@@ -63,6 +70,20 @@ IntIo sk_c64_io() { return sk_io(c64_io(), sdrk::launch_sk4096); }
 IntIo sk_ci16_io() { return sk_io(ci16_io(), sdrk::launch_sk4096_i16); }
 IntIo sk_pfb_io(const sdrk_plan* p) { return sk_io(pfb_io(p), nullptr); }
 IntIo sk_pfb_ci16_io(const sdrk_plan* p) { return sk_io(pfb_ci16_io(p), nullptr); }
+
+// two-channel cross-spectra: elements of 16 (complex64) or 8 (int16) bytes; always through the plan's plain complex64 transform
+IntIo xspec_io(size_t in_elem, FusedFn fused) {
+    IntIo io = int_io(in_elem, fused, launch_f32);
+    io.rows = nullptr;
+    io.rows2 = sdrk::launch_xspec_rows;
+    io.finalize = sdrk::launch_xspec_finalize;
+    io.planes = 4;
+    io.state = 4;
+    return io;
+}
+
+IntIo xspec_c64_io() { return xspec_io(2 * sizeof(float2), sdrk::launch_xspec4096); }
+IntIo xspec_ci16_io() { return xspec_io(8, sdrk::launch_xspec4096_i16); }
 
 }  // namespace
 
@@ -171,5 +192,27 @@ SDRK_SK_ENTRIES(pfb_sk, sk_pfb_io(p), SDRK_PFB_READY)
 SDRK_SK_ENTRIES(pfb_sk_ci16, sk_pfb_ci16_io(p), SDRK_PFB_READY)
 #undef SDRK_PFB_READY
 #undef SDRK_SK_ENTRIES
+
+// ---- two-channel cross-spectra: four planes per group, always the scaled-power form (detector and out_form are not read) ----
+
+#define SDRK_XSPEC_ENTRIES(SUFFIX, IO)                                                                                             \
+    int sdrk_exec_device_##SUFFIX(sdrk_plan* p, const void* d_iq2, size_t n_groups, size_t k_frames, size_t frame_stride,         \
+                                  float scale, float* d_out, void* stream) {                                                      \
+        return exec_device_integrated(IO, p, d_iq2, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, SDRK_INT_OUT_POWER, scale,   \
+                                      d_out, stream);                                                                             \
+    }                                                                                                                             \
+    int sdrk_exec_device_##SUFFIX##_timed_each(sdrk_plan* p, const void* d_iq2, size_t n_groups, size_t k_frames,                 \
+                                               size_t frame_stride, float scale, float* d_out, int launches, float* each_ms) {   \
+        return exec_device_integrated_timed_each(IO, p, d_iq2, n_groups, k_frames, frame_stride, SDRK_DET_MEAN,                   \
+                                                 SDRK_INT_OUT_POWER, scale, d_out, launches, each_ms);                            \
+    }                                                                                                                             \
+    int sdrk_exec_host_##SUFFIX(sdrk_plan* p, const void* iq2, size_t n_groups, size_t k_frames, size_t frame_stride,             \
+                                float scale, float* out) {                                                                        \
+        return exec_host_integrated(IO, p, iq2, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, SDRK_INT_OUT_POWER, scale, out); \
+    }
+
+SDRK_XSPEC_ENTRIES(xspec, xspec_c64_io())
+SDRK_XSPEC_ENTRIES(xspec_ci16, xspec_ci16_io())
+#undef SDRK_XSPEC_ENTRIES
 
 }  // extern "C"

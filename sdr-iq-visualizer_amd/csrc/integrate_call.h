@@ -4,6 +4,9 @@
 // launcher of the N = 4096 kernel that reduces inside the transform, and the plan's own transform for every other length.
 // The spectral-kurtosis calls (sdrk_exec_*_sk*) are the same call with other kernels behind it: an IntIo also names the
 // reduction down the columns of staged spectra, the finalize of split groups, and how many planes of nfft floats a group gives.
+// The two-channel cross-spectrum calls (sdrk_exec_*_xspec*) are the same call once more: their input is a stream of elements
+// (both channels' sample n side by side), their unit state is four floats per bin, and their staged route de-interleaves a chunk
+// of frames (kernels_xspec.h) and runs the plan's transform once per channel before the column kernel takes both spectra.
 //
 // N = 4096 runs the fused kernel on the caller's samples: one launch, plus a finalize when the groups are too few to fill the
 // device and were cut into slices (integrate_split.h).  Every other length (chirp-z included) runs "the plan's own transform
@@ -17,6 +20,7 @@
 
 #include "host_pool.h"
 #include "kernels_integrate.h"
+#include "kernels_xspec.h"
 #include "plan_internal.h"
 
 namespace sdrk_host {
@@ -34,6 +38,12 @@ struct IntIo {
     decltype(&sdrk::launch_integrate_finalize) finalize = sdrk::launch_integrate_finalize;
     size_t planes = 1;
     size_t min_k = 1;
+    // floats of unit state per bin: the size of the carry rows and the partial rows (cross-spectra: 4)
+    size_t state = 2;
+    // two-channel element input (in_elem 16: complex64, 8: int16): the column kernel over both channels' staged spectra; the
+    // staged route then splits each chunk's frames into packed complex64 frames per channel first, at most INT_STAGE_BYTES of
+    // them beside at most INT_STAGE_BYTES of spectra, and `rows` is not used
+    hipError_t (*rows2)(const sdrk::IntegrateArgs&, const float2*) = nullptr;
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -96,20 +106,23 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
     // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel
     const size_t ways = c.fused ? 1 : (nfft + 255) / 256;
     c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
-    const size_t row = nfft * sizeof(float2);
+    const size_t row = nfft * sizeof(float2);              // a staged spectrum
+    const size_t state_row = nfft * io.state * sizeof(float);
     const size_t n_partials = c.sp.slices > 1 ? n_groups * c.sp.slices : 0;
     Staging& sg = p->integ;   // buf[0]: carry and partial rows; buf[1]: spectra of the generic route
-    int st = sg.reserve(0, (2 + n_partials) * row);
+    int st = sg.reserve(0, (2 + n_partials) * state_row);
     if (st != SDRK_OK) return st;
     if (!c.fused) {
-        c.stage_frames = INT_STAGE_BYTES / row ? INT_STAGE_BYTES / row : 1;
+        // (two channels: both spectra of a frame share the 64 MiB, and the split frames take as much again behind them)
+        const size_t per_frame = io.rows2 ? 2 * row : row;
+        c.stage_frames = INT_STAGE_BYTES / per_frame ? INT_STAGE_BYTES / per_frame : 1;
         if (c.stage_frames > n_groups * k) c.stage_frames = n_groups * k;
-        st = sg.reserve(1, c.stage_frames * row);
+        st = sg.reserve(1, c.stage_frames * (io.rows2 ? 4 * row : row));
         if (st != SDRK_OK) return st;
     }
     c.carry[0] = static_cast<float2*>(sg.buf[0].d);
-    c.carry[1] = c.carry[0] + nfft;
-    c.partials = c.carry[1] + nfft;
+    c.carry[1] = c.carry[0] + nfft * io.state / 2;
+    c.partials = c.carry[1] + nfft * io.state / 2;
     return sg.enter(stream);   // one state and one staging per plan: a call on another stream waits for the last one's work
 }
 
@@ -150,6 +163,18 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
             a.d_in = src;
             a.in_stride = c.stride;
             e = c.io.fused(a);
+        } else if (c.io.rows2) {   // [spectra 0][spectra 1][frames 0][frames 1], stage_frames frames each
+            const size_t n = s1 - s0, plane = c.stage_frames * (size_t)p->nfft;
+            float2* const spec0 = static_cast<float2*>(p->integ.buf[1].d);
+            float2 *const spec1 = spec0 + plane, *const x0 = spec1 + plane, *const x1 = x0 + plane;
+            e = sdrk::launch_xspec_split(src, c.io.in_elem == 8, n, c.stride, p->nfft, x0, x1, p->num_cus, c.stream);
+            if (e != hipSuccess) return fail(SDRK_ERR_HIP, "cross-spectrum split launch failed: %s", hipGetErrorString(e));
+            int st = c.io.transform(p, x0, n, (size_t)p->nfft, spec0, sdrk::EPI_COMPLEX, c.stream);
+            if (st == SDRK_OK) st = c.io.transform(p, x1, n, (size_t)p->nfft, spec1, sdrk::EPI_COMPLEX, c.stream);
+            if (st != SDRK_OK) return st;
+            a.d_in = spec0;
+            a.in_stride = (size_t)p->nfft;
+            e = c.io.rows2(a, spec1);
         } else {
             void* const d_stage = p->integ.buf[1].d;
             int st = c.io.transform(p, src, s1 - s0, c.stride, d_stage, sdrk::EPI_COMPLEX, c.stream);

@@ -10,6 +10,10 @@ zipped together with a README.  The reference's offline reader
 (scripts/process_sigmf_data.py:20-62) goes through the ``sigmf`` package, which is not a
 dependency here: the format is simple enough to read directly.  File I/O only — no
 signal processing in this module.
+
+Multi-channel recordings (``core:num_channels = C``, the channels' samples interleaved per sample instant, as a 2 x 2 front
+end delivers them): ``write_sigmf(..., num_channels=C)`` and ``read_sigmf_channels`` -> ``(n, C)``.  ``read_sigmf`` itself
+reads the data file as one stream whatever the channel count says.
 """
 from __future__ import annotations
 
@@ -28,10 +32,10 @@ _DTYPES = {"cf32_le": np.dtype("<c8"), "cf64_le": np.dtype("<c16"),
 
 def make_metadata(sample_rate: float, center_freq: float, *, description: str = "IQ recording",
                   author: str = "sdr_iq_visualizer_amd", hw: str = "", when: Optional[datetime] = None,
-                  datatype: str = "cf32_le") -> dict:
-    """Metadata dict with the keys of app/dashboard/callbacks.py:285-304."""
+                  datatype: str = "cf32_le", num_channels: int = 1) -> dict:
+    """Metadata dict with the keys of app/dashboard/callbacks.py:285-304 (and ``core:num_channels`` where it is not 1)."""
     when = when or datetime.now(timezone.utc)
-    return {
+    meta = {
         "global": {
             "core:datatype": datatype,
             "core:sample_rate": int(sample_rate),
@@ -48,6 +52,9 @@ def make_metadata(sample_rate: float, center_freq: float, *, description: str = 
         }],
         "annotations": [],
     }
+    if int(num_channels) != 1:
+        meta["global"]["core:num_channels"] = int(num_channels)
+    return meta
 
 
 def _to_ci16(samples) -> np.ndarray:
@@ -64,11 +71,23 @@ def _to_ci16(samples) -> np.ndarray:
 
 
 def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float, datatype: str = "cf32_le",
-                **meta_kw) -> Tuple[str, str]:
+                num_channels: int = 1, **meta_kw) -> Tuple[str, str]:
     """Write ``<base>.sigmf-data`` (cf32_le, or ci16_le on request: interleaved int16 I,Q from an int16 ``(n, 2)`` array or
-    from integer-valued complex samples) and ``<base>.sigmf-meta``; returns both paths."""
+    from integer-valued complex samples) and ``<base>.sigmf-meta``; returns both paths.
+    ``num_channels=C`` (> 1): ``samples`` is ``(n, C)`` complex (or ``(n, C, 2)`` int16), stored with the channels
+    interleaved per sample instant and ``core:num_channels = C`` in the metadata."""
     if datatype not in ("cf32_le", "ci16_le"):
         raise ValueError(f"write_sigmf writes 'cf32_le' or 'ci16_le', not {datatype!r}")
+    num_channels = int(num_channels)
+    if num_channels < 1:
+        raise ValueError("num_channels must be >= 1")
+    if num_channels > 1:
+        shape = np.shape(samples)
+        int16 = getattr(samples, "dtype", None) == np.int16
+        if len(shape) != (3 if int16 else 2) or shape[1] != num_channels:
+            raise ValueError(f"num_channels={num_channels} needs samples of shape (n, {num_channels})"
+                             f"{' (or (n, C, 2) int16)' if int16 else ''}, got {shape}")
+        meta_kw["num_channels"] = num_channels   # (C-order flattening below interleaves the channels)
     data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
     if datatype == "ci16_le":
         _to_ci16(samples).tofile(data_path)
@@ -128,6 +147,38 @@ def read_sigmf(path: str, max_samples: Optional[int] = None, native: bool = Fals
     out = dict(meta)
     out["sample_rate"] = float(g.get("core:sample_rate", 1.0))
     out["center_freq"] = float(caps[0].get("core:frequency", 0.0))
+    return samples, out
+
+
+def read_sigmf_channels(path: str) -> Tuple[np.ndarray, dict]:
+    """Read a recording (``.sigmf-meta``, ``.sigmf-data`` or base name) honouring ``core:num_channels = C`` (default 1):
+    ``(samples, meta)`` with the samples in their own format and the channels de-interleaved by a reshape, not a copy —
+    ``(n, C)`` complex64 for ``cf32_le``, ``(n, C, 2)`` int16 for ``ci16_le``; a trailing partial sample instant is dropped.
+    ``meta`` as from ``read_sigmf``, plus ``meta['num_channels']``."""
+    base = path
+    for ext in (".sigmf-meta", ".sigmf-data"):
+        if base.endswith(ext):
+            base = base[: -len(ext)]
+    with open(base + ".sigmf-meta") as fh:
+        meta = json.load(fh)
+    g = meta.get("global", {})
+    datatype, nch = g.get("core:datatype", "cf32_le"), int(g.get("core:num_channels", 1))
+    if datatype not in ("cf32_le", "ci16_le"):
+        raise ValueError(f"read_sigmf_channels reads 'cf32_le' or 'ci16_le', not {datatype!r}")
+    if nch < 1:
+        raise ValueError(f"core:num_channels is {nch}")
+    per = nch if datatype == "cf32_le" else 2 * nch          # values of the file's dtype per sample instant
+    a = np.fromfile(base + ".sigmf-data", dtype=_DTYPES[datatype])
+    a = a[: a.size // per * per]
+    if datatype == "cf32_le":
+        samples = a.reshape(-1, nch).astype(np.complex64, copy=False)
+    else:
+        samples = a.reshape(-1, nch, 2).astype(np.int16, copy=False)
+    caps = meta.get("captures") or [{}]
+    out = dict(meta)
+    out["sample_rate"] = float(g.get("core:sample_rate", 1.0))
+    out["center_freq"] = float(caps[0].get("core:frequency", 0.0))
+    out["num_channels"] = nch
     return samples, out
 
 

@@ -130,6 +130,70 @@ def _as_ci16(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
     return a
 
 
+def _as_iq2_c64(iq2) -> np.ndarray:
+    """Two-channel complex64 elements ``(n, 2)``, C-contiguous (a view where ``iq2`` already is that).  A pair ``(a, b)`` of
+    equal-length 1-D arrays is stacked into one: that is a copy of both."""
+    if isinstance(iq2, (tuple, list)) and len(iq2) == 2:
+        a, b = (np.asarray(c) for c in iq2)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError(f"a channel pair must be two 1-D arrays of equal length, got shapes {a.shape} and {b.shape}")
+        return np.stack([a.astype(np.complex64, copy=False), b.astype(np.complex64, copy=False)], axis=1)
+    x = np.asarray(iq2)
+    if x.ndim != 2 or x.shape[1] != 2 or not np.issubdtype(x.dtype, np.complexfloating):
+        raise ValueError(f"two-channel input must be a complex (n, 2) array or a pair (a, b), got shape {x.shape} {x.dtype}")
+    return _as_c64(x)
+
+
+def _as_iq2_ci16(iq2) -> np.ndarray:
+    """Two-channel int16 elements ``(n, 2, 2)`` (channel, then I,Q) or ``(n, 4)``: checked, never converted.  A pair
+    ``(a, b)`` of ``(n, 2)`` int16 arrays of equal length is stacked into one: that is a copy of both."""
+    if isinstance(iq2, (tuple, list)) and len(iq2) == 2:
+        a, b = (np.asarray(c) for c in iq2)
+        if a.dtype != np.int16 or b.dtype != np.int16 or a.ndim != 2 or a.shape[1] != 2 or a.shape != b.shape:
+            raise ValueError(f"a channel pair must be two (n, 2) int16 arrays of equal length, got {a.shape} {a.dtype} and "
+                             f"{b.shape} {b.dtype}")
+        return np.stack([a, b], axis=1)
+    if not isinstance(iq2, np.ndarray) or iq2.dtype != np.int16:
+        raise ValueError(f"two-channel ci16 input must be a numpy int16 array, got {getattr(iq2, 'dtype', type(iq2).__name__)}")
+    if not ((iq2.ndim == 3 and iq2.shape[1:] == (2, 2)) or (iq2.ndim == 2 and iq2.shape[1] == 4)):
+        raise ValueError(f"two-channel ci16 input must have shape (n, 2, 2) or (n, 4) (I0 Q0 I1 Q1), got {iq2.shape}")
+    if not iq2.flags.c_contiguous:
+        raise ValueError("two-channel ci16 input must be C-contiguous (interleaved I0 Q0 I1 Q1)")
+    return iq2
+
+
+class CrossSpectrum(NamedTuple):
+    """What ``SpectrumPlan.cross_spectrum`` returns: four ``(groups, nfft)`` float32 views of one array, per group of ``k``
+    frames and bin ``scale/k`` times the sums of ``|A|^2``, ``|B|^2``, ``Re(A conj B)`` and ``Im(A conj B)``."""
+    paa: np.ndarray
+    pbb: np.ndarray
+    cre: np.ndarray
+    cim: np.ndarray
+
+    @property
+    def cross(self) -> np.ndarray:
+        """The averaged cross-spectrum ``<A conj(B)>`` as complex64 (a new array)."""
+        c = np.empty(self.cre.shape, dtype=np.complex64)
+        c.real, c.imag = self.cre, self.cim
+        return c
+
+    @property
+    def coherence(self) -> np.ndarray:
+        """Magnitude-squared coherence ``|C|^2 / (Paa * Pbb)`` in float64: 1 where the channels carry one signal, about
+        ``1/k`` on independent noise.  0 where the denominator is 0 (a dead bin), never NaN."""
+        cre, cim = self.cre.astype(np.float64), self.cim.astype(np.float64)
+        den = self.paa.astype(np.float64) * self.pbb.astype(np.float64)
+        ok = np.isfinite(den) & (den > 0)
+        coh = np.zeros(den.shape, dtype=np.float64)
+        np.divide(cre * cre + cim * cim, den, out=coh, where=ok)
+        return np.where(np.isfinite(coh), coh, 0.0)
+
+    @property
+    def phase(self) -> np.ndarray:
+        """The phase of the cross-spectrum in radians, ``atan2(cim, cre)`` in float64: channel 0's phase minus channel 1's."""
+        return np.arctan2(self.cim.astype(np.float64), self.cre.astype(np.float64))
+
+
 PFB_MAX_TAPS = 32                 # sdrk.h: taps of a prototype filter
 
 
@@ -782,6 +846,75 @@ class SpectrumPlan:
         """``exec_device_pfb_sk_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
         return self._exec_device_sk(_PFB_CI16, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, launches=launches)
 
+    # -- two-channel cross-spectra: auto and cross power per k frames, four sums kept inside the transform (float32 plans) --
+    def _host_xspec(self, x: np.ndarray, ci16: bool, k: int, hop: Optional[int], scale: float, what: str) -> CrossSpectrum:
+        self._float32_only(what)
+        groups = self._n_groups(self.nfft, x.shape[0], k, hop)
+        res = np.empty((groups, 4, self.nfft), dtype=np.float32)
+        if groups:
+            fn = getattr(lib(), "sdrk_exec_host_xspec_ci16" if ci16 else "sdrk_exec_host_xspec")
+            with self._lock:
+                check(fn(self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups), c_size_t(int(k)),
+                         c_size_t(self.nfft if hop is None else int(hop)), c_float(scale), res.ctypes.data_as(c_void_p)))
+        return CrossSpectrum(res[:, 0], res[:, 1], res[:, 2], res[:, 3])
+
+    def cross_spectrum(self, iq2, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CrossSpectrum:
+        """Auto and cross power of two coherent channels per ``k >= 1`` consecutive frames of one contiguous two-channel
+        stream: a ``CrossSpectrum`` of four ``(groups, nfft)`` float32 views of one array, ``scale/k`` times the sums over
+        the group of ``|A|^2``, ``|B|^2``, ``Re(A conj B)``, ``Im(A conj B)`` with ``A = fft(w*x0_f)``, ``B = fft(w*x1_f)``;
+        its ``.cross``, ``.coherence`` and ``.phase`` derive the rest.  ``iq2`` is an ``(n, 2)`` complex array (element ``n``
+        = sample ``n`` of channel 0, then of channel 1: used as it is when complex64 and C-contiguous) or a pair ``(a, b)``
+        of equal-length arrays, which is stacked first — a copy of both.  Frames start every ``hop`` elements (default
+        ``nfft``).  The sums are plain float32 sums kept inside the transform, as for ``spectral_kurtosis``."""
+        return self._host_xspec(_as_iq2_c64(iq2), False, k, hop, scale, "cross_spectrum")
+
+    def cross_spectrum_ci16(self, iq2, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CrossSpectrum:
+        """``cross_spectrum`` over int16 elements, ``(n, 2, 2)`` or ``(n, 4)`` int16 (``I0 Q0 I1 Q1``; or a pair of
+        ``(n, 2)`` int16 arrays, stacked first — a copy): bit-identical to it on the widened elements, from half the bytes."""
+        return self._host_xspec(_as_iq2_ci16(iq2), True, k, hop, scale, "cross_spectrum_ci16")
+
+    def _xspec_device_args(self, what: str, d_iq2: int, n_groups: int, k: int, d_out: int, frame_stride, scale: float) -> list:
+        self._float32_only(what)
+        stride = self.nfft if frame_stride is None else int(frame_stride)
+        if int(k) < 1 or int(n_groups) < 1:
+            raise ValueError("k and n_groups must be >= 1")
+        if stride < 1:
+            raise ValueError("frame_stride must be >= 1")
+        return [c_void_p(d_iq2), c_size_t(int(n_groups)), c_size_t(int(k)), c_size_t(stride), c_float(scale), c_void_p(d_out)]
+
+    def _exec_device_xspec(self, sym: str, d_iq2: int, n_groups: int, k: int, d_out: int, frame_stride, scale: float,
+                           stream: int = 0, launches: Optional[int] = None):
+        args = self._xspec_device_args(sym, d_iq2, n_groups, k, d_out, frame_stride, scale)
+        with self._lock:
+            if launches is None:
+                return check(getattr(lib(), sym)(self.handle, *args, c_void_p(stream) if stream else None))
+            ms = (c_float * int(launches))()
+            check(getattr(lib(), sym + "_timed_each")(self.handle, *args, int(launches), ms))
+        return [float(v) for v in ms]
+
+    def exec_device_xspec(self, d_iq2: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                          scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: complex64 elements in (16 bytes each; ``frame_stride`` counts elements), ``n_groups * 4 * nfft``
+        float32 out (per group the four planes of ``cross_spectrum``), asynchronous on ``stream`` (0: the plan's stream)."""
+        self._exec_device_xspec("sdrk_exec_device_xspec", d_iq2, n_groups, k, d_out, frame_stride, scale, stream)
+
+    def exec_device_xspec_timed_each(self, d_iq2: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                     frame_stride: Optional[int] = None, scale: float = 1.0) -> list:
+        """``exec_device_xspec`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_xspec("sdrk_exec_device_xspec", d_iq2, n_groups, k, d_out, frame_stride, scale,
+                                       launches=launches)
+
+    def exec_device_xspec_ci16(self, d_iq2: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
+                               scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_xspec`` from int16 elements (8 bytes each)."""
+        self._exec_device_xspec("sdrk_exec_device_xspec_ci16", d_iq2, n_groups, k, d_out, frame_stride, scale, stream)
+
+    def exec_device_xspec_ci16_timed_each(self, d_iq2: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                          frame_stride: Optional[int] = None, scale: float = 1.0) -> list:
+        """``exec_device_xspec_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_xspec("sdrk_exec_device_xspec_ci16", d_iq2, n_groups, k, d_out, frame_stride, scale,
+                                       launches=launches)
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -1175,6 +1308,17 @@ def pfb_spectral_kurtosis(iq, nfft: int, taps: int, k: int, hop: Optional[int] =
     SpectrumPlan._int_codes("mean", out, True)
     plan = _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device)
     return plan._host_sk(m, x, k, hop, out, scale)
+
+
+def cross_spectrum(a, b, nfft: int, k: int, hop: Optional[int] = None, window: WindowArg = None, *, scale: float = 1.0,
+                   shift: bool = True, device: int = 0) -> CrossSpectrum:
+    """The ``CrossSpectrum`` of two coherent channels per ``k`` frames of ``nfft`` samples, accumulated on the device in one
+    pass (``SpectrumPlan.cross_spectrum``).  ``a`` and ``b`` are equal-length complex arrays, or two ``(n, 2)`` int16 I,Q
+    arrays (the int16 form: the same bits from half the bytes); they are stacked into one element stream, a copy of both."""
+    plan = _cached_plan(int(nfft), window, 1e-12, shift, device)
+    if isinstance(a, np.ndarray) and a.dtype == np.int16:
+        return plan.cross_spectrum_ci16((a, b), k, hop, scale)
+    return plan.cross_spectrum((a, b), k, hop, scale)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,

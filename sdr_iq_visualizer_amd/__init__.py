@@ -17,7 +17,9 @@ if not _os.path.isdir(_SRC_DIR):  # pragma: no cover - broken checkout
 __path__.append(_SRC_DIR)
 
 from .spectrum import (  # noqa: E402
+    CrossSpectrum,
     SpectrumPlan,
+    cross_spectrum,
     fft_c64,
     fft_c128,
     fft_ci16,
@@ -47,9 +49,11 @@ from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
 from ._ffi import SdrkError, device_count, device_info, library_path  # noqa: E402
 
 __all__ = [
+    "CrossSpectrum",
     "SpectrumPlan",
     "WaterfallBuffer",
     "SdrkError",
+    "cross_spectrum",
     "device_count",
     "device_info",
     "fft_c64",
