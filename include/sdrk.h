@@ -520,6 +520,55 @@ int sdrk_exec_device_xspec_ci16_timed_each(sdrk_plan* plan, const void* d_iq2_ci
 int sdrk_exec_host_xspec_ci16(sdrk_plan* plan, const void* iq2_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                               float scale, float* out);
 
+/* ---- FIR filtering and channel extraction: tune, filter, decimate in one pass --------------
+ * The way back from a spectrum to samples: tune to a channel seen in the waterfall, band-limit it, lower the rate, and hand the
+ * IQ to a demodulator or to a smaller recording.  Overlap-save fast convolution in blocks of 4096 samples: forward transform,
+ * multiply by the filter's frequency response, inverse transform, keep the valid samples — in one kernel, 8*4096/L bytes read
+ * and 8/D written per input sample (4*4096/L from int16).  The reference has no counterpart.
+ * The filter belongs to the plan, as the PFB prototype does: sdrk_plan_set_fir takes M = ntaps complex64 taps h from host
+ * memory, 1 <= M <= 2049, and keeps H = DFT_4096(h zero-padded), computed once in float64 and rounded once to complex64, as a
+ * plan-owned device copy of 4096 complex64 in natural bin order.  It may be set again (not while work of the plan is in
+ * flight) and coexists with a prototype set by sdrk_plan_set_pfb; neither disturbs the other.
+ * With D = decim (a power of two in 1..256), s = shift_bins (-2048..2047) and W4096^q = exp(-2 pi i q / 4096) from the plan's
+ * own twiddle table, the device entry computes, in "valid" form,
+ *     n_out  = (n_in - M)/D + 1                                  (integer division)
+ *     h_s[t] = h[t] exp(+2 pi i s t / 4096)                      (realised as H rotated by s bins, H_s[k] = H[(k - s) mod 4096]: exact)
+ *     v[i]   = sum_t h_s[t] x[i + M - 1 - t]                     i = 0 .. n_in - M
+ *     out[m] = v[m D] W4096^((phase0 + s m D) mod 4096)          (s = 0: no mixer)
+ * so the band centred on bin s of 4096 is filtered by the low-pass h, moved to DC and decimated; the phase is continuous from
+ * call to call as long as the caller carries phase0 (any int, taken mod 4096).
+ * Blocks: L is the largest multiple of 256 with L <= 4097 - M; block b reads input samples b L .. b L + 4095 (past n_in: zeros)
+ * and yields outputs i = b L .. b L + L - 1 from its positions M - 1 .. M - 2 + L.  The inverse transform is the forward one on
+ * the conjugated product, conjugated again, scaled by the exact 2^-12.
+ * The host entries are the device entry applied to the virtual stream prefix || iq (prefix: M - 1 samples, NULL = zeros; with a
+ * zero prefix this is lfilter(h, 1, x)): n outputs before decimation, of which those whose stream index sample0 + j is a multiple
+ * of D are kept, with the mixer phase s (sample0 + j) mod 4096; *n_out receives their number.  out_c64 holds at least
+ * (n + D - 1)/D complex64.  Chunked in whole blocks through the plan's pinned staging, in device memory that does not grow with
+ * n; every block is the same 4096 samples as in one device call on the same virtual stream from its first kept sample.
+ * Promised: the host entries return the bits of that device call however they are chunked; the int16 entries return the bits
+ * of the complex64 entries on the widened samples (x = float32(I) + i float32(Q)); repeated calls return the same bits.  Not
+ * promised: equal bits between different cuts of one stream into calls (the blocks differ).
+ * Served: float32 plans with nfft = 4096 only; the plan's window, shift and eps are ignored.  Plans of another length return
+ * SDRK_ERR_UNSUPPORTED with a message.  An f64 plan, no filter set, NULL pointers, n_in < M, decim not a power of two in 1..256
+ * and shift_bins outside -2048..2047 return SDRK_ERR_INVALID with a message.  A plan that has refused still works.
+ * Not provided: other block lengths, double precision, rational resampling, fine (sub-bin) tuning. */
+int sdrk_plan_set_fir(sdrk_plan* plan, int ntaps, const void* taps_c64);
+/* taps of the filter set on the plan; 0 = none */
+int sdrk_plan_fir_taps(const sdrk_plan* plan);
+/* device in / device out (d_out_c64: n_out complex64), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_fir(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int decim, int shift_bins, int phase0,
+                         void* d_out_c64, void* stream);
+int sdrk_exec_device_fir_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, int decim, int shift_bins, int phase0,
+                              void* d_out_c64, void* stream);
+/* the complex64 form, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_fir_timed_each(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int decim, int shift_bins, int phase0,
+                                    void* d_out_c64, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays) */
+int sdrk_exec_host_fir(sdrk_plan* plan, const void* prefix_c64, const void* iq_c64, size_t n, int decim, int shift_bins,
+                       uint64_t sample0, void* out_c64, size_t* n_out);
+int sdrk_exec_host_fir_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int shift_bins,
+                            uint64_t sample0, void* out_c64, size_t* n_out);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

@@ -197,6 +197,14 @@ SYMBOLS = [
     ("sdrk_exec_device_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
     ("sdrk_exec_device_xspec_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
+    # FIR filtering and channel extraction: overlap-save in blocks of 4096, tune + filter + decimate (nfft = 4096 plans)
+    ("sdrk_plan_set_fir", c_int, [c_void_p, c_int, c_void_p]),
+    ("sdrk_plan_fir_taps", c_int, [c_void_p]),
+    ("sdrk_exec_device_fir", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("sdrk_exec_device_fir_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("sdrk_exec_device_fir_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_fir", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_host_fir_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
 ]
 
 _lib = None

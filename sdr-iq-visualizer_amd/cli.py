@@ -1,11 +1,14 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
     python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross]] [--pfb T] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F --decim D [--taps M] --out BASE
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
 (app/sdr/streamer.py:119-121) and, with ``--welch N``, the averaged Hann PSD its offline script
-plots (scripts/process_sigmf_data.py:188-189).  All transforms run through libsdrk.
+plots (scripts/process_sigmf_data.py:188-189).  ``extract`` tunes to ``center_freq + F`` (rounded to a bin of
+``sample_rate/4096``), low-passes, decimates by D and writes the channel as a cf32_le SigMF recording at ``sample_rate/D``.
+All transforms run through libsdrk.
 """
 from __future__ import annotations
 
@@ -21,6 +24,36 @@ def _positive(text: str) -> int:
     if v < 1:
         raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
     return v
+
+
+EXTRACT_PIECE = 1 << 22            # samples per ChannelStream.push of `extract`
+
+
+def _extract(args, sigmf_io, spectrum) -> int:
+    """One channel of a single-channel cf32_le / ci16_le recording -> a cf32_le recording at sample_rate / decim."""
+    samples, meta = sigmf_io.read_sigmf(args.path, native=True)
+    g = meta.get("global", {})
+    if int(g.get("core:num_channels", 1)) != 1:
+        print(f"extract takes a single-channel recording; this one has core:num_channels = {g.get('core:num_channels')}",
+              file=sys.stderr)
+        return 2
+    fs, fc = float(meta["sample_rate"]), float(meta["center_freq"])
+    try:
+        taps = spectrum.channel_taps(args.decim, args.taps)
+        ch = spectrum.ChannelStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
+    except ValueError as err:
+        print(f"extract: {err}", file=sys.stderr)
+        return 2
+    with ch:
+        n = int(samples.shape[0])
+        out = [ch.push(samples[at:at + EXTRACT_PIECE]) for at in range(0, n, EXTRACT_PIECE)]
+    y = np.concatenate(out) if out else np.empty(0, np.complex64)
+    paths = sigmf_io.write_sigmf(args.out, y, fs / args.decim, fc + ch.tuned_hz,
+                                 description=f"channel at {ch.tuned_hz:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
+    print(json.dumps({"wrote": list(paths), "samples_in": n, "samples_out": int(y.shape[0]), "sample_rate": fs / args.decim,
+                      "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, "shift_bins": ch.shift_bins,
+                      "decim": args.decim, "taps": int(taps.shape[0])}))
+    return 0
 
 
 def main(argv=None) -> int:
@@ -49,6 +82,13 @@ def main(argv=None) -> int:
     p.add_argument("--window", default=None)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--out", default=None, help="write results to this .npz")
+    e = sub.add_parser("extract")
+    e.add_argument("path")
+    e.add_argument("--offset-hz", type=float, required=True, help="the channel's centre, relative to the recording's centre")
+    e.add_argument("--decim", type=_positive, required=True, help="decimation: a power of two in 1..256")
+    e.add_argument("--taps", type=_positive, default=None, help="filter length (default min(16*decim + 1, 2049))")
+    e.add_argument("--out", required=True, help="base name of the cf32_le SigMF recording to write")
+    e.add_argument("--device", type=int, default=0)
     s = sub.add_parser("synth")
     s.add_argument("base")
     s.add_argument("--frames", type=int, default=8)
@@ -71,6 +111,8 @@ def main(argv=None) -> int:
         return 0
 
     from . import spectrum
+    if args.cmd == "extract":
+        return _extract(args, sigmf_io, spectrum)
     # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
     # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
     samples, meta = sigmf_io.read_sigmf(args.path, native=True)

@@ -119,6 +119,11 @@ struct sdrk_plan {
     int pfb_taps = 0;
     int pfb_assign = 0;
     sdrk_host::Staging pfb;
+    // FIR filtering and channel extraction (pfb_api.hip): d_fir_h = DFT_4096 of the zero-padded taps, 4096 complex64 in natural
+    // bin order (sdrk_plan_set_fir; 0 taps = none); fir_assign = ols4096_kernel's block assignment (kernels_ols.h)
+    float2* d_fir_h = nullptr;
+    int fir_taps = 0;
+    int fir_assign = 0;
 };
 
 namespace sdrk_host {

@@ -511,6 +511,7 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     p->integ.release();
     if (p->d_pfb_h) (void)hipFree(p->d_pfb_h);
     p->pfb.release();
+    if (p->d_fir_h) (void)hipFree(p->d_fir_h);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {

@@ -222,6 +222,49 @@ def pfb_prototype(nfft: int, taps: int, window: WindowArg = "hann") -> np.ndarra
     return (np.sinc((m - (n - 1) / 2.0) / nfft) * w).astype(np.float32)
 
 
+FIR_MAX_TAPS = 2049               # sdrk.h: taps of a FIR filter (overlap-save in blocks of 4096)
+FIR_MAX_DECIM = 256
+FIR_BLOCK = 4096
+
+
+def channel_taps(decim: int, ntaps: Optional[int] = None, window: WindowArg = "hann") -> np.ndarray:
+    """The default low-pass of a channel extraction that decimates by ``decim``: complex64 windowed sinc with cutoff
+    ``0.4/decim`` cycles per sample and unit DC gain, ``sinc(0.8 (t - (M - 1)/2) / decim) * window(M + 2)[t + 1]`` normalised to sum 1,
+    computed in float64 and rounded once.  ``ntaps`` defaults to ``min(16*decim + 1, 2049)``.  ``window``: ``"hann"``
+    (``numpy.hanning``), ``"hamming"``, ``"blackman"``, ``None`` / ``"rect"``, or ``ntaps`` coefficients.
+    With the default length the stopband from ``0.6/decim`` on lies below -55 dB under Hann and below -75 dB under Blackman
+    for ``decim`` up to 128; at ``decim = 256`` the 2049-tap limit leaves -43 dB (Hann)."""
+    decim = int(decim)
+    if decim < 1 or decim > FIR_MAX_DECIM or decim & (decim - 1):
+        raise ValueError(f"decim must be a power of two in 1..{FIR_MAX_DECIM}, got {decim}")
+    m = min(16 * decim + 1, FIR_MAX_TAPS) if ntaps is None else int(ntaps)
+    if not 1 <= m <= FIR_MAX_TAPS:
+        raise ValueError(f"ntaps must be in 1..{FIR_MAX_TAPS}, got {m}")
+    if window is None or (isinstance(window, str) and window.lower() in ("rect", "rectangular", "boxcar", "none")):
+        w = np.ones(m, dtype=np.float64)
+    elif isinstance(window, str):
+        makers = {"hann": np.hanning, "hanning": np.hanning, "hamming": np.hamming, "blackman": np.blackman}
+        if window.lower() not in makers:
+            raise ValueError(f"unknown window {window!r} (use 'hann', 'hamming', 'blackman', None or an array of ntaps floats)")
+        w = makers[window.lower()](m + 2)[1:-1]              # (without the two zero end points: every tap works)
+    else:
+        w = np.asarray(window, dtype=np.float64)
+        if w.shape != (m,):
+            raise ValueError(f"window must have shape ({m},), got {w.shape}")
+    t = np.arange(m, dtype=np.float64) - (m - 1) / 2.0
+    h = np.sinc(0.8 * t / decim) * w
+    return (h / h.sum()).astype(np.complex64)
+
+
+def _fir_args(decim, shift_bins):
+    decim, shift_bins = int(decim), int(shift_bins)
+    if decim < 1 or decim > FIR_MAX_DECIM or decim & (decim - 1):
+        raise ValueError(f"decim must be a power of two in 1..{FIR_MAX_DECIM}, got {decim}")
+    if not -FIR_BLOCK // 2 <= shift_bins < FIR_BLOCK // 2:
+        raise ValueError(f"shift_bins must be in {-FIR_BLOCK // 2}..{FIR_BLOCK // 2 - 1}, got {shift_bins}")
+    return decim, shift_bins
+
+
 class _Mode(NamedTuple):
     """One corner of sample format x front end, and the C entry points that serve it (include/sdrk.h)."""
     ci16: bool                  # int16 I,Q pairs in (else complex64)
@@ -304,6 +347,7 @@ class SpectrumPlan:
         self.device = int(device)
         self._lock = threading.Lock()
         self.pfb_taps = 0                              # taps of the prototype filter set by set_pfb() (0: none)
+        self.fir_taps = 0                              # taps of the FIR filter set by set_fir() (0: none)
         self.last_placement: Optional[dict] = None     # report of the last tune_scratch() on this plan
         self._handle = c_void_p()
         wptr = warr.ctypes.data_as(c_void_p) if warr is not None else None
@@ -915,6 +959,96 @@ class SpectrumPlan:
         return self._exec_device_xspec("sdrk_exec_device_xspec_ci16", d_iq2, n_groups, k, d_out, frame_stride, scale,
                                        launches=launches)
 
+    # -- FIR filtering and channel extraction: tune, filter, decimate (float32 plans with nfft = 4096) -----------------------
+    def set_fir(self, taps) -> int:
+        """Set the FIR filter: 1..2049 complex taps (``channel_taps`` makes the usual low-pass); returns their number.  The plan
+        keeps the filter's 4096-point frequency response; may be called again, and leaves a PFB prototype alone."""
+        self._float32_only("FIR filtering")
+        h = _as_c64(taps)
+        if h.ndim != 1 or not 1 <= h.shape[0] <= FIR_MAX_TAPS:
+            raise ValueError(f"taps must be a 1-D array of 1..{FIR_MAX_TAPS} coefficients, got shape {h.shape}")
+        with self._lock:
+            check(lib().sdrk_plan_set_fir(self.handle, int(h.shape[0]), h.ctypes.data_as(c_void_p)))
+            self.fir_taps = int(h.shape[0])
+        return self.fir_taps
+
+    def _fir_ready(self) -> int:
+        self._float32_only("FIR filtering")
+        if self.fir_taps < 1:
+            raise ValueError("no FIR filter set: call set_fir() first")
+        return self.fir_taps
+
+    def _host_fir(self, sym: str, x: np.ndarray, n: int, prefix, decim: int, shift_bins: int, sample0: int) -> np.ndarray:
+        decim, shift_bins = _fir_args(decim, shift_bins)
+        if int(sample0) < 0:
+            raise ValueError("sample0 must be >= 0")
+        out = np.empty((n + decim - 1) // decim, dtype=np.complex64)
+        n_out = c_size_t(0)
+        with self._lock:
+            check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
+                                      x.ctypes.data_as(c_void_p), c_size_t(n), decim, shift_bins, _ffi.c_uint64(int(sample0)),
+                                      out.ctypes.data_as(c_void_p), byref(n_out)))
+        return out[: n_out.value]
+
+    def fir(self, iq, *, decim: int = 1, shift_bins: int = 0, prefix=None, sample0: int = 0) -> np.ndarray:
+        """Tune, filter and decimate one piece of a complex64 stream: with ``h`` the taps set by ``set_fir`` (``M`` of them),
+        ``y[j] = sum_t h[t] exp(2 pi i s t / 4096) v[j + M - 1 - t]`` over ``v = prefix || iq`` (``prefix``: the ``M - 1``
+        samples before ``iq``, default zeros: ``lfilter``), times ``exp(-2 pi i s (sample0 + j) / 4096)``, and of those the
+        samples whose stream index ``sample0 + j`` is a multiple of ``decim``.  Overlap-save on the GPU in one kernel."""
+        m = self._fir_ready()
+        x = _as_c64(iq).reshape(-1)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_c64(prefix).reshape(-1)
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return self._host_fir("sdrk_exec_host_fir", x, x.shape[0], pre, decim, shift_bins, sample0)
+
+    def fir_ci16(self, iq, *, decim: int = 1, shift_bins: int = 0, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``fir`` on interleaved int16 I,Q of shape ``(n, 2)`` (``prefix``: ``(M - 1, 2)`` int16): the bits of ``fir`` on the
+        widened samples, at 4 bytes per sample over the link and from device memory."""
+        m = self._fir_ready()
+        x = _as_ci16(iq, stream=True)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_ci16(prefix, stream=True)
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return self._host_fir("sdrk_exec_host_fir_ci16", x, x.shape[0], pre, decim, shift_bins, sample0)
+
+    def fir_outputs(self, n_in: int, decim: int = 1) -> int:
+        """Samples ``exec_device_fir`` writes for ``n_in`` input samples: ``(n_in - M)//decim + 1``."""
+        m = self._fir_ready()
+        if int(n_in) < m:
+            raise ValueError(f"n_in={n_in}: a valid convolution needs at least the {m} taps")
+        return (int(n_in) - m) // int(decim) + 1
+
+    def _device_fir_args(self, d_in: int, n_in: int, decim: int, shift_bins: int, phase0: int, d_out: int) -> list:
+        self._fir_ready()
+        decim, shift_bins = _fir_args(decim, shift_bins)
+        return [self.handle, c_void_p(d_in), c_size_t(int(n_in)), decim, shift_bins, int(phase0) & (FIR_BLOCK - 1), c_void_p(d_out)]
+
+    def exec_device_fir(self, d_in: int, n_in: int, d_out: int, *, decim: int = 1, shift_bins: int = 0, phase0: int = 0,
+                        stream: int = 0) -> None:
+        """Device pointers, "valid" form: ``n_in`` complex64 samples in, ``fir_outputs(n_in, decim)`` complex64 out,
+        ``out[m] = v[m decim] W4096^(phase0 + s m decim)``; asynchronous on ``stream`` (0: the plan's stream)."""
+        args = self._device_fir_args(d_in, n_in, decim, shift_bins, phase0, d_out)
+        check(lib().sdrk_exec_device_fir(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_fir_ci16(self, d_in: int, n_in: int, d_out: int, *, decim: int = 1, shift_bins: int = 0, phase0: int = 0,
+                             stream: int = 0) -> None:
+        """``exec_device_fir`` on int16 I,Q input (4 bytes per sample)."""
+        args = self._device_fir_args(d_in, n_in, decim, shift_bins, phase0, d_out)
+        check(lib().sdrk_exec_device_fir_ci16(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_fir_timed_each(self, d_in: int, n_in: int, d_out: int, launches: int = 1, *, decim: int = 1,
+                                   shift_bins: int = 0, phase0: int = 0) -> list:
+        """``exec_device_fir`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_fir_args(d_in, n_in, decim, shift_bins, phase0, d_out)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_fir_timed_each(*args, int(launches), each))
+        return list(each)
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -1339,3 +1473,80 @@ def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, 
     if devices is not None and len(devices) == 1:
         device = devices[0]
     return _cached_plan(int(nfft), window, eps, shift, device).stft_db(iq, hop)
+
+
+def _cached_fir_plan(taps, device: int) -> "SpectrumPlan":
+    h = _as_c64(taps)
+    key = (int(device), FIR_BLOCK, ("fir", hashlib.sha1(h.tobytes()).digest()), 1e-12, True, "single")
+    plan = _plans.get(key)
+    if plan is None:
+        with _plans_lock:
+            plan = _plans.get(key)
+            if plan is None:
+                plan = SpectrumPlan(FIR_BLOCK, device=device)
+                plan.set_fir(h)
+                _plans[key] = plan
+    return plan
+
+
+def fir_filter(iq, taps, decim: int = 1, shift_bins: int = 0, *, device: int = 0) -> np.ndarray:
+    """``SpectrumPlan.fir`` on a cached plan that holds ``taps``: ``lfilter(taps, 1, iq)`` of the band centred on bin
+    ``shift_bins`` of 4096, moved to DC, every ``decim``-th sample.  int16 ``(n, 2)`` input takes the int16 entry."""
+    _fir_args(decim, shift_bins)
+    plan = _cached_fir_plan(taps, device)
+    if isinstance(iq, np.ndarray) and iq.dtype == np.int16:
+        return plan.fir_ci16(iq, decim=decim, shift_bins=shift_bins)
+    return plan.fir(iq, decim=decim, shift_bins=shift_bins)
+
+
+class ChannelStream:
+    """One channel out of a stream that arrives in pieces: tuned to ``offset_hz`` from the centre, low-passed by ``taps``,
+    decimated by ``decim``.  The offset is rounded to a whole bin of ``sample_rate/4096`` (``shift_bins``; ``tuned_hz`` is the
+    frequency actually tuned).  ``push(iq)`` takes pieces of any length (complex64, or int16 ``(n, 2)`` throughout) and returns
+    the complex64 output samples they complete; the last ``M - 1`` input samples and the stream index are kept between calls,
+    so filter and mixer run on as over one stream.  ``plan``: a float32 ``SpectrumPlan(4096)`` to use (its FIR filter is
+    replaced), or None for one of the stream's own."""
+
+    def __init__(self, plan, taps, decim: int, offset_hz: float, sample_rate: float, *, device: int = 0):
+        self.decim, _ = _fir_args(decim, 0)
+        self.sample_rate = float(sample_rate)
+        if not self.sample_rate > 0:
+            raise ValueError("sample_rate must be positive")
+        bin_hz = self.sample_rate / FIR_BLOCK
+        self.shift_bins = int(np.rint(float(offset_hz) / bin_hz))
+        _fir_args(self.decim, self.shift_bins)           # an offset beyond the band: ValueError
+        self.tuned_hz = self.shift_bins * bin_hz
+        self.out_rate = self.sample_rate / self.decim
+        self._own = plan is None
+        self.plan = SpectrumPlan(FIR_BLOCK, device=device) if plan is None else plan
+        self.ntaps = int(self.plan.set_fir(taps))
+        self.sample_index = 0                              # stream index of the next input sample
+        self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
+
+    def push(self, iq) -> np.ndarray:
+        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
+        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
+        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
+            raise ValueError("a ChannelStream takes complex or int16 pieces, not both")
+        n = int(x.shape[0])
+        if n == 0:
+            return np.empty(0, dtype=np.complex64)
+        run = self.plan.fir_ci16 if ci16 else self.plan.fir
+        out = run(x, decim=self.decim, shift_bins=self.shift_bins, prefix=self._tail, sample0=self.sample_index)
+        keep = self.ntaps - 1
+        if keep:
+            if self._tail is None:
+                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
+            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+        self.sample_index += n
+        return out
+
+    def close(self) -> None:
+        if self._own:
+            self.plan.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -17,12 +17,15 @@ if not _os.path.isdir(_SRC_DIR):  # pragma: no cover - broken checkout
 __path__.append(_SRC_DIR)
 
 from .spectrum import (  # noqa: E402
+    ChannelStream,
     CrossSpectrum,
     SpectrumPlan,
+    channel_taps,
     cross_spectrum,
     fft_c64,
     fft_c128,
     fft_ci16,
+    fir_filter,
     freq_axis,
     integrated_db,
     integrated_db_ci16,
@@ -49,16 +52,19 @@ from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
 from ._ffi import SdrkError, device_count, device_info, library_path  # noqa: E402
 
 __all__ = [
+    "ChannelStream",
     "CrossSpectrum",
     "SpectrumPlan",
     "WaterfallBuffer",
     "SdrkError",
+    "channel_taps",
     "cross_spectrum",
     "device_count",
     "device_info",
     "fft_c64",
     "fft_c128",
     "fft_ci16",
+    "fir_filter",
     "freq_axis",
     "integrated_db",
     "integrated_db_ci16",

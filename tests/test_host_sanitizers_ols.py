@@ -1,0 +1,28 @@
+"""Sanitizer legs for the host side of the FIR filtering / channel extraction entry points (CPU).
+
+csrc/pfb_api.hip (sdrk_plan_set_fir, sdrk_exec_device_fir*, sdrk_exec_host_fir* and their chunk loop on the pinned staging slots)
+and the other host files of csrc/ (tests/host_sources.py), compiled with g++ against the stand-in runtime of tests/fake_hip and
+the stand-in kernels tests/fake_*_kernels.cpp (fake_ols_kernels.cpp among them: the real block geometry and the shared
+arithmetic of csrc/kernels_ols.h), driven by the stand-alone program tests/host_api_ols_stress.cpp under ThreadSanitizer and
+under AddressSanitizer + UBSan with leak checking.  Nothing is loaded into Python, nothing is preloaded.  Three threads on their
+own plans; both formats; device, timed and host entries; chunks of three blocks with a prefix and without; every output element
+checked against a direct convolution; the refusals; a PFB call between FIR calls on one plan."""
+import os
+import subprocess
+
+import pytest
+
+from tests.host_sources import SANITIZERS, build_driver
+
+
+@pytest.mark.parametrize("san", list(SANITIZERS))
+def test_fir_host_entry_points_under_sanitizers(san):
+    env = dict(os.environ, SDRK_HOST_THREADS="3", SDRK_FIR_CHUNK_BLOCKS="3",
+               TSAN_OPTIONS="halt_on_error=1 exitcode=66", ASAN_OPTIONS="detect_leaks=1 exitcode=67",
+               UBSAN_OPTIONS="halt_on_error=1 print_stacktrace=1")
+    r = subprocess.run([build_driver(san, "host_api_ols_stress.cpp"), "3", "1"], capture_output=True, text=True, env=env, timeout=900)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-4000:])
+    assert "bad=0" in r.stdout and "sdrk 500 ols threads=3" in r.stdout
+    compared = int(r.stdout.split("compared=")[1].split()[0])
+    assert compared > 500_000, r.stdout                       # (every output sample of every case, from every thread)
+    assert int(r.stdout.split("refused=")[1].split()[0]) >= 60
