@@ -569,6 +569,41 @@ int sdrk_exec_host_fir(sdrk_plan* plan, const void* prefix_c64, const void* iq_c
 int sdrk_exec_host_fir_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int shift_bins,
                             uint64_t sample0, void* out_c64, size_t* n_out);
 
+/* ---- channel bank: C tuned channels from one pass over the input ---------------------------
+ * A wide-band capture rarely holds one signal of interest: six carriers in the waterfall want six narrow IQ streams.  With the
+ * single call above that is six calls, each re-reading the capture and each repeating the forward transform of every block.
+ * The bank call reads the input once and transforms each block once; per channel only the channel-dependent half runs (H rotated
+ * by that channel's offset, the inverse transform, the mixer, the decimated store): 1 + C transforms per block instead of 2 C.
+ * The filter is the one set by sdrk_plan_set_fir, shared by all channels; D = decim is common; channel c is tuned to
+ * shift_bins[c] (-2048..2047, duplicates allowed) and starts its mixer at phase0[c] (any int, taken mod 4096; phase0 = NULL:
+ * zeros).  1 <= n_chan <= 64.  Both arrays are host memory and are read before the call returns.
+ * Channel c lies at d_out_c64 + c * out_stride complex64 (out_stride >= n_out) and holds n_out = (n_in - M)/D + 1 samples:
+ * EXACTLY THE BITS of sdrk_exec_device_fir(plan, d_in, n_in, D, shift_bins[c], phase0[c], ...) on the same input — for every C,
+ * M, D, set of offsets and length, from complex64 and from int16 (the bits of sdrk_exec_device_fir_ci16), and a channel with
+ * offset 0 runs no mixer, as there.  Elements between n_out and out_stride are not written.
+ * The host entries are the device entry on the virtual stream prefix || iq exactly as sdrk_exec_host_fir is (same prefix,
+ * sample0, kept samples and *n_out, the same for every channel; channel c's mixer phase is shift_bins[c] (sample0 + j) mod 4096),
+ * plane c at out_c64 + c * out_stride with out_stride >= (n + D - 1)/D; chunked in whole blocks through the same pinned staging
+ * (SDRK_FIR_CHUNK_BLOCKS honoured), in device memory that does not grow with n, and returning the device entry's bits however
+ * they are chunked.
+ * Served and refused as the single call is, and in addition SDRK_ERR_INVALID with a message for n_chan outside 1..64, a NULL
+ * shift_bins, an offset outside -2048..2047 and an out_stride below the outputs of a channel.  A plan that has refused still works.
+ * Not provided: per-channel filters or decimation, more than 64 channels (the critically sampled many-channel case is the
+ * polyphase filter bank's), a smaller inverse transform for D > 1. */
+int sdrk_exec_device_chanbank(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                              const int* phase0, void* d_out_c64, size_t out_stride, void* stream);
+int sdrk_exec_device_chanbank_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                                   const int* phase0, void* d_out_c64, size_t out_stride, void* stream);
+/* the complex64 form, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_chanbank_timed_each(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int decim, int n_chan,
+                                         const int* shift_bins, const int* phase0, void* d_out_c64, size_t out_stride, int launches,
+                                         float* each_ms);
+/* host in / host out (pageable or pinned caller arrays) */
+int sdrk_exec_host_chanbank(sdrk_plan* plan, const void* prefix_c64, const void* iq_c64, size_t n, int decim, int n_chan,
+                            const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out);
+int sdrk_exec_host_chanbank_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int n_chan,
+                                 const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out);
+
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic
  *   shape at N = 4096 (32 KiB read + 16 KiB written per frame, no arithmetic), timed per

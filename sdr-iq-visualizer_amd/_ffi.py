@@ -205,6 +205,12 @@ SYMBOLS = [
     ("sdrk_exec_device_fir_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_fir", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
     ("sdrk_exec_host_fir_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    # channel bank: C tuned channels from one pass over the input (the filter of sdrk_plan_set_fir; planes out_stride apart)
+    ("sdrk_exec_device_chanbank", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_chanbank_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_chanbank_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_size_t, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_chanbank", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
+    ("sdrk_exec_host_chanbank_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
 ]
 
 _lib = None

@@ -1,13 +1,14 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
     python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross]] [--pfb T] [--out rows.npz]
-    python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F --decim D [--taps M] --out BASE
+    python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F [F ...] --decim D [--taps M] --out BASE
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
 (app/sdr/streamer.py:119-121) and, with ``--welch N``, the averaged Hann PSD its offline script
 plots (scripts/process_sigmf_data.py:188-189).  ``extract`` tunes to ``center_freq + F`` (rounded to a bin of
-``sample_rate/4096``), low-passes, decimates by D and writes the channel as a cf32_le SigMF recording at ``sample_rate/D``.
+``sample_rate/4096``), low-passes, decimates by D and writes the channel as a cf32_le SigMF recording at ``sample_rate/D``;
+several offsets are extracted in one pass over the recording and written as ``BASE_0``, ``BASE_1``, ...
 All transforms run through libsdrk.
 """
 from __future__ import annotations
@@ -38,9 +39,11 @@ def _extract(args, sigmf_io, spectrum) -> int:
               file=sys.stderr)
         return 2
     fs, fc = float(meta["sample_rate"]), float(meta["center_freq"])
+    if len(args.offset_hz) > 1:
+        return _extract_bank(args, sigmf_io, spectrum, samples, fs, fc)
     try:
         taps = spectrum.channel_taps(args.decim, args.taps)
-        ch = spectrum.ChannelStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
+        ch = spectrum.ChannelStream(None, taps, args.decim, args.offset_hz[0], fs, device=args.device)
     except ValueError as err:
         print(f"extract: {err}", file=sys.stderr)
         return 2
@@ -52,6 +55,28 @@ def _extract(args, sigmf_io, spectrum) -> int:
                                  description=f"channel at {ch.tuned_hz:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
     print(json.dumps({"wrote": list(paths), "samples_in": n, "samples_out": int(y.shape[0]), "sample_rate": fs / args.decim,
                       "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, "shift_bins": ch.shift_bins,
+                      "decim": args.decim, "taps": int(taps.shape[0])}))
+    return 0
+
+
+def _extract_bank(args, sigmf_io, spectrum, samples, fs: float, fc: float) -> int:
+    """Several offsets: one ChannelBankStream, one pass over the recording, channel c -> the recording BASE_c."""
+    try:
+        taps = spectrum.channel_taps(args.decim, args.taps)
+        bank = spectrum.ChannelBankStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
+    except ValueError as err:
+        print(f"extract: {err}", file=sys.stderr)
+        return 2
+    with bank:
+        n = int(samples.shape[0])
+        out = [bank.push(samples[at:at + EXTRACT_PIECE]) for at in range(0, n, EXTRACT_PIECE)]
+    y = np.concatenate(out, axis=1) if out else np.empty((len(bank.shift_bins), 0), np.complex64)
+    channels = []
+    for c, (tuned, bins) in enumerate(zip(bank.tuned_hz, bank.shift_bins)):
+        paths = sigmf_io.write_sigmf(f"{args.out}_{c}", np.ascontiguousarray(y[c]), fs / args.decim, fc + tuned,
+                                     description=f"channel at {tuned:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
+        channels.append({"wrote": list(paths), "center_freq": fc + tuned, "tuned_offset_hz": tuned, "shift_bins": bins})
+    print(json.dumps({"channels": channels, "samples_in": n, "samples_out": int(y.shape[1]), "sample_rate": fs / args.decim,
                       "decim": args.decim, "taps": int(taps.shape[0])}))
     return 0
 
@@ -84,7 +109,8 @@ def main(argv=None) -> int:
     p.add_argument("--out", default=None, help="write results to this .npz")
     e = sub.add_parser("extract")
     e.add_argument("path")
-    e.add_argument("--offset-hz", type=float, required=True, help="the channel's centre, relative to the recording's centre")
+    e.add_argument("--offset-hz", type=float, nargs="+", required=True,
+                   help="the channel's centre, relative to the recording's centre; several: one pass, recordings OUT_0, OUT_1, ...")
     e.add_argument("--decim", type=_positive, required=True, help="decimation: a power of two in 1..256")
     e.add_argument("--taps", type=_positive, default=None, help="filter length (default min(16*decim + 1, 2049))")
     e.add_argument("--out", required=True, help="base name of the cf32_le SigMF recording to write")

@@ -19,8 +19,8 @@
 // The mixer's factor W4096^((phase0 + s i) mod 4096) comes from the plan's twiddle table (32 KiB, cache resident), one read per
 // stored sample; s = 0 compiles it out.
 // The int16 policy gives x = float32(I) + i float32(Q) exactly and then the same arithmetic in the same order.
-#include "fft4096_in_ci16.h"
 #include "kernels_ols.h"
+#include "ols_in.h"
 
 namespace sdrk {
 
@@ -28,28 +28,6 @@ namespace sdrk {
 // 158 (complex64), 132 (int16), 148 (int16 with the mixer) — and two for complex64 with the mixer, which needs 174.
 template <class In, bool MIX>
 constexpr int ols_wg_per_cu() { return (MIX && In::ELEM == 8) ? 2 : 3; }
-
-// Input policies (F4kInC64 / F4kInCi16<false> under a descriptor clipped to the samples that exist).
-struct OlsInC64 {
-    typedef v2u word;
-    static constexpr int ELEM = 8;
-    static __device__ __forceinline__ void load(word (&x)[16], const char* blk, unsigned bytes, int tid) {
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(blk, bytes);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, tid * ELEM, j * 256 * ELEM, F4K_NT);
-    }
-    static __device__ __forceinline__ cf widen(word w) { return F4kInC64::widen(w); }
-};
-struct OlsInI16 {
-    typedef unsigned word;
-    static constexpr int ELEM = 4;
-    static __device__ __forceinline__ void load(word (&x)[16], const char* blk, unsigned bytes, int tid) {
-        __amdgpu_buffer_rsrc_t r = frame_rsrc(blk, bytes);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b32(r, tid * ELEM, j * 256 * ELEM, F4K_NT);
-    }
-    static __device__ __forceinline__ cf widen(word w) { return F4kInCi16<false>::widen(w); }
-};
 
 struct OlsGeom {
     size_t n_in, n_out, n_blocks;

@@ -13,7 +13,8 @@
 // Integration over K folded frames is integrate_api.hip, with this file's launchers and checks.  Out of scope: double
 // precision, waterfall appends.
 // The last part of the file is the host side of "FIR filtering and channel extraction" (sdrk_plan_set_fir, sdrk_exec_*_fir*):
-// overlap-save fast convolution in blocks of 4096 through ols4096.hip, the filter held by the plan as the prototype is.
+// overlap-save fast convolution in blocks of 4096 through ols4096.hip, the filter held by the plan as the prototype is, and of
+// the channel bank (sdrk_exec_*_chanbank*): C tuned channels from one pass through ols_bank.hip, on the same chunk loop.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -24,7 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include "kernels_ols.h"
+#include "kernels_ols_bank.h"
 #include "kernels_pfb.h"
 #include "plan_internal.h"
 
@@ -293,10 +294,12 @@ size_t fir_chunk_blocks(size_t L, size_t in_elem) {
 // multiple of D, in chunks of whole blocks through the plan's three pinned staging slots.  Every block sees the 4096 samples it
 // sees in one device call on the whole virtual stream (a chunk carries its last block's 4096 - L samples of overlap, and a
 // launch is cut at its chunk's blocks), so the chunking does not show in the bits.
-int exec_host_fir(size_t in_elem, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int decim, int shift_bins,
-                  uint64_t sample0, void* out, size_t* n_out) {
-    int st = check_fir_call(p, decim, shift_bins);
-    if (st != SDRK_OK) return st;
+// One loop for the single call and the channel bank: `planes` output planes, out_stride complex64 apart in the caller's array
+// and packed in a slot's staging; launch(d_in, cn, index, d_out, nb, co) runs the first nb blocks of a chunk of cn samples,
+// whose first valid output has stream index `index` mod 4096 (the mixer's phase is s * index) and which keeps co outputs a plane.
+template <class Launch>
+int host_fir_chunks(size_t in_elem, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int decim, uint64_t sample0,
+                    size_t planes, void* out, size_t out_stride, size_t* n_out, Launch launch) {
     if (!n_out) return fail(SDRK_ERR_INVALID, "n_out pointer is NULL");
     *n_out = 0;
     if (n == 0) return SDRK_OK;
@@ -306,19 +309,18 @@ int exec_host_fir(size_t in_elem, sdrk_plan* p, const void* prefix, const void* 
     if (j0 >= n) return SDRK_OK;
     const size_t n_virt = n - j0 + M - 1;                 // the virtual stream from there: sample t is V[j0 + t], V = prefix || iq
     const size_t total_out = (n - j0 - 1) / D + 1;
-    const unsigned s_mod = (unsigned)shift_bins & (unsigned)(N - 1);
-    const unsigned phase_first = (s_mod * (unsigned)((sample0 + j0) & (N - 1))) & (unsigned)(N - 1);
     const size_t n_blocks = sdrk::ols_blocks(n_virt, p->fir_taps);
     const size_t per = fir_chunk_blocks(L, in_elem), opb = L / D;
-    const size_t chunk_in = ((per - 1) * L + N) * in_elem, chunk_out = per * opb * sizeof(float2);
+    const size_t chunk_in = ((per - 1) * L + N) * in_elem, chunk_out = planes * per * opb * sizeof(float2);
     HIP_TRY(hipSetDevice(p->device));
-    st = ensure_copy_streams(p);
+    int st = ensure_copy_streams(p);
     if (st != SDRK_OK) return st;
-    auto retire = [](HostSlot& s) -> int {
+    auto retire = [planes, out_stride](HostSlot& s) -> int {   // out_bytes: of one plane
         if (!s.busy) return SDRK_OK;
         s.busy = false;
         HIP_TRY(hipEventSynchronize(s.ev_done));
-        memcpy(s.user_out, s.h_out, s.out_bytes);
+        for (size_t c = 0; c < planes; ++c)
+            memcpy(static_cast<char*>(s.user_out) + c * out_stride * sizeof(float2), static_cast<char*>(s.h_out) + c * s.out_bytes, s.out_bytes);
         return SDRK_OK;
     };
     size_t c = 0;
@@ -344,13 +346,12 @@ int exec_host_fir(size_t in_elem, sdrk_plan* p, const void* prefix, const void* 
             memcpy(dst + done * in_elem, static_cast<const char*>(iq) + (v0 + done - (M - 1)) * in_elem, (cn - done) * in_elem);
         hipError_t e = stage_chunk_in(p, s, s.h_in, cn * in_elem);
         if (e == hipSuccess) {
-            const unsigned phase = (phase_first + s_mod * (unsigned)(t0 & (N - 1))) & (unsigned)(N - 1);
-            st = fir_launch(p, in_elem == 4, s.d_in, cn, decim, shift_bins, (int)phase, s.d_out, nb, p->stream);
+            st = launch(s.d_in, cn, (unsigned)((sample0 + j0 + t0) & (N - 1)), s.d_out, nb, co);
             if (st != SDRK_OK) { slots_abandon(p); return st; }
             e = hipEventRecord(s.ev_k, p->stream);
         }
         if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_out, s.d_out, co * sizeof(float2), hipMemcpyDeviceToHost, p->s_d2h);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.h_out, s.d_out, planes * co * sizeof(float2), hipMemcpyDeviceToHost, p->s_d2h);
         if (e == hipSuccess) e = hipEventRecord(s.ev_done, p->s_d2h);
         if (e != hipSuccess) {
             slots_abandon(p);
@@ -366,6 +367,92 @@ int exec_host_fir(size_t in_elem, sdrk_plan* p, const void* prefix, const void* 
     }
     *n_out = total_out;
     return SDRK_OK;
+}
+
+int exec_host_fir(size_t in_elem, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int decim, int shift_bins,
+                  uint64_t sample0, void* out, size_t* n_out) {
+    int st = check_fir_call(p, decim, shift_bins);
+    if (st != SDRK_OK) return st;
+    const unsigned s_mod = (unsigned)shift_bins & (unsigned)(sdrk::OLS_N - 1);
+    return host_fir_chunks(in_elem, p, prefix, iq, n, decim, sample0, 1, out, 0, n_out,
+                           [&](const void* d_in, size_t cn, unsigned index, void* d_out, size_t nb, size_t) {
+                               const unsigned phase = (s_mod * index) & (unsigned)(sdrk::OLS_N - 1);
+                               return fir_launch(p, in_elem == 4, d_in, cn, decim, shift_bins, (int)phase, d_out, nb, p->stream);
+                           });
+}
+
+// ---- channel bank: C tuned channels from one pass over the input (kernels_ols_bank.h) ----
+int check_bank_call(const sdrk_plan* p, int decim, int n_chan, const int* shift_bins) {
+    int st = check_fir_call(p, decim, 0);
+    if (st != SDRK_OK) return st;
+    if (n_chan < 1 || n_chan > sdrk::OLS_BANK_MAX_CHAN)
+        return fail(SDRK_ERR_INVALID, "n_chan=%d: must be in [1, %d]", n_chan, sdrk::OLS_BANK_MAX_CHAN);
+    if (!shift_bins) return fail(SDRK_ERR_INVALID, "shift_bins pointer is NULL");
+    for (int c = 0; c < n_chan; ++c)
+        if (shift_bins[c] < -sdrk::OLS_N / 2 || shift_bins[c] >= sdrk::OLS_N / 2)
+            return fail(SDRK_ERR_INVALID, "shift_bins[%d]=%d: must be in [%d, %d]", c, shift_bins[c], -sdrk::OLS_N / 2, sdrk::OLS_N / 2 - 1);
+    return SDRK_OK;
+}
+
+int check_bank_device(const sdrk_plan* p, const void* d_in, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                      const void* d_out, size_t out_stride) {
+    int st = check_bank_call(p, decim, n_chan, shift_bins);
+    if (st == SDRK_OK) st = check_fir_device(p, d_in, n_in, decim, 0, d_out);
+    if (st != SDRK_OK) return st;
+    const size_t n_out = sdrk::ols_outputs(n_in, p->fir_taps, decim);
+    if (out_stride < n_out) return fail(SDRK_ERR_INVALID, "out_stride=%zu: a plane holds the %zu outputs of a channel", out_stride, n_out);
+    return SDRK_OK;
+}
+
+// One launch: the first max_blocks blocks (0: all) of every channel; phase0 == nullptr: zeros.
+int bank_launch(sdrk_plan* p, bool i16, const void* d_in, size_t n_in, int decim, int n_chan, const int* shift_bins, const int* phase0,
+                void* d_out, size_t out_stride, size_t max_blocks, hipStream_t stream) {
+    static const int zeros[sdrk::OLS_BANK_MAX_CHAN] = {};
+    sdrk::OlsBankArgs a;
+    a.d_in = d_in;
+    a.n_in = n_in;
+    a.taps = p->fir_taps;
+    a.decim = decim;
+    a.n_chan = n_chan;
+    a.shift_bins = shift_bins;
+    a.phase0 = phase0 ? phase0 : zeros;
+    a.d_h = p->d_fir_h;
+    a.d_twiddle = p->d_twiddle;
+    a.d_out = static_cast<float2*>(d_out);
+    a.out_stride = out_stride;
+    a.max_blocks = max_blocks;
+    a.num_cus = p->num_cus;
+    a.stream = stream;
+    const hipError_t e = i16 ? sdrk::launch_chanbank_i16(a) : sdrk::launch_chanbank(a);
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "channel bank kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
+int exec_device_bank(bool i16, sdrk_plan* p, const void* d_in, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                     const int* phase0, void* d_out, size_t out_stride, void* stream) {
+    int st = check_bank_device(p, d_in, n_in, decim, n_chan, shift_bins, d_out, out_stride);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    return bank_launch(p, i16, d_in, n_in, decim, n_chan, shift_bins, phase0, d_out, out_stride, 0,
+                       stream ? static_cast<hipStream_t>(stream) : p->stream);
+}
+
+// The chunk loop of the single call with C planes: per chunk, channel c's phase is s_c times the chunk's stream index.
+int exec_host_bank(size_t in_elem, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int decim, int n_chan,
+                   const int* shift_bins, uint64_t sample0, void* out, size_t out_stride, size_t* n_out) {
+    int st = check_bank_call(p, decim, n_chan, shift_bins);
+    if (st != SDRK_OK) return st;
+    const size_t need = (n + (size_t)decim - 1) / (size_t)decim;
+    if (out_stride < need) return fail(SDRK_ERR_INVALID, "out_stride=%zu: a plane holds up to %zu outputs of a channel", out_stride, need);
+    return host_fir_chunks(in_elem, p, prefix, iq, n, decim, sample0, (size_t)n_chan, out, out_stride, n_out,
+                           [&](const void* d_in, size_t cn, unsigned index, void* d_out, size_t nb, size_t co) {
+                               int phase[sdrk::OLS_BANK_MAX_CHAN];
+                               for (int c = 0; c < n_chan; ++c) {
+                                   const unsigned s_mod = (unsigned)shift_bins[c] & (unsigned)(sdrk::OLS_N - 1);
+                                   phase[c] = (int)((s_mod * index) & (unsigned)(sdrk::OLS_N - 1));
+                               }
+                               return bank_launch(p, in_elem == 4, d_in, cn, decim, n_chan, shift_bins, phase, d_out, co, nb, p->stream);
+                           });
 }
 
 }  // namespace
@@ -437,6 +524,36 @@ int sdrk_exec_host_fir(sdrk_plan* p, const void* prefix_c64, const void* iq_c64,
 int sdrk_exec_host_fir_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int shift_bins,
                             uint64_t sample0, void* out_c64, size_t* n_out) {
     return exec_host_fir(4, p, prefix_ci16, iq_ci16, n, decim, shift_bins, sample0, out_c64, n_out);
+}
+
+int sdrk_exec_device_chanbank(sdrk_plan* p, const void* d_in_c64, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                              const int* phase0, void* d_out_c64, size_t out_stride, void* stream) {
+    return exec_device_bank(false, p, d_in_c64, n_in, decim, n_chan, shift_bins, phase0, d_out_c64, out_stride, stream);
+}
+
+int sdrk_exec_device_chanbank_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                                   const int* phase0, void* d_out_c64, size_t out_stride, void* stream) {
+    return exec_device_bank(true, p, d_in_ci16, n_in, decim, n_chan, shift_bins, phase0, d_out_c64, out_stride, stream);
+}
+
+int sdrk_exec_device_chanbank_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, int decim, int n_chan, const int* shift_bins,
+                                         const int* phase0, void* d_out_c64, size_t out_stride, int launches, float* each_ms) {
+    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
+    int st = check_bank_device(p, d_in_c64, n_in, decim, n_chan, shift_bins, d_out_c64, out_stride);
+    if (st != SDRK_OK) return st;
+    return timed_each(p, launches, each_ms, [&] {
+        return bank_launch(p, false, d_in_c64, n_in, decim, n_chan, shift_bins, phase0, d_out_c64, out_stride, 0, p->stream);
+    });
+}
+
+int sdrk_exec_host_chanbank(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, int decim, int n_chan,
+                            const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
+    return exec_host_bank(sizeof(float2), p, prefix_c64, iq_c64, n, decim, n_chan, shift_bins, sample0, out_c64, out_stride, n_out);
+}
+
+int sdrk_exec_host_chanbank_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int n_chan,
+                                 const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
+    return exec_host_bank(4, p, prefix_ci16, iq_ci16, n, decim, n_chan, shift_bins, sample0, out_c64, out_stride, n_out);
 }
 
 }  // extern "C"

@@ -225,6 +225,7 @@ def pfb_prototype(nfft: int, taps: int, window: WindowArg = "hann") -> np.ndarra
 FIR_MAX_TAPS = 2049               # sdrk.h: taps of a FIR filter (overlap-save in blocks of 4096)
 FIR_MAX_DECIM = 256
 FIR_BLOCK = 4096
+FIR_BANK_MAX_CHANNELS = 64        # sdrk.h: channels of one channel-bank call
 
 
 def channel_taps(decim: int, ntaps: Optional[int] = None, window: WindowArg = "hann") -> np.ndarray:
@@ -263,6 +264,17 @@ def _fir_args(decim, shift_bins):
     if not -FIR_BLOCK // 2 <= shift_bins < FIR_BLOCK // 2:
         raise ValueError(f"shift_bins must be in {-FIR_BLOCK // 2}..{FIR_BLOCK // 2 - 1}, got {shift_bins}")
     return decim, shift_bins
+
+
+def _bank_shifts(shift_bins):
+    """The tuning offsets of a channel-bank call as a ctypes int array: 1..64 of them, each a whole bin in -2048..2047."""
+    shifts = [int(v) for v in np.asarray(shift_bins).reshape(-1)]
+    if not 1 <= len(shifts) <= FIR_BANK_MAX_CHANNELS:
+        raise ValueError(f"a channel bank takes 1..{FIR_BANK_MAX_CHANNELS} shift_bins, got {len(shifts)}")
+    for v in shifts:
+        _fir_args(1, v)
+    return (c_int * len(shifts))(*shifts)
+
 
 
 class _Mode(NamedTuple):
@@ -1049,6 +1061,86 @@ class SpectrumPlan:
         check(lib().sdrk_exec_device_fir_timed_each(*args, int(launches), each))
         return list(each)
 
+    # -- channel bank: C tuned channels from one pass over the input (the filter of set_fir) ---------------------------------
+    def _host_fir_bank(self, sym: str, x: np.ndarray, prefix, shift_bins, decim: int, sample0: int) -> np.ndarray:
+        decim, _ = _fir_args(decim, 0)
+        shifts = _bank_shifts(shift_bins)
+        if int(sample0) < 0:
+            raise ValueError("sample0 must be >= 0")
+        n = int(x.shape[0])
+        stride = (n + decim - 1) // decim
+        out = np.empty((len(shifts), stride), dtype=np.complex64)
+        n_out = c_size_t(0)
+        with self._lock:
+            check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
+                                      x.ctypes.data_as(c_void_p), c_size_t(n), decim, len(shifts), shifts,
+                                      _ffi.c_uint64(int(sample0)), out.ctypes.data_as(c_void_p), c_size_t(stride), byref(n_out)))
+        return np.ascontiguousarray(out[:, : n_out.value])
+
+    def fir_bank(self, iq, shift_bins, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``fir`` for ``C = len(shift_bins)`` channels at once (1..64, duplicates allowed), from ONE pass over ``iq``: row
+        ``c`` of the ``(C, n_out)`` complex64 result carries the bits of ``fir(iq, decim=decim, shift_bins=shift_bins[c],
+        prefix=prefix, sample0=sample0)``.  The input is read once and every block transformed once; only the channel-dependent
+        half (rotated filter, inverse transform, mixer, decimated store) runs per channel."""
+        m = self._fir_ready()
+        x = _as_c64(iq).reshape(-1)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_c64(prefix).reshape(-1)
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return self._host_fir_bank("sdrk_exec_host_chanbank", x, pre, shift_bins, decim, sample0)
+
+    def fir_bank_ci16(self, iq, shift_bins, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``fir_bank`` on interleaved int16 I,Q of shape ``(n, 2)`` (``prefix``: ``(M - 1, 2)`` int16): the bits of
+        ``fir_bank`` on the widened samples."""
+        m = self._fir_ready()
+        x = _as_ci16(iq, stream=True)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_ci16(prefix, stream=True)
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return self._host_fir_bank("sdrk_exec_host_chanbank_ci16", x, pre, shift_bins, decim, sample0)
+
+    def _device_fir_bank_args(self, d_in: int, n_in: int, d_out: int, shift_bins, decim: int, phase0, out_stride) -> list:
+        decim, _ = _fir_args(decim, 0)
+        shifts = _bank_shifts(shift_bins)
+        n_out = self.fir_outputs(n_in, decim)
+        stride = n_out if out_stride is None else int(out_stride)
+        if stride < n_out:
+            raise ValueError(f"out_stride={stride}: a plane holds the {n_out} outputs of a channel")
+        phases = None
+        if phase0 is not None:
+            ph = [int(v) & (FIR_BLOCK - 1) for v in np.asarray(phase0).reshape(-1)]
+            if len(ph) != len(shifts):
+                raise ValueError(f"phase0 must hold one value per channel ({len(shifts)}), got {len(ph)}")
+            phases = (c_int * len(ph))(*ph)
+        return [c_void_p(d_in), c_size_t(int(n_in)), decim, len(shifts), shifts, phases, c_void_p(d_out), c_size_t(stride)]
+
+    def exec_device_fir_bank(self, d_in: int, n_in: int, d_out: int, shift_bins, *, decim: int = 1, phase0=None,
+                             out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """Device pointers: ``exec_device_fir`` for ``len(shift_bins)`` channels from one pass.  Plane ``c`` starts at
+        ``d_out + 8 * c * out_stride`` (default: packed, ``fir_outputs(n_in, decim)`` apart) and carries the bits of
+        ``exec_device_fir(..., shift_bins=shift_bins[c], phase0=phase0[c])`` (``phase0``: one value per channel, default zeros);
+        asynchronous on ``stream`` (0: the plan's stream)."""
+        args = self._device_fir_bank_args(d_in, n_in, d_out, shift_bins, decim, phase0, out_stride)
+        check(lib().sdrk_exec_device_chanbank(self.handle, *args, c_void_p(stream) if stream else None))
+
+    def exec_device_fir_bank_ci16(self, d_in: int, n_in: int, d_out: int, shift_bins, *, decim: int = 1, phase0=None,
+                                  out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """``exec_device_fir_bank`` on int16 I,Q input (4 bytes per sample)."""
+        args = self._device_fir_bank_args(d_in, n_in, d_out, shift_bins, decim, phase0, out_stride)
+        check(lib().sdrk_exec_device_chanbank_ci16(self.handle, *args, c_void_p(stream) if stream else None))
+
+    def exec_device_fir_bank_timed_each(self, d_in: int, n_in: int, d_out: int, shift_bins, launches: int = 1, *, decim: int = 1,
+                                        phase0=None, out_stride: Optional[int] = None) -> list:
+        """``exec_device_fir_bank`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_fir_bank_args(d_in, n_in, d_out, shift_bins, decim, phase0, out_stride)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_chanbank_timed_each(self.handle, *args, int(launches), each))
+        return list(each)
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -1499,6 +1591,17 @@ def fir_filter(iq, taps, decim: int = 1, shift_bins: int = 0, *, device: int = 0
     return plan.fir(iq, decim=decim, shift_bins=shift_bins)
 
 
+def fir_bank(iq, taps, shift_bins, decim: int = 1, *, device: int = 0) -> np.ndarray:
+    """``SpectrumPlan.fir_bank`` on a cached plan that holds ``taps``: ``fir_filter(iq, taps, decim, shift_bins[c])`` for every
+    channel ``c`` from one pass over ``iq``, as a ``(C, n_out)`` array.  int16 ``(n, 2)`` input takes the int16 entry."""
+    _fir_args(decim, 0)
+    _bank_shifts(shift_bins)
+    plan = _cached_fir_plan(taps, device)
+    if isinstance(iq, np.ndarray) and iq.dtype == np.int16:
+        return plan.fir_bank_ci16(iq, shift_bins, decim=decim)
+    return plan.fir_bank(iq, shift_bins, decim=decim)
+
+
 class ChannelStream:
     """One channel out of a stream that arrives in pieces: tuned to ``offset_hz`` from the centre, low-passed by ``taps``,
     decimated by ``decim``.  The offset is rounded to a whole bin of ``sample_rate/4096`` (``shift_bins``; ``tuned_hz`` is the
@@ -1533,6 +1636,58 @@ class ChannelStream:
             return np.empty(0, dtype=np.complex64)
         run = self.plan.fir_ci16 if ci16 else self.plan.fir
         out = run(x, decim=self.decim, shift_bins=self.shift_bins, prefix=self._tail, sample0=self.sample_index)
+        keep = self.ntaps - 1
+        if keep:
+            if self._tail is None:
+                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
+            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+        self.sample_index += n
+        return out
+
+    def close(self) -> None:
+        if self._own:
+            self.plan.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ChannelBankStream:
+    """``C`` channels out of a stream that arrives in pieces, from one pass over each piece: ``ChannelStream`` for every offset
+    of ``offsets_hz`` (1..64 of them, each rounded to a whole bin of ``sample_rate/4096``), with one filter, one decimation and
+    ONE kept tail for all channels.  ``push(iq)`` returns the ``(C, n)`` complex64 samples the piece completes; row ``c`` carries
+    the bits of a ``ChannelStream`` tuned to ``offsets_hz[c]`` that was pushed the same pieces.  ``shift_bins``, ``tuned_hz``:
+    one entry per channel."""
+
+    def __init__(self, plan, taps, decim: int, offsets_hz, sample_rate: float, *, device: int = 0):
+        self.decim, _ = _fir_args(decim, 0)
+        self.sample_rate = float(sample_rate)
+        if not self.sample_rate > 0:
+            raise ValueError("sample_rate must be positive")
+        bin_hz = self.sample_rate / FIR_BLOCK
+        self.shift_bins = [int(np.rint(float(f) / bin_hz)) for f in np.asarray(offsets_hz, dtype=np.float64).reshape(-1)]
+        _bank_shifts(self.shift_bins)                      # too few, too many, an offset beyond the band: ValueError
+        self.tuned_hz = [s * bin_hz for s in self.shift_bins]
+        self.out_rate = self.sample_rate / self.decim
+        self._own = plan is None
+        self.plan = SpectrumPlan(FIR_BLOCK, device=device) if plan is None else plan
+        self.ntaps = int(self.plan.set_fir(taps))
+        self.sample_index = 0                              # stream index of the next input sample
+        self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
+
+    def push(self, iq) -> np.ndarray:
+        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
+        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
+        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
+            raise ValueError("a ChannelBankStream takes complex or int16 pieces, not both")
+        n = int(x.shape[0])
+        if n == 0:
+            return np.empty((len(self.shift_bins), 0), dtype=np.complex64)
+        run = self.plan.fir_bank_ci16 if ci16 else self.plan.fir_bank
+        out = run(x, self.shift_bins, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
         keep = self.ntaps - 1
         if keep:
             if self._tail is None:

@@ -17,6 +17,7 @@ if not _os.path.isdir(_SRC_DIR):  # pragma: no cover - broken checkout
 __path__.append(_SRC_DIR)
 
 from .spectrum import (  # noqa: E402
+    ChannelBankStream,
     ChannelStream,
     CrossSpectrum,
     SpectrumPlan,
@@ -25,6 +26,7 @@ from .spectrum import (  # noqa: E402
     fft_c64,
     fft_c128,
     fft_ci16,
+    fir_bank,
     fir_filter,
     freq_axis,
     integrated_db,
@@ -52,6 +54,7 @@ from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
 from ._ffi import SdrkError, device_count, device_info, library_path  # noqa: E402
 
 __all__ = [
+    "ChannelBankStream",
     "ChannelStream",
     "CrossSpectrum",
     "SpectrumPlan",
@@ -64,6 +67,7 @@ __all__ = [
     "fft_c64",
     "fft_c128",
     "fft_ci16",
+    "fir_bank",
     "fir_filter",
     "freq_axis",
     "integrated_db",

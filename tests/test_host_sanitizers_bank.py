@@ -1,0 +1,31 @@
+"""Sanitizer legs for the host side of the channel-bank entry points (CPU).
+
+csrc/pfb_api.hip (sdrk_exec_device_chanbank*, sdrk_exec_host_chanbank* and the chunk loop they share with the single-channel FIR
+call, on the pinned staging slots) and the other host files of csrc/ (tests/host_sources.py), compiled with g++ against the
+stand-in runtime of tests/fake_hip and the stand-in kernels tests/fake_*_kernels.cpp (fake_bank_kernels.cpp among them: the real
+block geometry, one forward transform per block, the shared arithmetic of csrc/kernels_ols.h per channel), driven by the
+stand-alone program tests/host_api_bank_stress.cpp under ThreadSanitizer and under AddressSanitizer + UBSan with leak checking.
+Nothing is loaded into Python, nothing is preloaded.  Three threads on their own plans; both formats; device, timed and host
+entries; chunks of three blocks with a prefix and without; C = 1, 3 and 64; every output element of every channel compared with
+the single-channel call; the refusals; a single-channel call and a PFB call between bank calls on one plan."""
+import os
+import subprocess
+
+import pytest
+
+from tests.host_sources import SANITIZERS, build_driver
+
+
+@pytest.mark.parametrize("san", list(SANITIZERS))
+def test_channel_bank_host_entry_points_under_sanitizers(san):
+    env = dict(os.environ, SDRK_HOST_THREADS="3", SDRK_FIR_CHUNK_BLOCKS="3",
+               TSAN_OPTIONS="halt_on_error=1 exitcode=66", ASAN_OPTIONS="detect_leaks=1 exitcode=67",
+               UBSAN_OPTIONS="halt_on_error=1 print_stacktrace=1")
+    r = subprocess.run([build_driver(san, "host_api_bank_stress.cpp"), "3", "1"], capture_output=True, text=True, env=env, timeout=900)
+    print(r.stdout)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-4000:])
+    assert "bad=0" in r.stdout and "sdrk 500 bank threads=3" in r.stdout
+    compared = int(r.stdout.split("compared=")[1].split()[0])
+    # every output sample of every channel of every case, from every thread (the cases are fixed: 1,458,380 floats in all)
+    assert compared > 1_400_000, r.stdout
+    assert int(r.stdout.split("refused=")[1].split()[0]) == 2 * 48              # (every refusal of mode_refusals, from both formats)
