@@ -18,7 +18,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "host_pool.h"
 #include "kernels_integrate.h"
 #include "kernels_xspec.h"
 #include "plan_internal.h"
@@ -243,7 +242,8 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     int st = check_call_args(io, p, iq, n_groups, k_frames, frame_stride, detector, out_form, out);
     if (st != SDRK_OK) return st;
     HIP_TRY(hipSetDevice(p->device));
-    st = ensure_copy_streams(p);
+    SlotPipe pipe;
+    st = pipe.open(p, "host pipeline");
     if (st != SDRK_OK) return st;
     IntCall c;
     st = call_begin(c, io, p, n_groups, k_frames, frame_stride, detector, out_form, scale, p->stream);
@@ -264,45 +264,26 @@ inline int exec_host_integrated(const IntIo& io, sdrk_plan* p, const void* iq, s
     const size_t in_bytes = ((n_frames - 1) * frame_stride + span) * elem;
     const size_t out_bytes = n_groups * group_bytes;
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
-    auto retire = [&](HostSlot& s) -> int {
-        if (!s.busy) return SDRK_OK;
-        s.busy = false;
-        HIP_TRY(hipEventSynchronize(s.ev_done));
-        if (s.user_out && s.out_bytes) sdrk::CopyPool::get().copy(s.user_out, s.h_out, s.out_bytes);
-        return SDRK_OK;
-    };
-    auto bail = [&](int status) { slots_abandon(p); (void)call_end(c, status); return status; };
-    size_t n = 0;
-    for (size_t f0 = 0; f0 < n_frames; f0 += per, ++n) {
-        HostSlot& s = p->slot[n % HOST_SLOTS];
+    const ChunkOut::Rows via = out_pinned ? ChunkOut::Direct : ChunkOut::Pooled;
+    for (size_t f0 = 0; f0 < n_frames; f0 += per) {
         const size_t f1 = n_frames - f0 < per ? n_frames : f0 + per;
         const size_t cin = ((f1 - f0 - 1) * frame_stride + span) * elem;
+        // (a chunk in which no group ends brings back 0 bytes: its slot still completes through the D2H stream)
         const size_t row0 = f0 / K, rows = direct ? f1 / K - row0 : 0, cout = rows * group_bytes;
-        st = retire(s);
-        if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);
-        if (st != SDRK_OK) return bail(st);
-        const void* src = chunk_pinned_src(s, static_cast<const char*>(iq) + f0 * frame_stride * elem, cin, in_pinned);
-        hipError_t e = stage_chunk_in(p, s, src, cin);
-        if (e == hipSuccess) {
-            st = call_range(c, s.d_in, f0, f1, static_cast<float*>(s.d_out), row0);
-            if (st != SDRK_OK) return bail(st);
-            e = hipEventRecord(s.ev_k, p->stream);
-        }
-        float* user_rows = out + row0 * c.group_floats;
-        if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
-        if (e == hipSuccess && cout)
-            e = hipMemcpyAsync(out_pinned ? static_cast<void*>(user_rows) : s.h_out, s.d_out, cout, hipMemcpyDeviceToHost, p->s_d2h);
-        if (e == hipSuccess) e = hipEventRecord(s.ev_done, p->s_d2h);
-        if (e != hipSuccess) return bail(fail(SDRK_ERR_HIP, "host pipeline failed: %s", hipGetErrorString(e)));
-        s.busy = true;
-        s.user_out = out_pinned ? nullptr : user_rows;
-        s.out_bytes = cout;
+        HostSlot* s = nullptr;
+        st = pipe.acquire(chunk_in, chunk_out, s);
+        if (st != SDRK_OK) return call_end(c, st);
+        const void* src = chunk_pinned_src(*s, static_cast<const char*>(iq) + f0 * frame_stride * elem, cin, in_pinned);
+        st = pipe.upload(*s, src, cin);
+        if (st == SDRK_OK)
+            st = pipe.submit(*s, call_range(c, s->d_in, f0, f1, static_cast<float*>(s->d_out), row0),
+                             {via, out + row0 * c.group_floats, cout});
+        if (st != SDRK_OK) return call_end(c, st);
     }
-    for (size_t i = 0; i < HOST_SLOTS; ++i) {   // drain in submission order
-        st = retire(p->slot[(n + i) % HOST_SLOTS]);
-        if (st != SDRK_OK) return bail(st);
-    }
+    st = pipe.drain();
+    if (st != SDRK_OK) return call_end(c, st);
     if (!direct) {   // fewer groups than the device has workgroups: a handful of rows
+        auto bail = [&](int status) { slots_abandon(p); return call_end(c, status); };
         HostSlot& s = p->slot[0];
         st = slot_reserve(p, s, 0, out_bytes);
         if (st == SDRK_OK) st = call_finalize(c, static_cast<float*>(s.d_out));

@@ -46,20 +46,7 @@ __global__ __launch_bounds__(256) void integrate_rows_kernel(const float2* __res
 
 hipError_t launch_integrate_rows(const IntegrateArgs& a) {
     if (a.f1 <= a.f0) return hipSuccess;
-    IntUnits c;
-    const IntSplit sp{a.slices, a.slice_len};
-    c.f0 = a.f0;
-    c.f1 = a.f1;
-    c.k = a.k;
-    c.slice_len = a.slice_len;
-    c.slices = (unsigned)a.slices;
-    c.u_first = integrate_unit_of(a.f0, a.k, sp);
-    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
-    c.out_row0 = a.out_row0;
-    c.out_form = a.out_form;
-    c.scale = a.scale;
-    c.eps = a.eps;
-    c.inv_k = 1.0f / (float)a.k;
+    const IntUnits c = int_units(a);
     const unsigned col_blocks = (unsigned)((a.nfft + 255) / 256);
     const size_t n_items = (c.u_last - c.u_first + 1) * col_blocks;
     const size_t cap = (size_t)a.num_cus * 32;

@@ -54,6 +54,25 @@ struct IntUnits {
     float scale, eps, inv_k;
 };
 
+// ... of a launch's arguments (f1 > f0); a launcher that fixes the output form overrides out_form and eps behind it
+inline IntUnits int_units(const IntegrateArgs& a) {
+    IntUnits c;
+    const IntSplit sp{a.slices, a.slice_len};
+    c.f0 = a.f0;
+    c.f1 = a.f1;
+    c.k = a.k;
+    c.slice_len = a.slice_len;
+    c.slices = (unsigned)a.slices;
+    c.u_first = integrate_unit_of(a.f0, a.k, sp);
+    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
+    c.out_row0 = a.out_row0;
+    c.out_form = a.out_form;
+    c.scale = a.scale;
+    c.eps = a.eps;
+    c.inv_k = 1.0f / (float)a.k;
+    return c;
+}
+
 struct IntUnit {
     size_t g, fb, fe;     // group; frames [fb, fe) of the unit that this launch covers
     bool starts, ends;    // the unit begins / is complete within this launch

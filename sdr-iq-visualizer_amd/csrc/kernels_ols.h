@@ -1,4 +1,4 @@
-// kernels_ols.h — interface between pfb_api.hip and the overlap-save FIR kernel (ols4096.hip), and the one place the arithmetic
+// kernels_ols.h — interface between fir_api.hip and the overlap-save FIR kernel (ols4096.hip), and the one place the arithmetic
 // of a block is written: the kernel and the host stand-in (tests/fake_ols_kernels.cpp) both call the functions below.
 //
 // A block is 4096 consecutive samples.  With M taps, L = ols_block_len(M) outputs come out of each block; block b reads samples

@@ -1,4 +1,4 @@
-// kernels_ols_bank.h — interface between pfb_api.hip and the channel-bank kernel (ols_bank.hip): C channels out of one pass over
+// kernels_ols_bank.h — interface between fir_api.hip and the channel-bank kernel (ols_bank.hip): C channels out of one pass over
 // the input.  The block geometry and every formula are kernels_ols.h's; channel c of a bank launch carries the bits of
 // launch_ols4096 with (shift_bins[c], phase0[c]) on the same input.  tests/fake_bank_kernels.cpp is the host stand-in.
 #pragma once

@@ -36,20 +36,7 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void pfb4096_groups_kernel(
 hipError_t launch_pfb4096_groups(const IntegrateArgs& a) {
     if (a.f1 <= a.f0) return hipSuccess;
     if (a.nfft != F4K_N || a.d_window || !a.d_pfb_h || a.pfb_taps < 1 || a.pfb_taps > PFB_MAX_TAPS) return hipErrorInvalidValue;
-    IntUnits c;
-    const IntSplit sp{a.slices, a.slice_len};
-    c.f0 = a.f0;
-    c.f1 = a.f1;
-    c.k = a.k;
-    c.slice_len = a.slice_len;
-    c.slices = (unsigned)a.slices;
-    c.u_first = integrate_unit_of(a.f0, a.k, sp);
-    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
-    c.out_row0 = a.out_row0;
-    c.out_form = a.out_form;
-    c.scale = a.scale;
-    c.eps = a.eps;
-    c.inv_k = 1.0f / (float)a.k;
+    const IntUnits c = int_units(a);
     dim3 g(f4k_grid(a.num_cus, F4K_WAVES, c.u_last - c.u_first + 1)), b(F4K_THREADS);
     const float2* iq = static_cast<const float2*>(a.d_in);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);

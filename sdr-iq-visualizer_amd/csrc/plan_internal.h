@@ -16,16 +16,26 @@
 
 namespace sdrk_host {
 constexpr int HOST_SLOTS = 3;
+// What a chunk of a SlotPipe brings back, and how that reaches the caller's array `user` when the chunk's slot retires.
+struct ChunkOut {
+    enum Rows {
+        None,     // nothing per chunk: ev_k ends the chunk, the D2H stream is not touched
+        Pooled,   // D2H into h_out; at retire the helper threads copy h_out -> user
+        Direct,   // D2H straight into the caller's pinned array; nothing at retire
+        Kernel,   // the kernel wrote h_out itself (zero-copy): ev_done follows it on the plan's stream; then as Pooled
+        Planes,   // D2H of `planes` packed planes into h_out; at retire a memcpy of each -> user + i * plane_stride bytes
+    } rows = None;
+    void* user = nullptr;
+    size_t bytes = 0;   // of one plane; 0: no copy either way
+    size_t planes = 1, plane_stride = 0;
+};
 struct HostSlot {
     void *h_in = nullptr, *h_out = nullptr;   // pinned
     void *d_in = nullptr, *d_out = nullptr;
     size_t in_cap = 0, out_cap = 0;
     hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_done = nullptr;
-    // the chunk in flight in this slot (busy == true): where its rows go once ev_done has fired
-    // (user_out == nullptr: the rows were DMA'd straight into the caller's pinned array)
-    bool busy = false;
-    void* user_out = nullptr;
-    size_t out_bytes = 0;
+    bool busy = false;   // a chunk is in flight in this slot: `out` is what it brings back
+    ChunkOut out;
 };
 
 // Plan-owned device staging that calls on any stream share: growing buffers under one ordering.  `ev` follows the last work
@@ -119,7 +129,7 @@ struct sdrk_plan {
     int pfb_taps = 0;
     int pfb_assign = 0;
     sdrk_host::Staging pfb;
-    // FIR filtering and channel extraction (pfb_api.hip): d_fir_h = DFT_4096 of the zero-padded taps, 4096 complex64 in natural
+    // FIR filtering and channel extraction (fir_api.hip): d_fir_h = DFT_4096 of the zero-padded taps, 4096 complex64 in natural
     // bin order (sdrk_plan_set_fir; 0 taps = none); fir_assign = ols4096_kernel's block assignment (kernels_ols.h)
     float2* d_fir_h = nullptr;
     int fir_taps = 0;
@@ -289,12 +299,38 @@ struct HostIo {
 
 int slot_reserve(sdrk_plan* p, HostSlot& s, size_t in_bytes, size_t out_bytes);   // events and staging of at least these sizes
 void slots_abandon(sdrk_plan* p);   // error path: nothing may still be writing into the staging buffers
-int ensure_copy_streams(sdrk_plan* p);   // s_h2d / s_d2h, created at the first chunked call
 // Where a copy engine (or, on the zero-copy branch, the kernel) reads a chunk of the caller's input: the caller's own array
 // if it is pinned, else the slot's pinned h_in, filled by the helper threads.
 const void* chunk_pinned_src(HostSlot& s, const void* src, size_t bytes, bool in_pinned);
-// The pinned chunk -> the slot's d_in on s_h2d; ev_in behind it, and the plan's stream waits for that.
-hipError_t stage_chunk_in(sdrk_plan* p, HostSlot& s, const void* pinned_src, size_t bytes);
+
+// The chunks of one host call through the plan's HOST_SLOTS staging slots: the ordering every chunked entry point shares,
+// written once.  Per chunk the caller runs acquire -> (fills or picks the pinned input) -> upload -> its launch on the plan's
+// stream -> submit, and drain after the last chunk; how chunks are cut, what is launched and what comes back stay with the
+// caller.  Every step that fails has abandoned the slots before it returns the status.
+struct SlotPipe {
+    sdrk_plan* p = nullptr;
+    const char* what = nullptr;   // names the pipeline in a failure's text
+    size_t n = 0;                 // chunks submitted so far: chunk n takes slot n % HOST_SLOTS
+    // optional: called around a retire's wait (0 before, 1 after) and after its delivery (2) — exec_host's SDRK_HOST_TRACE
+    void (*mark)(void* ctx, int point) = nullptr;
+    void* mark_ctx = nullptr;
+
+    int open(sdrk_plan* plan, const char* name);                   // s_h2d / s_d2h, created at the first chunked call
+    // the next chunk's slot: waits for the chunk in flight there and delivers it, then staging of at least these sizes
+    int acquire(size_t chunk_in, size_t chunk_out, HostSlot*& s);
+    // the pinned chunk -> the slot's d_in on s_h2d; ev_in behind it, and the plan's stream waits for that
+    int upload(HostSlot& s, const void* pinned_src, size_t bytes);
+    // behind the caller's launch (launch_st: its status): ev_k on the plan's stream, then what `out` says — s_d2h waits for
+    // ev_k, copies out.planes * out.bytes from d_out (no copy of 0 bytes) and records ev_done; ChunkOut::None stops at ev_k;
+    // ChunkOut::Kernel records ev_done on the plan's stream and nothing else
+    int submit(HostSlot& s, int launch_st, const ChunkOut& out);
+    int drain();                                                   // retires the chunks in flight, in submission order
+
+private:
+    int retire(HostSlot& s);
+    int hip_failed(hipError_t e);
+};
+
 // the small mapped call, the zero-copy chunks and the three-slot pipeline of sdrk_exec_host, for any element sizes
 int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride, void* out, const HostIo& io);
 

@@ -262,44 +262,31 @@ int frame_features_host_impl(sdrk_plan* p, const void* iq, size_t n_frames, size
         // helper threads stage chunk c+1 (or the copy engine reads the caller's pinned array directly) while chunk
         // c crosses PCIe and chunk c-1 is measured.  The per-row results stay on the device until the end (they are
         // ~1 % of the input).
-        st = ensure_copy_streams(p);
+        // A slot is free once its chunk is measured (ChunkOut::None): nothing comes back per chunk, and no drain — the one
+        // stream sync behind the results below covers every chunk.
+        SlotPipe pipe;
+        st = pipe.open(p, "feature pipeline");
         if (st != SDRK_OK) return st;
         const size_t stride_bytes = (frame_stride ? frame_stride : 1) * sizeof(float2);
         size_t per = HOST_CHUNK_BYTES / stride_bytes;
         if (per < 1) per = 1;
         const size_t chunk_in = ((per - 1) * frame_stride + nfft) * sizeof(float2);
         const bool in_pinned = pinned_ranges().covers(iq, in_bytes);
-        size_t c = 0;
-        for (size_t f0 = 0; f0 < n_frames; f0 += per, ++c) {
-            HostSlot& s = p->slot[c % HOST_SLOTS];
+        for (size_t f0 = 0; f0 < n_frames; f0 += per) {
             const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
             const size_t cin = ((nf - 1) * frame_stride + nfft) * sizeof(float2);
-            hipError_t e = hipSuccess;
-            if (s.busy) {                                         // chunk c - HOST_SLOTS: measured, its staging is free
-                e = hipEventSynchronize(s.ev_k);
-                s.busy = false;
-            }
-            if (e == hipSuccess) {
-                st = slot_reserve(p, s, chunk_in, 0);
-                if (st != SDRK_OK) { slots_abandon(p); return st; }
-                const void* src = static_cast<const float2*>(iq) + f0 * frame_stride;
-                e = stage_chunk_in(p, s, chunk_pinned_src(s, src, cin, in_pinned), cin);
-            }
-            if (e != hipSuccess) {
-                slots_abandon(p);
-                return fail(SDRK_ERR_HIP, "feature pipeline failed: %s", hipGetErrorString(e));
-            }
-            st = sdrk_frame_features_device(p, s.d_in, nf, frame_stride, d_rows ? d_rows + f0 * nfft : nullptr, rank, gamma,
-                                            min_distance, max_peaks, d_stats + f0 * 16, d_thr + f0,
-                                            d_idx ? d_idx + f0 * (size_t)max_peaks : nullptr, d_cnt ? d_cnt + f0 : nullptr, nullptr);
-            if (st != SDRK_OK) { slots_abandon(p); return st; }
-            e = hipEventRecord(s.ev_k, p->stream);
-            if (e != hipSuccess) {
-                slots_abandon(p);
-                return fail(SDRK_ERR_HIP, "feature pipeline failed: %s", hipGetErrorString(e));
-            }
-            s.busy = true;
-            s.user_out = nullptr;
+            HostSlot* s = nullptr;
+            st = pipe.acquire(chunk_in, 0, s);
+            if (st != SDRK_OK) return st;
+            const void* src = static_cast<const float2*>(iq) + f0 * frame_stride;
+            st = pipe.upload(*s, chunk_pinned_src(*s, src, cin, in_pinned), cin);
+            if (st == SDRK_OK)
+                st = pipe.submit(*s, sdrk_frame_features_device(p, s->d_in, nf, frame_stride, d_rows ? d_rows + f0 * nfft : nullptr,
+                                                                rank, gamma, min_distance, max_peaks, d_stats + f0 * 16, d_thr + f0,
+                                                                d_idx ? d_idx + f0 * (size_t)max_peaks : nullptr,
+                                                                d_cnt ? d_cnt + f0 : nullptr, nullptr),
+                                 ChunkOut{});
+            if (st != SDRK_OK) return st;
         }
     }
     // the results come back through ONE exit: whatever fails from here on, no chunk of the pipelined form may still be

@@ -1,6 +1,7 @@
 // sdrk_host_pipeline.hip — the numpy boundary of include/sdrk.h (sdrk_exec_host, sdrk_exec_fft_host, sdrk_welch_psd_host and,
-// through sdrk_host::exec_host, their float64 forms): the small mapped call, zero-copy chunks, and the three pinned staging
-// slots that sdrk_features.hip's chunked path shares.  Host code only.
+// through sdrk_host::exec_host, their float64 forms): the small mapped call, zero-copy chunks, and SlotPipe — the order in which
+// a chunk goes through the three pinned staging slots — which the chunked paths of sdrk_features.hip, integrate_call.h and
+// fir_api.hip run on as well.  Host code only.
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
@@ -47,41 +48,11 @@ int slot_reserve(sdrk_plan* p, HostSlot& s, size_t in_bytes, size_t out_bytes) {
     return SDRK_OK;
 }
 
-namespace {
-
-struct HostTrace {   // SDRK_HOST_TRACE=1: where a pipelined sdrk_exec_host call spends its wall time (stderr)
-    bool on = false;
-    double t_in = 0, t_wait = 0, t_out = 0;
-    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-};
-
-// Wait for the chunk in flight in slot `s` and hand its rows to the caller's array.
-int slot_retire(HostSlot& s, HostTrace& tr) {
-    if (!s.busy) return SDRK_OK;
-    s.busy = false;
-    const double t0 = tr.on ? HostTrace::now() : 0;
-    HIP_TRY(hipEventSynchronize(s.ev_done));
-    const double t1 = tr.on ? HostTrace::now() : 0;
-    if (s.user_out) sdrk::CopyPool::get().copy(s.user_out, s.h_out, s.out_bytes);
-    if (tr.on) { tr.t_wait += t1 - t0; tr.t_out += HostTrace::now() - t1; }
-    return SDRK_OK;
-}
-
-}  // namespace
-
 void slots_abandon(sdrk_plan* p) {   // error path: nothing may still be writing into the staging buffers
     (void)hipStreamSynchronize(p->s_h2d);
     (void)hipStreamSynchronize(p->stream);
     (void)hipStreamSynchronize(p->s_d2h);
     for (auto& s : p->slot) s.busy = false;
-}
-
-int ensure_copy_streams(sdrk_plan* p) {
-    if (!p->s_h2d) {
-        HIP_TRY(hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p->s_d2h, hipStreamNonBlocking));
-    }
-    return SDRK_OK;
 }
 
 const void* chunk_pinned_src(HostSlot& s, const void* src, size_t bytes, bool in_pinned) {
@@ -90,12 +61,103 @@ const void* chunk_pinned_src(HostSlot& s, const void* src, size_t bytes, bool in
     return s.h_in;
 }
 
-hipError_t stage_chunk_in(sdrk_plan* p, HostSlot& s, const void* pinned_src, size_t bytes) {
+int SlotPipe::open(sdrk_plan* plan, const char* name) {
+    p = plan;
+    what = name;
+    if (!p->s_h2d) {
+        HIP_TRY(hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&p->s_d2h, hipStreamNonBlocking));
+    }
+    return SDRK_OK;
+}
+
+int SlotPipe::hip_failed(hipError_t e) {
+    slots_abandon(p);
+    return fail(SDRK_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
+// Wait for the chunk in flight in slot `s` and hand what it brought back to the caller's array.
+int SlotPipe::retire(HostSlot& s) {
+    if (!s.busy) return SDRK_OK;
+    s.busy = false;
+    const ChunkOut& o = s.out;
+    if (mark) mark(mark_ctx, 0);
+    const hipError_t e = hipEventSynchronize(o.rows == ChunkOut::None ? s.ev_k : s.ev_done);
+    if (e != hipSuccess) return hip_failed(e);
+    if (mark) mark(mark_ctx, 1);
+    if (o.rows == ChunkOut::Planes) {
+        for (size_t i = 0; i < o.planes; ++i)
+            memcpy(static_cast<char*>(o.user) + i * o.plane_stride, static_cast<char*>(s.h_out) + i * o.bytes, o.bytes);
+    } else if ((o.rows == ChunkOut::Pooled || o.rows == ChunkOut::Kernel) && o.bytes) {
+        sdrk::CopyPool::get().copy(o.user, s.h_out, o.bytes);
+    }
+    if (mark) mark(mark_ctx, 2);
+    return SDRK_OK;
+}
+
+int SlotPipe::acquire(size_t chunk_in, size_t chunk_out, HostSlot*& s) {
+    s = &p->slot[n % HOST_SLOTS];
+    int st = retire(*s);                                       // chunk n - HOST_SLOTS: delivered, slot free
+    if (st != SDRK_OK) return st;
+    st = slot_reserve(p, *s, chunk_in, chunk_out);
+    if (st != SDRK_OK) slots_abandon(p);
+    return st;
+}
+
+int SlotPipe::upload(HostSlot& s, const void* pinned_src, size_t bytes) {
     hipError_t e = hipMemcpyAsync(s.d_in, pinned_src, bytes, hipMemcpyHostToDevice, p->s_h2d);
     if (e == hipSuccess) e = hipEventRecord(s.ev_in, p->s_h2d);
     if (e == hipSuccess) e = hipStreamWaitEvent(p->stream, s.ev_in, 0);
-    return e;
+    return e == hipSuccess ? SDRK_OK : hip_failed(e);
 }
+
+int SlotPipe::submit(HostSlot& s, int launch_st, const ChunkOut& out) {
+    if (launch_st != SDRK_OK) {
+        slots_abandon(p);
+        return launch_st;
+    }
+    hipError_t e;
+    if (out.rows == ChunkOut::Kernel) {
+        e = hipEventRecord(s.ev_done, p->stream);
+    } else {
+        e = hipEventRecord(s.ev_k, p->stream);
+        if (out.rows != ChunkOut::None) {
+            if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
+            if (e == hipSuccess && out.bytes)
+                e = hipMemcpyAsync(out.rows == ChunkOut::Direct ? out.user : s.h_out, s.d_out, out.planes * out.bytes,
+                                   hipMemcpyDeviceToHost, p->s_d2h);
+            if (e == hipSuccess) e = hipEventRecord(s.ev_done, p->s_d2h);
+        }
+    }
+    if (e != hipSuccess) return hip_failed(e);
+    s.busy = true;
+    s.out = out;
+    ++n;
+    return SDRK_OK;
+}
+
+int SlotPipe::drain() {
+    for (size_t i = 0; i < HOST_SLOTS; ++i)
+        if (int st = retire(p->slot[(n + i) % HOST_SLOTS]); st != SDRK_OK) return st;
+    return SDRK_OK;
+}
+
+namespace {
+
+struct HostTrace {   // SDRK_HOST_TRACE=1: where a pipelined sdrk_exec_host call spends its wall time (stderr)
+    bool on = false;
+    double t_in = 0, t_wait = 0, t_out = 0, t_mark = 0;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    static void mark(void* ctx, int point) {   // SlotPipe's hook: a retire's wait ends at point 1, its delivery at point 2
+        HostTrace& tr = *static_cast<HostTrace*>(ctx);
+        const double t = now();
+        if (point == 1) tr.t_wait += t - tr.t_mark;
+        if (point == 2) tr.t_out += t - tr.t_mark;
+        tr.t_mark = t;
+    }
+};
+
+}  // namespace
 
 // The numpy boundary.  Small calls (the live app's one 4096-sample buffer, streamer.py:114-121): the
 // kernel reads and writes pinned mapped host memory, no DMA copies.  Everything else: the frames go
@@ -160,7 +222,8 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
         memcpy(out, p->h_small_out, out_bytes);
         return SDRK_OK;
     }
-    st = ensure_copy_streams(p);
+    SlotPipe pipe;
+    st = pipe.open(p, "host pipeline");
     if (st != SDRK_OK) return st;
     // frames per chunk: ~HOST_CHUNK_BYTES of input, but at least 4 chunks per call when the call is big
     // enough for the overlap to matter, and never less than one frame
@@ -202,54 +265,38 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
         (void)hipGetLastError();   // no device view of the range: take the copy-engine path below
     }
     const double t_call = tr.on ? HostTrace::now() : 0;
-    size_t c = 0;
-    for (size_t f0 = 0; f0 < n_frames; f0 += per, ++c) {
-        HostSlot& s = p->slot[c % HOST_SLOTS];
+    if (tr.on) { pipe.mark = HostTrace::mark; pipe.mark_ctx = &tr; }
+    const ChunkOut::Rows rows = zero_copy ? ChunkOut::Kernel : out_pinned ? ChunkOut::Direct : ChunkOut::Pooled;
+    for (size_t f0 = 0; f0 < n_frames; f0 += per) {
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
         const size_t cin = ((nf - 1) * frame_stride + span) * in_elem;
         const size_t cout = nf * nfft * out_elem;
-        st = slot_retire(s, tr);                               // chunk c - HOST_SLOTS: rows out, slot free
-        if (st == SDRK_OK) st = slot_reserve(p, s, chunk_in, chunk_out);
-        if (st != SDRK_OK) { slots_abandon(p); return st; }
+        HostSlot* sp = nullptr;
+        st = pipe.acquire(chunk_in, chunk_out, sp);
+        if (st != SDRK_OK) return st;
+        HostSlot& s = *sp;
         const double t0 = tr.on ? HostTrace::now() : 0;
         const void* src = static_cast<const char*>(iq) + f0 * frame_stride * in_elem;
         src = chunk_pinned_src(s, src, cin, in_pinned);
         void* user_rows = static_cast<char*>(out) + f0 * nfft * out_elem;
         if (tr.on) tr.t_in += HostTrace::now() - t0;
-        hipError_t e = hipSuccess;
         if (zero_copy) {
             // the transform reads the pinned chunk and writes the pinned rows itself, over PCIe: no DMA-engine
             // copies, two API calls per chunk
-            st = io.launch(p, s.h_in, nf, frame_stride, s.h_out, epilogue, p->stream);
-            if (st != SDRK_OK) { slots_abandon(p); return st; }
-            e = hipEventRecord(s.ev_done, p->stream);
+            st = pipe.submit(s, io.launch(p, s.h_in, nf, frame_stride, s.h_out, epilogue, p->stream), {rows, user_rows, cout});
         } else {
-            e = stage_chunk_in(p, s, src, cin);
-            if (e == hipSuccess) {
-                st = io.launch(p, s.d_in, nf, frame_stride, s.d_out, epilogue, p->stream);
-                if (st != SDRK_OK) { slots_abandon(p); return st; }
-                e = hipEventRecord(s.ev_k, p->stream);
-            }
-            if (e == hipSuccess) e = hipStreamWaitEvent(p->s_d2h, s.ev_k, 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(out_pinned ? user_rows : s.h_out, s.d_out, cout, hipMemcpyDeviceToHost, p->s_d2h);
-            if (e == hipSuccess) e = hipEventRecord(s.ev_done, p->s_d2h);
+            st = pipe.upload(s, src, cin);
+            if (st == SDRK_OK)
+                st = pipe.submit(s, io.launch(p, s.d_in, nf, frame_stride, s.d_out, epilogue, p->stream), {rows, user_rows, cout});
         }
-        if (e != hipSuccess) {
-            slots_abandon(p);
-            return fail(SDRK_ERR_HIP, "host pipeline failed: %s", hipGetErrorString(e));
-        }
-        s.busy = true;
-        s.user_out = (out_pinned && !zero_copy) ? nullptr : user_rows;
-        s.out_bytes = cout;
+        if (st != SDRK_OK) return st;
     }
-    for (size_t i = 0; i < HOST_SLOTS; ++i) {                  // drain in submission order
-        st = slot_retire(p->slot[(c + i) % HOST_SLOTS], tr);
-        if (st != SDRK_OK) { slots_abandon(p); return st; }
-    }
+    st = pipe.drain();
+    if (st != SDRK_OK) return st;
     if (tr.on) {
         const double t = HostTrace::now() - t_call;
         fprintf(stderr, "[sdrk host] %zu chunks of %zu frames, %.1f MiB in: total %.3f ms = stage-in %.3f + wait %.3f + "
-                "stage-out %.3f + other %.3f (%.1f GB/s of input, %d helper threads)\n", c, per,
+                "stage-out %.3f + other %.3f (%.1f GB/s of input, %d helper threads)\n", pipe.n, per,
                 in_bytes / 1048576.0, t * 1e3, tr.t_in * 1e3, tr.t_wait * 1e3, tr.t_out * 1e3,
                 (t - tr.t_in - tr.t_wait - tr.t_out) * 1e3, in_bytes / t / 1e9, pool.helpers());
     }

@@ -162,20 +162,9 @@ __global__ __launch_bounds__(F4K_THREADS, XS_WG_PER_CU) void xspec4096_kernel(
 template <class In>
 static hipError_t launch_xspec4096_of(const IntegrateArgs& a) {
     if (a.f1 <= a.f0) return hipSuccess;
-    IntUnits c;
-    const IntSplit sp{a.slices, a.slice_len};
-    c.f0 = a.f0;
-    c.f1 = a.f1;
-    c.k = a.k;
-    c.slice_len = a.slice_len;
-    c.slices = (unsigned)a.slices;
-    c.u_first = integrate_unit_of(a.f0, a.k, sp);
-    c.u_last = integrate_unit_of(a.f1 - 1, a.k, sp);
-    c.out_row0 = a.out_row0;
+    IntUnits c = int_units(a);   // power planes, whatever the call's out_form says
     c.out_form = INT_OUT_POWER;
-    c.scale = a.scale;
     c.eps = 0.0f;
-    c.inv_k = 1.0f / (float)a.k;
     dim3 g(f4k_grid(a.num_cus, XS_WG_PER_CU, c.u_last - c.u_first + 1)), b(F4K_THREADS);
     const char* iq = static_cast<const char*>(a.d_in);
     const float2* tw = static_cast<const float2*>(a.d_twiddle);

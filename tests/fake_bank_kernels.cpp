@@ -1,5 +1,5 @@
 // tests/fake_bank_kernels.cpp — stand-ins for the channel-bank launchers of csrc/kernels_ols_bank.h, for the host-only sanitizer
-// build of csrc/pfb_api.hip (beside tests/fake_ols_kernels.cpp and the other stand-in kernels).  The real kernel's contract block
+// build of csrc/fir_api.hip (beside tests/fake_ols_kernels.cpp and the other stand-in kernels).  The real kernel's contract block
 // by block: the block geometry of kernels_ols.h, ONE forward transform per block shared by all channels, then per channel the
 // shared arithmetic (ols_filter with H rotated by that channel's shift, the transform again, ols_unscale, ols_mix unless the
 // shift is 0) and every D-th output stored into the channel's plane, out_stride apart; max_blocks cuts a launch.  The transform

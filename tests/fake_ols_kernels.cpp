@@ -1,5 +1,5 @@
 // tests/fake_ols_kernels.cpp — stand-ins for the overlap-save FIR launchers of csrc/kernels_ols.h, for the host-only sanitizer
-// build of csrc/pfb_api.hip (with the stand-in runtime of tests/fake_hip, beside the other stand-in kernels).  They keep the
+// build of csrc/fir_api.hip (with the stand-in runtime of tests/fake_hip, beside the other stand-in kernels).  They keep the
 // real kernel's contract block by block — ols_block_len / ols_blocks / ols_outputs, block b reads samples b L .. b L + 4095 with
 // zeros past n_in, positions M - 1 .. M - 2 + L are outputs b L .. b L + L - 1, every D-th is stored, max_blocks cuts a launch —
 // and the arithmetic between the two transforms is kernels_ols.h's own (ols_filter, ols_unscale, ols_mix, the two index

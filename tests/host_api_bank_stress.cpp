@@ -1,5 +1,5 @@
 // tests/host_api_bank_stress.cpp — drives the host side of the channel-bank entry points (sdrk_exec_device_chanbank*,
-// sdrk_exec_host_chanbank*: csrc/pfb_api.hip and the staging slots of csrc/sdrk_host_pipeline.hip; built with the other host
+// sdrk_exec_host_chanbank*: csrc/fir_api.hip and the staging slots of csrc/sdrk_host_pipeline.hip; built with the other host
 // files by g++ against the stand-in runtime of tests/fake_hip and the stand-in kernels tests/fake_*_kernels.cpp) for the sanitizer
 // legs of tests/test_host_sanitizers_bank.py.  A program of its own: nothing is loaded into Python, nothing is preloaded.
 //
@@ -159,6 +159,7 @@ template <class S> void mode_cases(const Mode<S>& m, unsigned s) {
     if (!m.c64) run_case(m, p, {5, 8, 3, 300, 0, false, 1}, TIMED, s + 4);
     // host entry, 3 blocks per chunk: chunk boundaries with a prefix and without, the first kept sample inside the piece
     run_case(m, p, {300, 8, 3, 7 * L300 + 5, 13, true, 3}, HOST, s + 5);
+    run_case(m, p, {300, 8, 3, 10 * L300 + 5, 2, true, 3}, HOST, s + 11);               // four chunks: the first slot's planes leave before it is reused
     run_case(m, p, {5, 1, 1, 4 * L5, 1u << 20, false, 0}, HOST, s + 6);
     run_case(m, p, {2049, 64, 64, 3 * L2049 + 9, 0, false, 0}, HOST, s + 7);            // C = 64 over two chunks
     run_case(m, p, {2, 256, 3, 200, 100, true, 2}, HOST, s + 8);                        // one output a plane: stream index 256

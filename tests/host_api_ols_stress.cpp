@@ -1,5 +1,5 @@
 // tests/host_api_ols_stress.cpp — drives the host side of the FIR filtering / channel extraction entry points (sdrk_plan_set_fir,
-// sdrk_exec_device_fir*, sdrk_exec_host_fir*: csrc/pfb_api.hip and the staging slots of csrc/sdrk_host_pipeline.hip; built with
+// sdrk_exec_device_fir*, sdrk_exec_host_fir*: csrc/fir_api.hip and the staging slots of csrc/sdrk_host_pipeline.hip; built with
 // the other host files by g++ against the stand-in runtime of tests/fake_hip and the stand-in kernels tests/fake_*_kernels.cpp)
 // for the sanitizer legs of tests/test_host_sanitizers_ols.py.  A program of its own: nothing is loaded into Python, nothing is
 // preloaded.

@@ -87,10 +87,10 @@ static void exec_host_paths(int id, int rounds) {
     CHECK(sdrk_plan_destroy(p) == SDRK_OK);
 }
 
-// the chunked per-row feature path (> 32 MiB of IQ) and its planes form
+// the chunked per-row feature path (> 32 MiB of IQ) and its planes form: 50 MiB, four chunks, so the first slot is reused
 static void features_paths(int id) {
     const int nfft = 4096, mp = 8;
-    const size_t nf = 1200;
+    const size_t nf = 1600;
     sdrk_plan* p = nullptr;
     CHECK(sdrk_plan_create(0, nfft, nf, SDRK_WINDOW_RECT, nullptr, 1e-12f, 1, &p) == SDRK_OK);
     if (!p) return;

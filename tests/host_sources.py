@@ -16,7 +16,7 @@ CSRC = os.path.join(os.path.dirname(HERE), "sdr-iq-visualizer_amd", "csrc")
 
 # The host translation units among the Makefile's SRCS: the files without a kernel (test_host_sources.py holds the list to that).
 HOST_SOURCES = ("sdrk_api.hip", "sdrk_plan.hip", "sdrk_host_pipeline.hip", "sdrk_features.hip", "sdrk_waterfall.hip",
-                "sdrk_probes.hip", "sdrk_f64.hip", "ci16_api.hip", "integrate_api.hip", "pfb_api.hip")
+                "sdrk_probes.hip", "sdrk_f64.hip", "ci16_api.hip", "integrate_api.hip", "pfb_api.hip", "fir_api.hip")
 
 SANITIZERS = {"tsan": ("-fsanitize=thread",),
               "asan_ubsan": ("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")}

@@ -1,6 +1,6 @@
 """Sanitizer legs for the host side of the FIR filtering / channel extraction entry points (CPU).
 
-csrc/pfb_api.hip (sdrk_plan_set_fir, sdrk_exec_device_fir*, sdrk_exec_host_fir* and their chunk loop on the pinned staging slots)
+csrc/fir_api.hip (sdrk_plan_set_fir, sdrk_exec_device_fir*, sdrk_exec_host_fir* and their chunk loop on the pinned staging slots)
 and the other host files of csrc/ (tests/host_sources.py), compiled with g++ against the stand-in runtime of tests/fake_hip and
 the stand-in kernels tests/fake_*_kernels.cpp (fake_ols_kernels.cpp among them: the real block geometry and the shared
 arithmetic of csrc/kernels_ols.h), driven by the stand-alone program tests/host_api_ols_stress.cpp under ThreadSanitizer and
