@@ -551,7 +551,8 @@ int sdrk_exec_host_xspec_ci16(sdrk_plan* plan, const void* iq2_ci16, size_t n_gr
  * Served: float32 plans with nfft = 4096 only; the plan's window, shift and eps are ignored.  Plans of another length return
  * SDRK_ERR_UNSUPPORTED with a message.  An f64 plan, no filter set, NULL pointers, n_in < M, decim not a power of two in 1..256
  * and shift_bins outside -2048..2047 return SDRK_ERR_INVALID with a message.  A plan that has refused still works.
- * Not provided: other block lengths, double precision, rational resampling, fine (sub-bin) tuning. */
+ * Not provided: other block lengths, double precision, rational resampling.  Not provided by THESE entry points: fine (sub-bin) tuning
+ * and decimation by an integer that is no power of two; both are the digital down-converter's (sdrk_exec_*_ddc, below). */
 int sdrk_plan_set_fir(sdrk_plan* plan, int ntaps, const void* taps_c64);
 /* taps of the filter set on the plan; 0 = none */
 int sdrk_plan_fir_taps(const sdrk_plan* plan);
@@ -589,7 +590,8 @@ int sdrk_exec_host_fir_ci16(sdrk_plan* plan, const void* prefix_ci16, const void
  * Served and refused as the single call is, and in addition SDRK_ERR_INVALID with a message for n_chan outside 1..64, a NULL
  * shift_bins, an offset outside -2048..2047 and an out_stride below the outputs of a channel.  A plan that has refused still works.
  * Not provided: per-channel filters or decimation, more than 64 channels (the critically sampled many-channel case is the
- * polyphase filter bank's), a smaller inverse transform for D > 1. */
+ * polyphase filter bank's), a smaller inverse transform for D > 1.  Channels tuned finer than a bin, or decimated by another
+ * integer: sdrk_exec_*_ddcbank, below. */
 int sdrk_exec_device_chanbank(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int decim, int n_chan, const int* shift_bins,
                               const int* phase0, void* d_out_c64, size_t out_stride, void* stream);
 int sdrk_exec_device_chanbank_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, int decim, int n_chan, const int* shift_bins,
@@ -603,6 +605,72 @@ int sdrk_exec_host_chanbank(sdrk_plan* plan, const void* prefix_c64, const void*
                             const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out);
 int sdrk_exec_host_chanbank_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int n_chan,
                                  const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out);
+
+/* ---- digital down-converter (DDC): exact-frequency tuning and any integer decimation, one pass ----
+ * The two calls above tune to a bin of fs/4096 and decimate by a power of two.  A DDC tunes to a frequency, low-passes and
+ * decimates: here by a 32-bit frequency word (steps of fs/2^32: 0.014 Hz at 61.44 Msps) and by any integer D = decim in 1..256
+ * (2.4 Msps -> 48 kHz is D = 50), in the same single pass, as a single call and as the C-channel bank, from complex64 and from
+ * int16.  The filter is the one sdrk_plan_set_fir sets (M taps, L as above); block b reads samples b L .. b L + 4095 and the
+ * forward and inverse transforms, the product with H and the exact 2^-12 scaling are those of the FIR call, in its order.
+ *   freq_word  uint32_t: the tuned frequency is int32(freq_word) / 2^32 cycles per input sample.
+ *   decim      D, any integer 1 <= D <= 256.
+ *   index0     uint64_t: the stream index of valid-convolution output i = 0.
+ * Filter centre: s = ((freq_word + 0x80000) >> 20) & 4095, the nearest bin; H is rotated by s bins as above.  So the FILTER is
+ * centred within fs/8192 of the tuned frequency (half a bin: leave the pass band that much room), while the SIGNAL at the tuned
+ * frequency lands at DC exactly.
+ * Kept samples: with v[i] the filtered sample as above, i = 0 .. n_in - M, output i is kept iff (index0 + i) % D == 0, and the
+ * kept samples are stored in ascending i.  With i_first = (D - index0 % D) % D,
+ *     n_out = i_first > n_in - M ? 0 : (n_in - M - i_first)/D + 1
+ * which sdrk_ddc_outputs(n_in, taps, decim, index0) returns (0 for taps < 1, n_in < taps or decim outside 1..256).  n_out = 0
+ * is a successful no-op.
+ * Mixer: out = v[i] f, f = exp(-2 pi i phase / 2^32) formed as
+ *     phase = freq_word * (uint32)(index0 + i)             (uint32 wrap-around: exact mod 2^32)
+ *     q = phase >> 20;  r = phase & 0xFFFFF;  W = W4096^q  (the plan's twiddle table)
+ *     r == 0:  f = W
+ *     else:    a = (float)r * 0x1.921fb6p-30f              (2 pi 2^-32 rounded to float32)
+ *              c = fmaf(-0.5f a, a, 1.0f);  t = (a a) (1.0f/6.0f);  sn = fmaf(-t, a, a);  f = W (c - i sn)
+ * with the complex products of the FIR call's mixer (c is within 2^-25 of cos a and sn within 1.6e-10 of sin a for every r).
+ * freq_word == 0 runs no mixer at all: -0.0, Inf and NaN pass as they are.  A freq_word that is a multiple of 2^20, with D a
+ * power of two and index0 a multiple of D, gives the bits of sdrk_exec_device_fir with shift_bins = int32(freq_word) >> 20 and
+ * phase0 = shift_bins index0 mod 4096.
+ * Host entries: the device entry on the virtual stream prefix || iq (prefix: M - 1 samples, NULL = zeros) with index0 = sample0:
+ * output j has stream index sample0 + j; out holds at least (n + D - 1)/D samples; *n_out receives the count.  Chunked in whole
+ * blocks through the same pinned staging slots (SDRK_FIR_CHUNK_BLOCKS honoured); device memory does not grow with n.
+ * Bank: 1 <= n_chan <= 64, freq_word[c] per channel (host memory, read before the call returns), D and index0 shared, plane c at
+ * out + c out_stride (out_stride >= n_out; the host entries: >= (n + D - 1)/D); elements behind n_out are not written.
+ * Promised: the host entries return the bits of the device entry however they are chunked; the int16 entries return the bits of
+ * the complex64 entries on the widened samples; plane c of the bank carries the bits of the single call with freq_word[c];
+ * repeated calls return the same bits.  Not promised: equal bits between different cuts of one stream into calls.
+ * Served and refused as the FIR call is (float32 plans with nfft = 4096 only); in addition decim outside 1..256, n_chan outside
+ * 1..64, a NULL freq_word array and a short out_stride return SDRK_ERR_INVALID with a message.  A plan that has refused still
+ * works.  Not provided: rational (non-integer) resampling, per-channel filters or decimation, D above 256, double precision. */
+size_t sdrk_ddc_outputs(size_t n_in, int taps, int decim, uint64_t index0);
+/* device in / device out (d_out_c64: n_out complex64), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_ddc(sdrk_plan* plan, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                         void* d_out_c64, void* stream);
+int sdrk_exec_device_ddc_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                              void* d_out_c64, void* stream);
+/* the complex64 form, timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_ddc_timed_each(sdrk_plan* plan, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim,
+                                    uint64_t index0, void* d_out_c64, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays) */
+int sdrk_exec_host_ddc(sdrk_plan* plan, const void* prefix_c64, const void* iq_c64, size_t n, uint32_t freq_word, int decim,
+                       uint64_t sample0, void* out_c64, size_t* n_out);
+int sdrk_exec_host_ddc_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, uint32_t freq_word, int decim,
+                            uint64_t sample0, void* out_c64, size_t* n_out);
+/* the bank */
+int sdrk_exec_device_ddcbank(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                             uint64_t index0, void* d_out_c64, size_t out_stride, void* stream);
+int sdrk_exec_device_ddcbank_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, int n_chan, const uint32_t* freq_word,
+                                  int decim, uint64_t index0, void* d_out_c64, size_t out_stride, void* stream);
+int sdrk_exec_device_ddcbank_timed_each(sdrk_plan* plan, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word,
+                                        int decim, uint64_t index0, void* d_out_c64, size_t out_stride, int launches,
+                                        float* each_ms);
+int sdrk_exec_host_ddcbank(sdrk_plan* plan, const void* prefix_c64, const void* iq_c64, size_t n, int n_chan,
+                           const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out);
+int sdrk_exec_host_ddcbank_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int n_chan,
+                                const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride,
+                                size_t* n_out);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

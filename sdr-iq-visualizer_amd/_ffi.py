@@ -211,6 +211,18 @@ SYMBOLS = [
     ("sdrk_exec_device_chanbank_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_size_t, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_chanbank", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("sdrk_exec_host_chanbank_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, POINTER(c_int), c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
+    # digital down-converter: the two calls above tuned by a 32-bit frequency word, decimated by any integer 1..256
+    ("sdrk_ddc_outputs", c_size_t, [c_size_t, c_int, c_int, c_uint64]),
+    ("sdrk_exec_device_ddc", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_ddc_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_ddc_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_ddc", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_host_ddc_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_device_ddcbank", c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_ddcbank_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_ddcbank_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_ddcbank", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
+    ("sdrk_exec_host_ddcbank_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
 ]
 
 _lib = None

@@ -1,14 +1,15 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
     python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross]] [--pfb T] [--out rows.npz]
-    python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F [F ...] --decim D [--taps M] --out BASE
+    python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F [F ...] --decim D [--exact] [--taps M] --out BASE
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
 (app/sdr/streamer.py:119-121) and, with ``--welch N``, the averaged Hann PSD its offline script
 plots (scripts/process_sigmf_data.py:188-189).  ``extract`` tunes to ``center_freq + F`` (rounded to a bin of
 ``sample_rate/4096``), low-passes, decimates by D and writes the channel as a cf32_le SigMF recording at ``sample_rate/D``;
-several offsets are extracted in one pass over the recording and written as ``BASE_0``, ``BASE_1``, ...
+several offsets are extracted in one pass over the recording and written as ``BASE_0``, ``BASE_1``, ...  With ``--exact`` the
+digital down-converter does it: F is tuned to the nearest 32-bit frequency word (``sample_rate/2^32``) and D is any integer in 1..256.
 All transforms run through libsdrk.
 """
 from __future__ import annotations
@@ -42,8 +43,12 @@ def _extract(args, sigmf_io, spectrum) -> int:
     if len(args.offset_hz) > 1:
         return _extract_bank(args, sigmf_io, spectrum, samples, fs, fc)
     try:
-        taps = spectrum.channel_taps(args.decim, args.taps)
-        ch = spectrum.ChannelStream(None, taps, args.decim, args.offset_hz[0], fs, device=args.device)
+        if args.exact:
+            taps = spectrum.ddc_taps(args.decim, args.taps)
+            ch = spectrum.DdcStream(None, taps, args.decim, args.offset_hz[0], fs, device=args.device)
+        else:
+            taps = spectrum.channel_taps(args.decim, args.taps)
+            ch = spectrum.ChannelStream(None, taps, args.decim, args.offset_hz[0], fs, device=args.device)
     except ValueError as err:
         print(f"extract: {err}", file=sys.stderr)
         return 2
@@ -53,8 +58,9 @@ def _extract(args, sigmf_io, spectrum) -> int:
     y = np.concatenate(out) if out else np.empty(0, np.complex64)
     paths = sigmf_io.write_sigmf(args.out, y, fs / args.decim, fc + ch.tuned_hz,
                                  description=f"channel at {ch.tuned_hz:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
+    tuning = {"freq_word": ch.freq_word} if args.exact else {"shift_bins": ch.shift_bins}
     print(json.dumps({"wrote": list(paths), "samples_in": n, "samples_out": int(y.shape[0]), "sample_rate": fs / args.decim,
-                      "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, "shift_bins": ch.shift_bins,
+                      "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, **tuning,
                       "decim": args.decim, "taps": int(taps.shape[0])}))
     return 0
 
@@ -62,20 +68,25 @@ def _extract(args, sigmf_io, spectrum) -> int:
 def _extract_bank(args, sigmf_io, spectrum, samples, fs: float, fc: float) -> int:
     """Several offsets: one ChannelBankStream, one pass over the recording, channel c -> the recording BASE_c."""
     try:
-        taps = spectrum.channel_taps(args.decim, args.taps)
-        bank = spectrum.ChannelBankStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
+        if args.exact:
+            taps = spectrum.ddc_taps(args.decim, args.taps)
+            bank = spectrum.DdcBankStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
+        else:
+            taps = spectrum.channel_taps(args.decim, args.taps)
+            bank = spectrum.ChannelBankStream(None, taps, args.decim, args.offset_hz, fs, device=args.device)
     except ValueError as err:
         print(f"extract: {err}", file=sys.stderr)
         return 2
     with bank:
         n = int(samples.shape[0])
         out = [bank.push(samples[at:at + EXTRACT_PIECE]) for at in range(0, n, EXTRACT_PIECE)]
-    y = np.concatenate(out, axis=1) if out else np.empty((len(bank.shift_bins), 0), np.complex64)
+    key, tunings = ("freq_word", bank.freq_words) if args.exact else ("shift_bins", bank.shift_bins)
+    y = np.concatenate(out, axis=1) if out else np.empty((len(tunings), 0), np.complex64)
     channels = []
-    for c, (tuned, bins) in enumerate(zip(bank.tuned_hz, bank.shift_bins)):
+    for c, (tuned, bins) in enumerate(zip(bank.tuned_hz, tunings)):
         paths = sigmf_io.write_sigmf(f"{args.out}_{c}", np.ascontiguousarray(y[c]), fs / args.decim, fc + tuned,
                                      description=f"channel at {tuned:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
-        channels.append({"wrote": list(paths), "center_freq": fc + tuned, "tuned_offset_hz": tuned, "shift_bins": bins})
+        channels.append({"wrote": list(paths), "center_freq": fc + tuned, "tuned_offset_hz": tuned, key: bins})
     print(json.dumps({"channels": channels, "samples_in": n, "samples_out": int(y.shape[1]), "sample_rate": fs / args.decim,
                       "decim": args.decim, "taps": int(taps.shape[0])}))
     return 0
@@ -111,7 +122,11 @@ def main(argv=None) -> int:
     e.add_argument("path")
     e.add_argument("--offset-hz", type=float, nargs="+", required=True,
                    help="the channel's centre, relative to the recording's centre; several: one pass, recordings OUT_0, OUT_1, ...")
-    e.add_argument("--decim", type=_positive, required=True, help="decimation: a power of two in 1..256")
+    e.add_argument("--decim", type=_positive, required=True,
+                   help="decimation: a power of two in 1..256 (with --exact: any integer in 1..256)")
+    e.add_argument("--exact", action="store_true",
+                   help="digital down-converter: tune each offset to the nearest 32-bit frequency word (sample_rate/2^32) instead "
+                        "of a bin of sample_rate/4096, and allow any integer --decim; the report has freq_word for shift_bins")
     e.add_argument("--taps", type=_positive, default=None, help="filter length (default min(16*decim + 1, 2049))")
     e.add_argument("--out", required=True, help="base name of the cf32_le SigMF recording to write")
     e.add_argument("--device", type=int, default=0)

@@ -1,7 +1,9 @@
 // fir_api.hip — host side of "FIR filtering and channel extraction" of include/sdrk.h (sdrk_plan_set_fir, sdrk_plan_fir_taps,
 // sdrk_exec_*_fir*): tune, filter, decimate by overlap-save fast convolution in blocks of 4096 through ols4096.hip, the filter
 // held by the plan as the polyphase prototype is (kernels_ols.h has the block geometry); and of the channel bank
-// (sdrk_exec_*_chanbank*): C tuned channels from one pass over the input through ols_bank.hip (kernels_ols_bank.h).
+// (sdrk_exec_*_chanbank*): C tuned channels from one pass over the input through ols_bank.hip (kernels_ols_bank.h); and of the
+// digital down-converter (sdrk_ddc_outputs, sdrk_exec_*_ddc*, sdrk_exec_*_ddcbank*): the same two calls tuned by a 32-bit frequency
+// word and decimated by any integer, through ddc4096.hip (kernels_ddc.h), with a chunk loop of its own on the same SlotPipe.
 //
 // A device call is one launch on the caller's stream.  The numpy boundary runs the same launches on the virtual stream
 // prefix || iq in chunks of whole blocks through sdrk_host_pipeline.hip's SlotPipe, one loop (host_fir_chunks) for the single
@@ -17,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kernels_ddc.h"
 #include "kernels_ols_bank.h"
 #include "plan_internal.h"
 
@@ -248,6 +251,137 @@ int exec_host_bank(size_t in_elem, sdrk_plan* p, const void* prefix, const void*
                            });
 }
 
+// ---- digital down-converter: a 32-bit frequency word, any integer decimation (kernels_ddc.h) ----
+int check_ddc_call(const sdrk_plan* p, int decim) {
+    int st = check_fir_plan(p);
+    if (st != SDRK_OK) return st;
+    if (p->fir_taps < 1 || !p->d_fir_h) return fail(SDRK_ERR_INVALID, "no FIR filter set: call sdrk_plan_set_fir first");
+    if (decim < 1 || decim > sdrk::DDC_MAX_DECIM) return fail(SDRK_ERR_INVALID, "decim=%d: must be in [1, %d]", decim, sdrk::DDC_MAX_DECIM);
+    return SDRK_OK;
+}
+
+int check_ddc_chans(int n_chan, const uint32_t* freq_word) {
+    if (n_chan < 1 || n_chan > sdrk::DDC_MAX_CHAN) return fail(SDRK_ERR_INVALID, "n_chan=%d: must be in [1, %d]", n_chan, sdrk::DDC_MAX_CHAN);
+    if (!freq_word) return fail(SDRK_ERR_INVALID, "freq_word pointer is NULL");
+    return SDRK_OK;
+}
+
+// bank: n_chan planes out_stride apart; !bank: one channel, freq_word points at its word
+int check_ddc_device(const sdrk_plan* p, bool bank, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                     uint64_t index0, const void* d_out, size_t out_stride) {
+    int st = check_ddc_call(p, decim);
+    if (st == SDRK_OK && bank) st = check_ddc_chans(n_chan, freq_word);
+    if (st != SDRK_OK) return st;
+    if (!d_in || !d_out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
+    if (n_in < (size_t)p->fir_taps) return fail(SDRK_ERR_INVALID, "n_in=%zu: a valid convolution needs at least the %d taps", n_in, p->fir_taps);
+    const size_t n_out = sdrk::ddc_outputs(n_in, p->fir_taps, decim, index0);
+    if (bank && out_stride < n_out) return fail(SDRK_ERR_INVALID, "out_stride=%zu: a plane holds the %zu outputs of a channel", out_stride, n_out);
+    return SDRK_OK;
+}
+
+// One launch: the outputs i < max_blocks L (0: all) of the valid convolution of n_in samples, for every channel.
+int ddc_launch(sdrk_plan* p, bool i16, bool bank, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+               uint64_t index0, void* d_out, size_t out_stride, size_t max_blocks, hipStream_t stream) {
+    sdrk::DdcArgs a;
+    a.d_in = d_in;
+    a.n_in = n_in;
+    a.taps = p->fir_taps;
+    a.decim = decim;
+    a.n_chan = n_chan;
+    a.freq_word = freq_word;
+    a.index0 = index0;
+    a.d_h = p->d_fir_h;
+    a.d_twiddle = p->d_twiddle;
+    a.d_out = static_cast<float2*>(d_out);
+    a.out_stride = out_stride;
+    a.max_blocks = max_blocks;
+    a.num_cus = p->num_cus;
+    a.stream = stream;
+    if (sdrk::ddc_launch_outputs(a) == 0) return SDRK_OK;   // nothing kept: a successful no-op
+    const hipError_t e = bank ? (i16 ? sdrk::launch_ddcbank_i16(a) : sdrk::launch_ddcbank(a)) : (i16 ? sdrk::launch_ddc_i16(a) : sdrk::launch_ddc(a));
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "DDC kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
+int exec_device_ddc(bool i16, bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                    uint64_t index0, void* d_out, size_t out_stride, void* stream) {
+    int st = check_ddc_device(p, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    return ddc_launch(p, i16, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0,
+                      stream ? static_cast<hipStream_t>(stream) : p->stream);
+}
+
+int exec_device_ddc_timed(bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                          uint64_t index0, void* d_out, size_t out_stride, int launches, float* each_ms) {
+    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
+    int st = check_ddc_device(p, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride);
+    if (st != SDRK_OK) return st;
+    return timed_each(p, launches, each_ms, [&] {
+        return ddc_launch(p, false, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0, p->stream);
+    });
+}
+
+// The numpy boundary: the device entry on the virtual stream V = prefix || iq with index0 = sample0 (output j of the valid
+// convolution has stream index sample0 + j), in chunks of whole blocks through the plan's pinned staging slots.  Every block is
+// the 4096 samples it is in one device call on V (a chunk carries its last block's overlap and its launch is cut at
+// max_blocks L outputs) and the mixer's phase and the keeping follow the stream index, which the chunk's launch is handed as its
+// index0, so the chunking does not show in the bits.  A block yields L / D outputs or one more, so the outputs of a chunk are
+// counted, not multiplied out: chunk [b0, b0 + nb) starts at output ddc_count(b0 L) and holds ddc_count of its own.
+int exec_host_ddc(size_t in_elem, bool bank, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int n_chan,
+                  const uint32_t* freq_word, int decim, uint64_t sample0, void* out, size_t out_stride, size_t* n_out) {
+    int st = check_ddc_call(p, decim);
+    if (st == SDRK_OK && bank) st = check_ddc_chans(n_chan, freq_word);
+    if (st != SDRK_OK) return st;
+    if (!n_out) return fail(SDRK_ERR_INVALID, "n_out pointer is NULL");
+    *n_out = 0;
+    const size_t D = (size_t)decim, need = (n + D - 1) / D;
+    if (bank && out_stride < need) return fail(SDRK_ERR_INVALID, "out_stride=%zu: a plane holds up to %zu outputs of a channel", out_stride, need);
+    if (n == 0) return SDRK_OK;
+    if (!iq || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
+    uint32_t words[sdrk::DDC_MAX_CHAN];   // read before the call returns: the launches below see this copy
+    memcpy(words, freq_word, (size_t)n_chan * sizeof(uint32_t));
+    const size_t M = (size_t)p->fir_taps, L = (size_t)sdrk::ols_block_len(p->fir_taps), N = sdrk::OLS_N, planes = (size_t)n_chan;
+    const size_t n_virt = n + M - 1, total_out = sdrk::ddc_count(n, decim, sample0);
+    if (total_out == 0) return SDRK_OK;
+    const size_t n_blocks = sdrk::ols_blocks(n_virt, p->fir_taps), per = fir_chunk_blocks(L, in_elem);
+    const size_t chunk_in = ((per - 1) * L + N) * in_elem, chunk_out = planes * (per * L / D + 1) * sizeof(float2);
+    HIP_TRY(hipSetDevice(p->device));
+    SlotPipe pipe;
+    st = pipe.open(p, "host pipeline");
+    if (st != SDRK_OK) return st;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += per) {
+        const size_t nb = n_blocks - b0 < per ? n_blocks - b0 : per;
+        const size_t t0 = b0 * L;
+        const size_t cn = (nb - 1) * L + N < n_virt - t0 ? (nb - 1) * L + N : n_virt - t0;
+        const size_t valid = nb * L < cn - M + 1 ? nb * L : cn - M + 1;
+        const size_t o0 = sdrk::ddc_count(t0, decim, sample0), co = sdrk::ddc_count(valid, decim, sample0 + t0);
+        HostSlot* s = nullptr;
+        st = pipe.acquire(chunk_in, chunk_out, s);
+        if (st != SDRK_OK) return st;
+        // samples V[t0 .. t0 + cn): the part below M - 1 from the prefix (NULL: zeros), the rest from iq
+        char* dst = static_cast<char*>(s->h_in);
+        size_t done = 0;
+        if (t0 < M - 1) {
+            done = M - 1 - t0 < cn ? M - 1 - t0 : cn;
+            if (prefix) memcpy(dst, static_cast<const char*>(prefix) + t0 * in_elem, done * in_elem);
+            else memset(dst, 0, done * in_elem);
+        }
+        if (done < cn)
+            memcpy(dst + done * in_elem, static_cast<const char*>(iq) + (t0 + done - (M - 1)) * in_elem, (cn - done) * in_elem);
+        st = pipe.upload(*s, s->h_in, cn * in_elem);
+        if (st == SDRK_OK)
+            st = pipe.submit(*s, ddc_launch(p, in_elem == 4, bank, s->d_in, cn, n_chan, words, decim, sample0 + t0, s->d_out, co, nb, p->stream),
+                             {ChunkOut::Planes, static_cast<char*>(out) + o0 * sizeof(float2), co * sizeof(float2), planes,
+                              out_stride * sizeof(float2)});
+        if (st != SDRK_OK) return st;
+    }
+    st = pipe.drain();
+    if (st != SDRK_OK) return st;
+    *n_out = total_out;
+    return SDRK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,6 +481,61 @@ int sdrk_exec_host_chanbank(sdrk_plan* p, const void* prefix_c64, const void* iq
 int sdrk_exec_host_chanbank_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, int decim, int n_chan,
                                  const int* shift_bins, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
     return exec_host_bank(4, p, prefix_ci16, iq_ci16, n, decim, n_chan, shift_bins, sample0, out_c64, out_stride, n_out);
+}
+
+size_t sdrk_ddc_outputs(size_t n_in, int taps, int decim, uint64_t index0) {
+    if (taps < 1 || decim < 1 || decim > sdrk::DDC_MAX_DECIM) return 0;
+    return sdrk::ddc_outputs(n_in, taps, decim, index0);
+}
+
+int sdrk_exec_device_ddc(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                         void* d_out_c64, void* stream) {
+    return exec_device_ddc(false, false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
+}
+
+int sdrk_exec_device_ddc_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                              void* d_out_c64, void* stream) {
+    return exec_device_ddc(true, false, p, d_in_ci16, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
+}
+
+int sdrk_exec_device_ddc_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                                    void* d_out_c64, int launches, float* each_ms) {
+    return exec_device_ddc_timed(false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, launches, each_ms);
+}
+
+int sdrk_exec_host_ddc(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, uint32_t freq_word, int decim,
+                       uint64_t sample0, void* out_c64, size_t* n_out) {
+    return exec_host_ddc(sizeof(float2), false, p, prefix_c64, iq_c64, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
+}
+
+int sdrk_exec_host_ddc_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, uint32_t freq_word, int decim,
+                            uint64_t sample0, void* out_c64, size_t* n_out) {
+    return exec_host_ddc(4, false, p, prefix_ci16, iq_ci16, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
+}
+
+int sdrk_exec_device_ddcbank(sdrk_plan* p, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                             uint64_t index0, void* d_out_c64, size_t out_stride, void* stream) {
+    return exec_device_ddc(false, true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
+}
+
+int sdrk_exec_device_ddcbank_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+                                  uint64_t index0, void* d_out_c64, size_t out_stride, void* stream) {
+    return exec_device_ddc(true, true, p, d_in_ci16, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
+}
+
+int sdrk_exec_device_ddcbank_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word,
+                                        int decim, uint64_t index0, void* d_out_c64, size_t out_stride, int launches, float* each_ms) {
+    return exec_device_ddc_timed(true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, launches, each_ms);
+}
+
+int sdrk_exec_host_ddcbank(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, int n_chan, const uint32_t* freq_word,
+                           int decim, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
+    return exec_host_ddc(sizeof(float2), true, p, prefix_c64, iq_c64, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
+}
+
+int sdrk_exec_host_ddcbank_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, int n_chan,
+                                const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
+    return exec_host_ddc(4, true, p, prefix_ci16, iq_ci16, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
 }
 
 }  // extern "C"

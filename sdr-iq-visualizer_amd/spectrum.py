@@ -238,6 +238,16 @@ def channel_taps(decim: int, ntaps: Optional[int] = None, window: WindowArg = "h
     decim = int(decim)
     if decim < 1 or decim > FIR_MAX_DECIM or decim & (decim - 1):
         raise ValueError(f"decim must be a power of two in 1..{FIR_MAX_DECIM}, got {decim}")
+    return _lowpass_taps(decim, ntaps, window)
+
+
+def ddc_taps(decim: int, ntaps: Optional[int] = None, window: WindowArg = "hann") -> np.ndarray:
+    """``channel_taps`` for the digital down-converter: the same low-pass (cutoff ``0.4/decim``, unit DC gain, default length
+    ``min(16*decim + 1, 2049)``) for ANY integer ``decim`` in 1..256; for a power of two it is ``channel_taps(decim, ...)``."""
+    return _lowpass_taps(_ddc_decim(decim), ntaps, window)
+
+
+def _lowpass_taps(decim: int, ntaps: Optional[int], window: WindowArg) -> np.ndarray:
     m = min(16 * decim + 1, FIR_MAX_TAPS) if ntaps is None else int(ntaps)
     if not 1 <= m <= FIR_MAX_TAPS:
         raise ValueError(f"ntaps must be in 1..{FIR_MAX_TAPS}, got {m}")
@@ -274,6 +284,43 @@ def _bank_shifts(shift_bins):
     for v in shifts:
         _fir_args(1, v)
     return (c_int * len(shifts))(*shifts)
+
+
+def _ddc_decim(decim) -> int:
+    decim = int(decim)
+    if decim < 1 or decim > FIR_MAX_DECIM:
+        raise ValueError(f"decim must be in 1..{FIR_MAX_DECIM}, got {decim}")
+    return decim
+
+
+def _ddc_word(word) -> int:
+    """A frequency word as the C call takes it: any int, taken mod 2^32 (so -1 is the word just below zero)."""
+    return int(word) & 0xFFFFFFFF
+
+
+def _ddc_words(freq_words):
+    """The frequency words of a DDC bank call as a ctypes uint32 array: 1..64 of them."""
+    words = [_ddc_word(v) for v in np.asarray(freq_words, dtype=object).reshape(-1)]
+    if not 1 <= len(words) <= FIR_BANK_MAX_CHANNELS:
+        raise ValueError(f"a DDC bank takes 1..{FIR_BANK_MAX_CHANNELS} frequency words, got {len(words)}")
+    return (_ffi.c_uint32 * len(words))(*words)
+
+
+def freq_word(offset_hz: float, sample_rate: float) -> int:
+    """The 32-bit frequency word of the digital down-converter nearest to ``offset_hz`` at ``sample_rate``:
+    ``round(offset_hz / sample_rate * 2^32) mod 2^32`` (steps of ``sample_rate / 2^32``); offsets beyond half the sample rate
+    wrap around, as the frequencies of a sampled signal do."""
+    fs = float(sample_rate)
+    if not fs > 0:
+        raise ValueError("sample_rate must be positive")
+    from fractions import Fraction
+    return int(round(Fraction(float(offset_hz)) / Fraction(fs) * (1 << 32))) & 0xFFFFFFFF
+
+
+def freq_word_hz(word: int, sample_rate: float) -> float:
+    """The frequency a word tunes to: ``int32(word) / 2^32 * sample_rate``, in -sample_rate/2 .. sample_rate/2."""
+    w = _ddc_word(word)
+    return (w - (1 << 32) if w >= 1 << 31 else w) / float(1 << 32) * float(sample_rate)
 
 
 
@@ -1141,6 +1188,138 @@ class SpectrumPlan:
         check(lib().sdrk_exec_device_chanbank_timed_each(self.handle, *args, int(launches), each))
         return list(each)
 
+    # -- digital down-converter: the two calls above tuned by a 32-bit frequency word, decimated by any integer 1..256 ------
+    def _ddc_input(self, iq, prefix, ci16: bool):
+        m = self._fir_ready()
+        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_ci16(prefix, stream=True) if ci16 else _as_c64(prefix).reshape(-1)
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return x, pre
+
+    def _host_ddc(self, sym: str, x: np.ndarray, prefix, word, decim: int, sample0: int) -> np.ndarray:
+        decim, word = _ddc_decim(decim), _ddc_word(word)
+        if int(sample0) < 0:
+            raise ValueError("sample0 must be >= 0")
+        n = int(x.shape[0])
+        out = np.empty((n + decim - 1) // decim, dtype=np.complex64)
+        n_out = c_size_t(0)
+        with self._lock:
+            check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
+                                      x.ctypes.data_as(c_void_p), c_size_t(n), _ffi.c_uint32(word), decim,
+                                      _ffi.c_uint64(int(sample0)), out.ctypes.data_as(c_void_p), byref(n_out)))
+        return out[: n_out.value]
+
+    def ddc(self, iq, freq_word: int, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """Tune, filter and decimate one piece of a complex64 stream as a digital down-converter does: ``fir`` with the tuning
+        given as a 32-bit frequency word (``int32(freq_word) / 2^32`` cycles per sample: ``spectrum.freq_word`` makes one from
+        hertz) and ``decim`` ANY integer in 1..256.  The filter is centred on the nearest bin of 4096, the signal at the tuned
+        frequency lands at DC exactly, and of the outputs those whose stream index ``sample0 + j`` is a multiple of ``decim``
+        are returned — none, if the piece holds none."""
+        x, pre = self._ddc_input(iq, prefix, False)
+        return self._host_ddc("sdrk_exec_host_ddc", x, pre, freq_word, decim, sample0)
+
+    def ddc_ci16(self, iq, freq_word: int, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``ddc`` on interleaved int16 I,Q of shape ``(n, 2)`` (``prefix``: ``(M - 1, 2)`` int16): the bits of ``ddc`` on the
+        widened samples."""
+        x, pre = self._ddc_input(iq, prefix, True)
+        return self._host_ddc("sdrk_exec_host_ddc_ci16", x, pre, freq_word, decim, sample0)
+
+    def _host_ddc_bank(self, sym: str, x: np.ndarray, prefix, freq_words, decim: int, sample0: int) -> np.ndarray:
+        decim, words = _ddc_decim(decim), _ddc_words(freq_words)
+        if int(sample0) < 0:
+            raise ValueError("sample0 must be >= 0")
+        n = int(x.shape[0])
+        stride = (n + decim - 1) // decim
+        out = np.empty((len(words), stride), dtype=np.complex64)
+        n_out = c_size_t(0)
+        with self._lock:
+            check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
+                                      x.ctypes.data_as(c_void_p), c_size_t(n), len(words), words, decim,
+                                      _ffi.c_uint64(int(sample0)), out.ctypes.data_as(c_void_p), c_size_t(stride), byref(n_out)))
+        return np.ascontiguousarray(out[:, : n_out.value])
+
+    def ddc_bank(self, iq, freq_words, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``ddc`` for ``C = len(freq_words)`` channels at once (1..64, duplicates allowed), from ONE pass over ``iq``: row ``c``
+        of the ``(C, n_out)`` complex64 result carries the bits of ``ddc(iq, freq_words[c], decim=decim, prefix=prefix,
+        sample0=sample0)``."""
+        x, pre = self._ddc_input(iq, prefix, False)
+        return self._host_ddc_bank("sdrk_exec_host_ddcbank", x, pre, freq_words, decim, sample0)
+
+    def ddc_bank_ci16(self, iq, freq_words, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``ddc_bank`` on interleaved int16 I,Q of shape ``(n, 2)``: the bits of ``ddc_bank`` on the widened samples."""
+        x, pre = self._ddc_input(iq, prefix, True)
+        return self._host_ddc_bank("sdrk_exec_host_ddcbank_ci16", x, pre, freq_words, decim, sample0)
+
+    def ddc_outputs(self, n_in: int, decim: int = 1, index0: int = 0) -> int:
+        """Samples ``exec_device_ddc`` writes for ``n_in`` input samples whose first valid output has stream index ``index0``:
+        the ``i`` in ``0 .. n_in - M`` with ``(index0 + i) % decim == 0`` (``sdrk_ddc_outputs``)."""
+        m = self._fir_ready()
+        if int(n_in) < m:
+            raise ValueError(f"n_in={n_in}: a valid convolution needs at least the {m} taps")
+        if int(index0) < 0:
+            raise ValueError("index0 must be >= 0")
+        return int(lib().sdrk_ddc_outputs(c_size_t(int(n_in)), m, _ddc_decim(decim), _ffi.c_uint64(int(index0))))
+
+    def _device_ddc_args(self, d_in: int, n_in: int, freq_word: int, decim: int, index0: int, d_out: int) -> list:
+        self.ddc_outputs(n_in, decim, index0)
+        return [self.handle, c_void_p(d_in), c_size_t(int(n_in)), _ffi.c_uint32(_ddc_word(freq_word)), _ddc_decim(decim),
+                _ffi.c_uint64(int(index0)), c_void_p(d_out)]
+
+    def exec_device_ddc(self, d_in: int, n_in: int, d_out: int, freq_word: int, *, decim: int = 1, index0: int = 0,
+                        stream: int = 0) -> None:
+        """Device pointers, "valid" form: ``n_in`` complex64 samples in, ``ddc_outputs(n_in, decim, index0)`` complex64 out;
+        asynchronous on ``stream`` (0: the plan's stream)."""
+        args = self._device_ddc_args(d_in, n_in, freq_word, decim, index0, d_out)
+        check(lib().sdrk_exec_device_ddc(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_ci16(self, d_in: int, n_in: int, d_out: int, freq_word: int, *, decim: int = 1, index0: int = 0,
+                             stream: int = 0) -> None:
+        """``exec_device_ddc`` on int16 I,Q input (4 bytes per sample)."""
+        args = self._device_ddc_args(d_in, n_in, freq_word, decim, index0, d_out)
+        check(lib().sdrk_exec_device_ddc_ci16(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_timed_each(self, d_in: int, n_in: int, d_out: int, freq_word: int, launches: int = 1, *, decim: int = 1,
+                                   index0: int = 0) -> list:
+        """``exec_device_ddc`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_ddc_args(d_in, n_in, freq_word, decim, index0, d_out)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_ddc_timed_each(*args, int(launches), each))
+        return list(each)
+
+    def _device_ddc_bank_args(self, d_in: int, n_in: int, d_out: int, freq_words, decim: int, index0: int, out_stride) -> list:
+        words = _ddc_words(freq_words)
+        n_out = self.ddc_outputs(n_in, decim, index0)
+        stride = n_out if out_stride is None else int(out_stride)
+        if stride < n_out:
+            raise ValueError(f"out_stride={stride}: a plane holds the {n_out} outputs of a channel")
+        return [self.handle, c_void_p(d_in), c_size_t(int(n_in)), len(words), words, _ddc_decim(decim), _ffi.c_uint64(int(index0)),
+                c_void_p(d_out), c_size_t(stride)]
+
+    def exec_device_ddc_bank(self, d_in: int, n_in: int, d_out: int, freq_words, *, decim: int = 1, index0: int = 0,
+                             out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """Device pointers: ``exec_device_ddc`` for ``len(freq_words)`` channels from one pass.  Plane ``c`` starts at
+        ``d_out + 8 * c * out_stride`` (default: packed, ``ddc_outputs(n_in, decim, index0)`` apart) and carries the bits of
+        ``exec_device_ddc(..., freq_words[c])``; asynchronous on ``stream`` (0: the plan's stream)."""
+        args = self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride)
+        check(lib().sdrk_exec_device_ddcbank(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_bank_ci16(self, d_in: int, n_in: int, d_out: int, freq_words, *, decim: int = 1, index0: int = 0,
+                                  out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """``exec_device_ddc_bank`` on int16 I,Q input (4 bytes per sample)."""
+        args = self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride)
+        check(lib().sdrk_exec_device_ddcbank_ci16(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_bank_timed_each(self, d_in: int, n_in: int, d_out: int, freq_words, launches: int = 1, *, decim: int = 1,
+                                        index0: int = 0, out_stride: Optional[int] = None) -> list:
+        """``exec_device_ddc_bank`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_ddcbank_timed_each(*args, int(launches), each))
+        return list(each)
+
     def window_power(self) -> float:
         """``sum(w^2)`` of the plan's window (float64)."""
         if self._wkey == "rect":
@@ -1602,6 +1781,30 @@ def fir_bank(iq, taps, shift_bins, decim: int = 1, *, device: int = 0) -> np.nda
     return plan.fir_bank(iq, shift_bins, decim=decim)
 
 
+def ddc(iq, taps, offset_hz: float, sample_rate: float, decim: int = 1, *, device: int = 0) -> np.ndarray:
+    """``SpectrumPlan.ddc`` on a cached plan that holds ``taps``: the band around ``offset_hz`` (to the nearest frequency word,
+    ``freq_word(offset_hz, sample_rate)``) moved to DC, low-passed by ``taps`` and decimated by any integer ``decim`` in 1..256.
+    int16 ``(n, 2)`` input takes the int16 entry."""
+    _ddc_decim(decim)
+    word = freq_word(offset_hz, sample_rate)
+    plan = _cached_fir_plan(taps, device)
+    if isinstance(iq, np.ndarray) and iq.dtype == np.int16:
+        return plan.ddc_ci16(iq, word, decim=decim)
+    return plan.ddc(iq, word, decim=decim)
+
+
+def ddc_bank(iq, taps, offsets_hz, sample_rate: float, decim: int = 1, *, device: int = 0) -> np.ndarray:
+    """``SpectrumPlan.ddc_bank`` on a cached plan that holds ``taps``: ``ddc(iq, taps, offsets_hz[c], sample_rate, decim)`` for
+    every channel ``c`` from one pass over ``iq``, as a ``(C, n_out)`` array.  int16 ``(n, 2)`` input takes the int16 entry."""
+    _ddc_decim(decim)
+    words = [freq_word(f, sample_rate) for f in np.asarray(offsets_hz, dtype=np.float64).reshape(-1)]
+    _ddc_words(words)
+    plan = _cached_fir_plan(taps, device)
+    if isinstance(iq, np.ndarray) and iq.dtype == np.int16:
+        return plan.ddc_bank_ci16(iq, words, decim=decim)
+    return plan.ddc_bank(iq, words, decim=decim)
+
+
 class ChannelStream:
     """One channel out of a stream that arrives in pieces: tuned to ``offset_hz`` from the centre, low-passed by ``taps``,
     decimated by ``decim``.  The offset is rounded to a whole bin of ``sample_rate/4096`` (``shift_bins``; ``tuned_hz`` is the
@@ -1705,3 +1908,89 @@ class ChannelBankStream:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class _DdcStreamBase:
+    """What DdcStream and DdcBankStream share: the plan, the filter, the M - 1 kept samples and the stream index."""
+
+    def __init__(self, plan, taps, decim: int, sample_rate: float, device: int):
+        self.decim = _ddc_decim(decim)
+        self.sample_rate = float(sample_rate)
+        if not self.sample_rate > 0:
+            raise ValueError("sample_rate must be positive")
+        self.out_rate = self.sample_rate / self.decim
+        self._own = plan is None
+        self.plan = SpectrumPlan(FIR_BLOCK, device=device) if plan is None else plan
+        self.ntaps = int(self.plan.set_fir(taps))
+        self.sample_index = 0                              # stream index of the next input sample
+        self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
+
+    def _piece(self, iq):
+        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
+        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
+        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
+            raise ValueError(f"a {type(self).__name__} takes complex or int16 pieces, not both")
+        return x, ci16
+
+    def _advance(self, x, ci16: bool) -> None:
+        keep = self.ntaps - 1
+        if keep:
+            if self._tail is None:
+                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
+            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+        self.sample_index += int(x.shape[0])
+
+    def close(self) -> None:
+        if self._own:
+            self.plan.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DdcStream(_DdcStreamBase):
+    """``ChannelStream`` as a digital down-converter: tuned to ``offset_hz`` to the nearest 32-bit frequency word (``freq_word``;
+    ``tuned_hz`` is that word's frequency, within ``sample_rate / 2^33`` of the request) and decimated by ANY integer ``decim``
+    in 1..256.  ``push(iq)`` takes pieces of any length (complex64, or int16 ``(n, 2)`` throughout) and returns the output
+    samples whose stream index is a multiple of ``decim`` — however many fall into the piece, none included."""
+
+    def __init__(self, plan, taps, decim: int, offset_hz: float, sample_rate: float, *, device: int = 0):
+        word = freq_word(offset_hz, sample_rate)           # (checks the rate before a plan is made)
+        super().__init__(plan, taps, decim, sample_rate, device)
+        self.freq_word = word
+        self.tuned_hz = freq_word_hz(word, self.sample_rate)
+
+    def push(self, iq) -> np.ndarray:
+        x, ci16 = self._piece(iq)
+        if x.shape[0] == 0:
+            return np.empty(0, dtype=np.complex64)
+        run = self.plan.ddc_ci16 if ci16 else self.plan.ddc
+        out = run(x, self.freq_word, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._advance(x, ci16)
+        return out
+
+
+class DdcBankStream(_DdcStreamBase):
+    """``C`` digital down-converters on one stream that arrives in pieces, from one pass over each piece: a ``DdcStream`` for every
+    offset of ``offsets_hz`` (1..64), with one filter, one decimation and one kept tail.  ``push(iq)`` returns ``(C, n)`` complex64;
+    row ``c`` carries the bits of a ``DdcStream`` tuned to ``offsets_hz[c]`` that was pushed the same pieces.  ``freq_words``,
+    ``tuned_hz``: one entry per channel."""
+
+    def __init__(self, plan, taps, decim: int, offsets_hz, sample_rate: float, *, device: int = 0):
+        words = [freq_word(f, sample_rate) for f in np.asarray(offsets_hz, dtype=np.float64).reshape(-1)]
+        _ddc_words(words)                                  # too few or too many: ValueError
+        super().__init__(plan, taps, decim, sample_rate, device)
+        self.freq_words = words
+        self.tuned_hz = [freq_word_hz(w, self.sample_rate) for w in words]
+
+    def push(self, iq) -> np.ndarray:
+        x, ci16 = self._piece(iq)
+        if x.shape[0] == 0:
+            return np.empty((len(self.freq_words), 0), dtype=np.complex64)
+        run = self.plan.ddc_bank_ci16 if ci16 else self.plan.ddc_bank
+        out = run(x, self.freq_words, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._advance(x, ci16)
+        return out

@@ -20,15 +20,22 @@ from .spectrum import (  # noqa: E402
     ChannelBankStream,
     ChannelStream,
     CrossSpectrum,
+    DdcBankStream,
+    DdcStream,
     SpectrumPlan,
     channel_taps,
     cross_spectrum,
+    ddc,
+    ddc_bank,
+    ddc_taps,
     fft_c64,
     fft_c128,
     fft_ci16,
     fir_bank,
     fir_filter,
     freq_axis,
+    freq_word,
+    freq_word_hz,
     integrated_db,
     integrated_db_ci16,
     pfb_db,
@@ -57,11 +64,16 @@ __all__ = [
     "ChannelBankStream",
     "ChannelStream",
     "CrossSpectrum",
+    "DdcBankStream",
+    "DdcStream",
     "SpectrumPlan",
     "WaterfallBuffer",
     "SdrkError",
     "channel_taps",
     "cross_spectrum",
+    "ddc",
+    "ddc_bank",
+    "ddc_taps",
     "device_count",
     "device_info",
     "fft_c64",
@@ -70,6 +82,8 @@ __all__ = [
     "fir_bank",
     "fir_filter",
     "freq_axis",
+    "freq_word",
+    "freq_word_hz",
     "integrated_db",
     "integrated_db_ci16",
     "is_pinned",
