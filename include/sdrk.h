@@ -318,6 +318,35 @@ int sdrk_exec_device_integrated_ci16_timed_each(sdrk_plan* plan, const void* d_i
 int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                    int detector, int out_form, float scale, float* out);
 
+/* ---- 8-bit input: SigMF ci8 and cu8 -------------------------------------------------
+ * What the two most common radios write: a HackRF signed 8-bit pairs (SigMF "ci8"), an RTL-SDR unsigned ones ("cu8").  A
+ * sample is 2 bytes, I then Q; frame f at sample f*frame_stride (layout rules as the int16 entry points; the buffer need only
+ * be 2-byte aligned).  `iq8_format`, right after the input pointer, says which:
+ *     SDRK_IQ8_SIGNED    (int8)    x[n] = float32(I[n]) + i*float32(Q[n])
+ *     SDRK_IQ8_UNSIGNED  (uint8)   x[n] = (float32(I[n]) - 127.5f) + i*(float32(Q[n]) - 127.5f)     (127.5: mid-scale of 0...255)
+ * both exact in float32 (no -0.0 arises), then exactly what the plan's complex64 entry point computes on those values — the
+ * same bits, at every nfft, stride, window, epilogue and detector, device and host entry alike.  No scale is applied, as with
+ * int16.  Per-frame rows / spectra and the integrated spectra have an 8-bit form; nfft = 4096 reads the bytes inside the
+ * transform (2 bytes per sample in), every other length is widened on the device in chunks of at most 64 MiB first.  Each
+ * entry point has the signature and the refusals of its _ci16 twin, and refuses an f64 plan and a format other than the two
+ * with SDRK_ERR_INVALID; a plan that has refused still works.  The filter bank, spectral kurtosis, cross-spectra, FIR / channel
+ * bank / DDC, Welch, features and waterfall entry points have no 8-bit form. */
+enum sdrk_iq8_format { SDRK_IQ8_SIGNED = 0, SDRK_IQ8_UNSIGNED = 1 };
+int sdrk_exec_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db);
+int sdrk_exec_fft_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
+                           void* out_c64);
+int sdrk_exec_device_ci8(sdrk_plan* plan, const void* d_iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
+                         float* d_out_db, void* stream);
+int sdrk_exec_device_ci8_timed_each(sdrk_plan* plan, const void* d_iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
+                                    float* d_out_db, int launches, float* each_ms);
+int sdrk_exec_device_integrated_ci8(sdrk_plan* plan, const void* d_iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
+                                    size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_integrated_ci8_timed_each(sdrk_plan* plan, const void* d_iq_ci8, int iq8_format, size_t n_groups,
+                                               size_t k_frames, size_t frame_stride, int detector, int out_form, float scale,
+                                               float* d_out, int launches, float* each_ms);
+int sdrk_exec_host_integrated_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
+                                  size_t frame_stride, int detector, int out_form, float scale, float* out);
+
 /* ---- polyphase filter bank spectra: a T-tap weighted fold in front of the transform ------
  * A plain windowed FFT gives every bin the window's response: a wide main lobe, side lobes that fall slowly.  A polyphase
  * filter bank (weighted overlap-add) applies a prototype filter h of T*nfft coefficients (typically a windowed sinc) to T*nfft

@@ -153,6 +153,17 @@ SYMBOLS = [
                                                             c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_integrated_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
                                                c_void_p]),
+    # 8-bit I,Q (SigMF ci8 / cu8): per-frame and integrated, the format (SDRK_IQ8_*) right after the input pointer
+    ("sdrk_exec_host_ci8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_ci8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_ci8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrk_exec_device_ci8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_device_integrated_ci8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                c_void_p, c_void_p]),
+    ("sdrk_exec_device_integrated_ci8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                           c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_integrated_ci8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                              c_void_p]),
     # polyphase filter bank: T blocks folded under a prototype of T*nfft coefficients in front of the transform
     ("sdrk_plan_set_pfb", c_int, [c_void_p, c_int, c_void_p]),
     ("sdrk_plan_pfb_taps", c_int, [c_void_p]),

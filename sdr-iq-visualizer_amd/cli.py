@@ -155,8 +155,9 @@ def main(argv=None) -> int:
     if args.cmd == "extract":
         return _extract(args, sigmf_io, spectrum)
     # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
-    # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for
-    samples, meta = sigmf_io.read_sigmf(args.path, native=True)
+    # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for.
+    # A ci8 / cu8 recording stays 8-bit for the spectrum row and the --integrate rows; every other option widens it on the host.
+    samples, meta = sigmf_io.read_sigmf(args.path, native="all")
     pair = None
     if args.cross:   # both channels as they are stored (element n: sample n of channel 0, then of channel 1); the rest: channel 0
         g = meta.get("global", {})
@@ -169,6 +170,9 @@ def main(argv=None) -> int:
         pair, _ = sigmf_io.read_sigmf_channels(args.path)
         samples = np.ascontiguousarray(pair[:, 0])
     raw16 = samples if samples.dtype == np.int16 else None
+    raw8 = np.ascontiguousarray(samples) if samples.dtype in (np.int8, np.uint8) else None
+    if raw8 is not None:
+        samples = spectrum.iq8_to_c64(raw8) if (args.welch or args.pfb or args.sk) else raw8
     n_samples = int(samples.shape[0])
     if n_samples < args.nfft:
         print(f"recording has {n_samples} samples, need {args.nfft}", file=sys.stderr)
@@ -176,6 +180,8 @@ def main(argv=None) -> int:
     fs, fc = meta["sample_rate"], meta["center_freq"]
     if raw16 is not None:
         power_db = spectrum.spectrum_db_ci16(np.ascontiguousarray(raw16[: args.nfft]), window=args.window, device=args.device)
+    elif raw8 is not None:
+        power_db = spectrum.spectrum_db_ci8(raw8[: args.nfft], window=args.window, device=args.device)
     else:
         power_db = spectrum.spectrum_db(samples[: args.nfft], window=args.window, device=args.device)
     freqs = spectrum.freq_axis(args.nfft, fs, fc)
@@ -197,6 +203,9 @@ def main(argv=None) -> int:
         if raw16 is not None:   # the int16 samples as they are: the same rows from half the bytes, nothing widened on the host
             rows = spectrum.integrated_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.integrate, detector=args.detector,
                                                window=args.window, device=args.device)
+        elif raw8 is not None:   # ... and the bytes of a ci8 / cu8 recording as they are
+            rows = spectrum.integrated_db_ci8(raw8, args.nfft, args.integrate, detector=args.detector, window=args.window,
+                                              device=args.device)
         else:
             rows = spectrum.integrated_db(samples, args.nfft, args.integrate, detector=args.detector, window=args.window,
                                           device=args.device)

@@ -6,14 +6,21 @@
 // data.  Every other length (N < 256, the two-pass lengths 2^15 ... 2^22 with the persistent N = 65536 form, chirp-z) runs
 // "widen a chunk of frames into plan-owned complex64 staging, then plan_launch" on the same stream, the staging capped at
 // 64 MiB however many frames the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with 4-byte samples.
-// The integrated int16 entries are integrate_api.hip.  Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
+// The integrated int16 entries are integrate_api.hip.
+//
+// The 8-bit entry points (sdrk_exec_*_ci8: SigMF ci8 / cu8, 2 bytes per sample, the format right after the input pointer) live
+// here too, on the same machinery: N = 4096 is one launch of fft4096_ci8.hip on the caller's data, every other length the same
+// unpack route with kernels_ci8.h's widening copy in front (launch_ci8).  Their integrated forms are integrate_api.hip's.
+// Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <vector>
 
 #include "kernels_ci16.h"
+#include "kernels_ci8.h"
 #include "plan_internal.h"
 
 using namespace sdrk_host;
@@ -22,8 +29,16 @@ namespace {
 
 constexpr size_t CI16_STAGE_BYTES = (size_t)64 << 20;   // complex64 staging of the unpack route, per plan
 constexpr size_t CI16_ELEM = 4;                          // bytes per int16 I,Q sample
+constexpr size_t CI8_ELEM = 2;                           // bytes per 8-bit I,Q sample
+constexpr int FMT_CI16 = -1;                             // unpack_route's format: int16, or an SDRK_IQ8_* value
 
-int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+// in_elem: bytes per input sample; fmt: FMT_CI16, or the 8-bit format whose widening copy feeds the staging instead.
+int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream,
+                 size_t in_elem = CI16_ELEM, int fmt = FMT_CI16) {
+    auto unpack = [&](const void* src, size_t row_stride, void* dst, size_t n_rows, size_t row_len) {
+        return fmt == FMT_CI16 ? sdrk::launch_unpack_ci16(src, row_stride, dst, n_rows, row_len, p->num_cus, stream)
+                               : sdrk::launch_unpack_ci8(src, fmt, row_stride, dst, n_rows, row_len, p->num_cus, stream);
+    };
     const size_t nfft = (size_t)p->nfft;
     const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
     if (n_frames == 1) stride = nfft;
@@ -35,7 +50,8 @@ int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride,
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
     const size_t st_stride = overlapped ? stride : nfft;
-    sdrk_host::Staging& sg = p->ci16;   // one staging per plan: a call on another stream waits for the last one's reads
+    sdrk_host::Staging& sg = p->ci16;   // one staging per plan (int16 and 8-bit calls share it: complex64 either way): a call
+                                        // on another stream waits for the last one's reads
     int st = sg.reserve(0, ((per - 1) * st_stride + nfft) * sizeof(float2));
     if (st == SDRK_OK) st = sg.enter(stream);
     if (st != SDRK_OK) return st;
@@ -46,14 +62,14 @@ int unpack_route(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride,
     // the last 64 are covered by the error check behind sdrk_plan_sync.
     for (size_t f0 = 0; f0 < n_frames && st == SDRK_OK; f0 += per) {
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
-        const char* src = static_cast<const char*>(d_in) + f0 * stride * CI16_ELEM;
+        const char* src = static_cast<const char*>(d_in) + f0 * stride * in_elem;
         hipError_t e;
         if (overlapped || stride == nfft)
-            e = sdrk::launch_unpack_ci16(src, 0, d_stage, 1, (nf - 1) * st_stride + nfft, p->num_cus, stream);
+            e = unpack(src, 0, d_stage, 1, (nf - 1) * st_stride + nfft);
         else
-            e = sdrk::launch_unpack_ci16(src, stride, d_stage, nf, nfft, p->num_cus, stream);
+            e = unpack(src, stride, d_stage, nf, nfft);
         if (e != hipSuccess) {
-            st = fail(SDRK_ERR_HIP, "ci16 unpack launch failed: %s", hipGetErrorString(e));
+            st = fail(SDRK_ERR_HIP, "%s unpack launch failed: %s", fmt == FMT_CI16 ? "ci16" : "ci8", hipGetErrorString(e));
             break;
         }
         st = plan_launch(p, d_stage, nf, st_stride, static_cast<char*>(d_out) + f0 * nfft * out_elem, epilogue, stream,
@@ -78,7 +94,51 @@ int sdrk_host::launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size
     return SDRK_OK;
 }
 
+// One transform of a float32 plan on 8-bit I,Q input of format `fmt` (SDRK_IQ8_*): N = 4096 is fft4096_ci8.hip on the caller's
+// data, every other length (the fft_lds lengths too: that kernel has no 8-bit format) the unpack route.  launch_ci8_fn gives
+// the LaunchFn of a format, for the numpy boundary and the integrated calls; declared in plan_internal.h.
+int sdrk_host::launch_ci8(sdrk_plan* p, const void* d_in, int fmt, size_t n_frames, size_t stride, void* d_out, int epilogue,
+                          hipStream_t stream) {
+    if (p->precision != 32) return fail(SDRK_ERR_INVALID, "ci8 transform requested of a float64 plan");
+    if (n_frames == 0) return SDRK_OK;
+    if (p->nfft != 4096 || p->blu_inner) return unpack_route(p, d_in, n_frames, stride, d_out, epilogue, stream, CI8_ELEM, fmt);
+    const sdrk::LaunchArgs a = plan_launch_args(p, d_in, n_frames, stride, d_out, epilogue, stream);
+    const hipError_t e = sdrk::launch_fft4096_ci8(a, fmt);
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "ci8 kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
 namespace {
+
+template <int FMT>
+int launch_ci8_bound(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+    return launch_ci8(p, d_in, FMT, n_frames, stride, d_out, epilogue, stream);
+}
+
+}  // namespace
+
+LaunchFn sdrk_host::launch_ci8_fn(int fmt) {
+    return fmt == SDRK_IQ8_SIGNED ? launch_ci8_bound<SDRK_IQ8_SIGNED> : launch_ci8_bound<SDRK_IQ8_UNSIGNED>;
+}
+
+int sdrk_host::check_iq8_format(const sdrk_plan* p, int fmt) {
+    if (fmt != SDRK_IQ8_SIGNED && fmt != SDRK_IQ8_UNSIGNED)
+        return fail(SDRK_ERR_INVALID, "iq8_format %d is neither SDRK_IQ8_SIGNED nor SDRK_IQ8_UNSIGNED", fmt);
+    if (p && p->precision != 32) return fail(SDRK_ERR_INVALID, "8-bit I,Q input needs a float32 plan: this one is float64");
+    return SDRK_OK;
+}
+
+namespace {
+
+// byte pairs in; float32 rows or complex64 out.  The kernel reads and writes pinned host memory itself at N = 4096 only (every
+// other length is the unpack route).  SDRK_CI8_ZERO_COPY=0 sends those chunks through the copy engines instead: A/B work
+// (tools/bench_ci8.py).
+HostIo ci8_io(int fmt, int epilogue) {
+    HostIo io = frames_io(CI8_ELEM, 0, launch_ci8_fn(fmt), epilogue);
+    const char* env = getenv("SDRK_CI8_ZERO_COPY");
+    if (!(env && env[0] == '0')) io.zero_copy_min_nfft = io.zero_copy_max_nfft = 4096;
+    return io;
+}
 
 // int16 pairs in; float32 rows or complex64 out.  The kernel reads and writes pinned host memory itself only at the lengths
 // whose transform reads int16 (the unpack route would cross PCIe for its staging's sake).
@@ -110,6 +170,29 @@ int sdrk_exec_device_ci16_timed_each(sdrk_plan* p, const void* d_iq_ci16, size_t
                                      float* d_out_db, int launches, float* each_ms) {
     return exec_device_frames_timed_each(check_exec_f32, launch_ci16, p, d_iq_ci16, n_frames, frame_stride, d_out_db, launches,
                                          each_ms);
+}
+
+int sdrk_exec_host_ci8(sdrk_plan* p, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host(p, iq_ci8, n_frames, frame_stride, out_db, ci8_io(iq8_format, sdrk::EPI_LOGPSD));
+}
+
+int sdrk_exec_fft_host_ci8(sdrk_plan* p, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, void* out_c64) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host(p, iq_ci8, n_frames, frame_stride, out_c64, ci8_io(iq8_format, sdrk::EPI_COMPLEX));
+}
+
+int sdrk_exec_device_ci8(sdrk_plan* p, const void* d_iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, float* d_out_db,
+                         void* stream) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_frames(check_exec_f32, launch_ci8_fn(iq8_format), p, d_iq_ci8, n_frames, frame_stride, d_out_db, stream);
+}
+
+int sdrk_exec_device_ci8_timed_each(sdrk_plan* p, const void* d_iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
+                                    float* d_out_db, int launches, float* each_ms) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_frames_timed_each(check_exec_f32, launch_ci8_fn(iq8_format), p, d_iq_ci8, n_frames, frame_stride, d_out_db,
+                                         launches, each_ms);
 }
 
 int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "integrate_call.h"
+#include "kernels_ci8.h"
 #include "kernels_integrate.h"
 #include "kernels_kgroup_ci16.h"
 #include "kernels_pfb.h"
@@ -53,6 +54,11 @@ IntIo int_io(size_t in_elem, FusedFn fused, LaunchFn transform, const sdrk_plan*
 
 IntIo c64_io() { return int_io(sizeof(float2), sdrk::launch_fft4096_integrate, launch_f32); }
 IntIo ci16_io() { return int_io(4, sdrk::launch_fft4096_kgroup_ci16, launch_ci16); }
+// 8-bit I,Q of format fmt (SDRK_IQ8_*, checked by the caller): the format is bound into both launchers
+IntIo ci8_io(int fmt) {
+    return fmt == SDRK_IQ8_SIGNED ? int_io(2, sdrk::launch_fft4096_kgroup_ci8<SDRK_IQ8_SIGNED>, launch_ci8_fn(fmt))
+                                  : int_io(2, sdrk::launch_fft4096_kgroup_ci8<SDRK_IQ8_UNSIGNED>, launch_ci8_fn(fmt));
+}
 IntIo pfb_io(const sdrk_plan* p) { return int_io(sizeof(float2), sdrk::launch_pfb4096_groups, launch_pfb, p); }
 IntIo pfb_ci16_io(const sdrk_plan* p) { return int_io(4, sdrk::launch_pfb4096_i16_groups, launch_pfb_ci16, p); }
 
@@ -121,6 +127,27 @@ int sdrk_exec_device_integrated_ci16_timed_each(sdrk_plan* p, const void* d_iq_c
 int sdrk_exec_host_integrated_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                    int detector, int out_form, float scale, float* out) {
     return exec_host_integrated(ci16_io(), p, iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
+}
+
+int sdrk_exec_device_integrated_ci8(sdrk_plan* p, const void* d_iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
+                                    size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_integrated(ci8_io(iq8_format), p, d_iq_ci8, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                  stream);
+}
+
+int sdrk_exec_device_integrated_ci8_timed_each(sdrk_plan* p, const void* d_iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
+                                               size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                               int launches, float* each_ms) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_integrated_timed_each(ci8_io(iq8_format), p, d_iq_ci8, n_groups, k_frames, frame_stride, detector, out_form,
+                                             scale, d_out, launches, each_ms);
+}
+
+int sdrk_exec_host_integrated_ci8(sdrk_plan* p, const void* iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
+                                  size_t frame_stride, int detector, int out_form, float scale, float* out) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_integrated(ci8_io(iq8_format), p, iq_ci8, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }
 
 int sdrk_exec_device_pfb_integrated(sdrk_plan* p, const void* d_iq_c64, size_t n_groups, size_t k_frames, size_t frame_stride,

@@ -375,6 +375,13 @@ inline HostIo frames_io(size_t in_elem, size_t in_span, LaunchFn launch, int epi
 // One transform of a float32 plan on int16 I,Q input (4 bytes per sample), the ci16 form of plan_launch: a LaunchFn.
 int launch_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 
+// One transform of a float32 plan on 8-bit I,Q input (2 bytes per sample; fmt: SDRK_IQ8_SIGNED / _UNSIGNED), the LaunchFn
+// that has a format bound into it, and the refusal every 8-bit entry point makes first: a format that is neither, a float64 plan
+// (a NULL plan is left to the checks behind it).
+int launch_ci8(sdrk_plan* p, const void* d_in, int fmt, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
+LaunchFn launch_ci8_fn(int fmt);
+int check_iq8_format(const sdrk_plan* p, int fmt);
+
 // ---- pfb_api.hip ----
 // One polyphase-filter-bank transform of a float32 plan on a raw complex64 stream (taps * nfft samples per frame), and the
 // same on interleaved int16 I,Q (4 bytes per sample): LaunchFns.  N = 4096 is one launch; every other length folds chunks of

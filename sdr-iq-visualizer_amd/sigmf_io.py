@@ -1,6 +1,8 @@
 """Minimal SigMF reader/writer for ``cf32_le`` recordings (BASELINE.json config 1), and for ``ci16_le`` ones in their own
 format (``write_sigmf(..., datatype="ci16_le")``, ``read_sigmf(..., native=True)`` -> the ``(n, 2)`` int16 array the
-``*_ci16`` spectrum functions take).
+``*_ci16`` spectrum functions take).  The 8-bit formats of the common radios, ``ci8`` (signed: a HackRF) and ``cu8``
+(unsigned, mid-scale 127.5: an RTL-SDR), are written from and — with ``native="all"`` — read back as ``(n, 2)`` int8 / uint8
+arrays for the ``*_ci8`` functions.
 
 Format = what the reference's dashboard exports (app/dashboard/callbacks.py:285-319):
 a ``.sigmf-data`` file of interleaved little-endian float32 I,Q and a ``.sigmf-meta``
@@ -27,7 +29,9 @@ from typing import Optional, Tuple
 import numpy as np
 
 _DTYPES = {"cf32_le": np.dtype("<c8"), "cf64_le": np.dtype("<c16"),
-           "ci16_le": np.dtype("<i2"), "ci8": np.dtype("i1")}
+           "ci16_le": np.dtype("<i2"), "ci8": np.dtype("i1"), "cu8": np.dtype("u1")}
+_CU8_MID = np.float32(127.5)          # mid-scale of 0 ... 255: cu8 decodes to (I - 127.5) + 1j*(Q - 127.5)
+_NATIVE = {"ci16_le": np.int16, "ci8": np.int8, "cu8": np.uint8}   # the (n, 2) dtype read_sigmf(native=...) gives back
 
 
 def make_metadata(sample_rate: float, center_freq: float, *, description: str = "IQ recording",
@@ -70,14 +74,34 @@ def _to_ci16(samples) -> np.ndarray:
     return parts.astype("<i2")
 
 
+def _to_iq8(samples, datatype: str) -> np.ndarray:
+    """``(n, 2)`` int8 (``ci8``) / uint8 (``cu8``) from an array of that dtype and shape ``(..., 2)`` (as is), or from complex
+    samples that the format holds exactly: whole I and Q in [-128, 127] for ci8; I + 127.5 and Q + 127.5 whole and in
+    [0, 255] for cu8 (what the reader gives back).  Anything else would lose information: ValueError."""
+    dt = _NATIVE[datatype]
+    x = np.asarray(samples)
+    if x.dtype == dt and x.ndim >= 2 and x.shape[-1] == 2:
+        return np.ascontiguousarray(x.reshape(-1, 2))
+    if x.dtype in (np.int8, np.uint8):
+        raise ValueError(f"datatype={datatype!r} takes an (n, 2) {np.dtype(dt).name} array, got {x.dtype} of shape {x.shape}")
+    z = x.reshape(-1).astype(np.complex128)
+    parts = np.stack([z.real, z.imag], axis=-1) + (127.5 if datatype == "cu8" else 0.0)
+    lo, hi = (0, 255) if datatype == "cu8" else (-128, 127)
+    if not np.all(parts == np.rint(parts)) or parts.min(initial=lo) < lo or parts.max(initial=hi) > hi:
+        raise ValueError(f"datatype={datatype!r} needs samples whose I and Q" + (" + 127.5" if datatype == "cu8" else "")
+                         + f" are integers in [{lo}, {hi}]")
+    return parts.astype(dt)
+
+
 def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float, datatype: str = "cf32_le",
                 num_channels: int = 1, **meta_kw) -> Tuple[str, str]:
     """Write ``<base>.sigmf-data`` (cf32_le, or ci16_le on request: interleaved int16 I,Q from an int16 ``(n, 2)`` array or
-    from integer-valued complex samples) and ``<base>.sigmf-meta``; returns both paths.
+    from integer-valued complex samples; or ci8 / cu8: interleaved bytes from an ``(n, 2)`` int8 / uint8 array or from complex
+    samples the format holds exactly) and ``<base>.sigmf-meta``; returns both paths.
     ``num_channels=C`` (> 1): ``samples`` is ``(n, C)`` complex (or ``(n, C, 2)`` int16), stored with the channels
     interleaved per sample instant and ``core:num_channels = C`` in the metadata."""
-    if datatype not in ("cf32_le", "ci16_le"):
-        raise ValueError(f"write_sigmf writes 'cf32_le' or 'ci16_le', not {datatype!r}")
+    if datatype not in ("cf32_le", "ci16_le", "ci8", "cu8"):
+        raise ValueError(f"write_sigmf writes 'cf32_le', 'ci16_le', 'ci8' or 'cu8', not {datatype!r}")
     num_channels = int(num_channels)
     if num_channels < 1:
         raise ValueError("num_channels must be >= 1")
@@ -89,10 +113,12 @@ def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float,
                              f"{' (or (n, C, 2) int16)' if int16 else ''}, got {shape}")
         meta_kw["num_channels"] = num_channels   # (C-order flattening below interleaves the channels)
     data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
-    if datatype == "ci16_le":
-        _to_ci16(samples).tofile(data_path)
+    if datatype != "cf32_le":
+        if datatype != "ci16_le" and num_channels > 1:
+            raise ValueError(f"datatype={datatype!r} is written with one channel")
+        (_to_ci16(samples) if datatype == "ci16_le" else _to_iq8(samples, datatype)).tofile(data_path)
         with open(meta_path, "w") as fh:
-            json.dump(make_metadata(sample_rate, center_freq, datatype="ci16_le", **meta_kw), fh, indent=2)
+            json.dump(make_metadata(sample_rate, center_freq, datatype=datatype, **meta_kw), fh, indent=2)
         return data_path, meta_path
     x = np.asarray(samples)
     if x.dtype != np.complex64:                       # callbacks.py:307-308
@@ -107,17 +133,37 @@ def _decode(raw: bytes, datatype: str) -> np.ndarray:
     if datatype not in _DTYPES:
         raise ValueError(f"unsupported core:datatype {datatype!r} (supported: {sorted(_DTYPES)})")
     a = np.frombuffer(raw, dtype=_DTYPES[datatype])
-    if datatype.startswith("ci"):                     # interleaved integers -> complex64
+    if datatype == "cu8":                             # unsigned bytes around mid-scale 127.5 -> complex64 (exact)
+        a = (a[: a.size // 2 * 2].astype(np.float32) - _CU8_MID).view(np.complex64)
+    elif datatype.startswith("ci"):                   # interleaved integers -> complex64
         a = a[: a.size // 2 * 2].astype(np.float32).view(np.complex64)
     return a.astype(np.complex64, copy=False)
 
 
-def read_sigmf(path: str, max_samples: Optional[int] = None, native: bool = False) -> Tuple[np.ndarray, dict]:
+def _native_types(native) -> tuple:
+    """The datatypes ``read_sigmf(native=...)`` returns raw: ``True`` keeps its first meaning (``ci16_le`` alone), ``"all"``
+    is every integer format with entry points of its own, a name or a collection of names is those."""
+    if native is True:
+        return ("ci16_le",)
+    if not native:
+        return ()
+    if native == "all":
+        return tuple(_NATIVE)
+    names = (native,) if isinstance(native, str) else tuple(native)
+    for n in names:
+        if n not in _NATIVE:
+            raise ValueError(f"native={native!r}: {n!r} is none of {sorted(_NATIVE)}")
+    return names
+
+
+def read_sigmf(path: str, max_samples: Optional[int] = None, native=False) -> Tuple[np.ndarray, dict]:
     """Read a recording given its ``.sigmf-meta``, ``.sigmf-data``, base name, or the
     ``.zip`` the dashboard's download button produces.  Returns ``(samples complex64, meta)``;
     ``meta['sample_rate']`` and ``meta['center_freq']`` are lifted out for convenience.
     ``native=True``: a ``ci16_le`` recording comes back as its own ``(n, 2)`` int16 array, not widened (for the ``*_ci16``
-    spectrum functions); every other datatype as without it."""
+    spectrum functions); every other datatype as without it.  ``native="all"``, or a collection of datatype names (``"ci16_le"``,
+    ``"ci8"``, ``"cu8"``): ``ci8`` / ``cu8`` recordings too come back raw, ``(n, 2)`` int8 / uint8, for the ``*_ci8`` functions."""
+    raw_types = _native_types(native)
     if path.endswith(".zip"):
         with zipfile.ZipFile(path) as z:
             names = z.namelist()
@@ -136,9 +182,9 @@ def read_sigmf(path: str, max_samples: Optional[int] = None, native: bool = Fals
         with open(base + ".sigmf-data", "rb") as fh:
             raw = fh.read() if max_samples is None else fh.read(int(max_samples) * itemsize * 2)
     g = meta.get("global", {})
-    if native and g.get("core:datatype") == "ci16_le":
-        a = np.frombuffer(raw, dtype="<i2")
-        samples = a[: a.size // 2 * 2].reshape(-1, 2).astype(np.int16, copy=False)
+    if g.get("core:datatype") in raw_types:
+        a = np.frombuffer(raw, dtype=_DTYPES[g["core:datatype"]])
+        samples = a[: a.size // 2 * 2].reshape(-1, 2).astype(_NATIVE[g["core:datatype"]], copy=False)
     else:
         samples = _decode(raw, g.get("core:datatype", "cf32_le"))
     if max_samples is not None:

@@ -27,6 +27,10 @@ calls ``ci16_le``: a C-contiguous int16 array whose last axis holds (I, Q).  ``x
 the float32 path — the result has the same bits as the complex64 call on the widened samples, from half the input bytes.
 No scale is applied (fold 1/32768 into a custom window, or add a constant to the dB rows).
 
+``*_ci8`` take the 8-bit pairs of SigMF ``ci8`` (int8: ``x = I + 1j*Q``) and ``cu8`` (uint8: ``x = (I - 127.5) + 1j*(Q - 127.5)``)
+the same way — the array's dtype is the format — for per-frame rows / spectra and integrated spectra: the bits of the complex64
+call on ``iq8_to_c64(iq)``, from a quarter of the input bytes.
+
 ``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` / ``pfb_integrate`` and the module functions ``pfb_db`` and
 ``pfb_integrated_db``) put a polyphase filter bank front end before the transform: a prototype filter of ``T*nfft`` float32 coefficients (``pfb_prototype``: a windowed
 sinc) weights ``T*nfft`` consecutive samples, the ``T`` blocks are summed into ``nfft`` samples (float32, products and sums
@@ -128,6 +132,42 @@ def _as_ci16(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
         want = "(N, 2) or (B, N, 2)" if nfft is None else f"({nfft}, 2) or (B, {nfft}, 2)"
         raise ValueError(f"ci16 frames must have shape {want}, got {a.shape}")
     return a
+
+
+IQ8_SIGNED, IQ8_UNSIGNED = 0, 1      # SDRK_IQ8_SIGNED / SDRK_IQ8_UNSIGNED (include/sdrk.h)
+
+
+def _as_ci8(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
+    """Check an 8-bit I,Q array (no copy, no conversion): C-contiguous int8 (SigMF ci8, signed) or uint8 (cu8, unsigned),
+    last axis of length 2; shapes as ``_as_ci16``.  The dtype is the format.  Anything else is a ValueError, before any
+    device call."""
+    if not isinstance(a, np.ndarray) or a.dtype not in (np.int8, np.uint8):
+        raise ValueError(f"8-bit I,Q input must be a numpy int8 (ci8) or uint8 (cu8) array of (I, Q) pairs, got "
+                         f"{getattr(a, 'dtype', type(a).__name__)}")
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError(f"8-bit I,Q input must have a last axis of length 2 (I, Q), got shape {a.shape}")
+    if not a.flags.c_contiguous:
+        raise ValueError("8-bit I,Q input must be C-contiguous (interleaved I, Q)")
+    if stream:
+        if a.ndim != 2:
+            raise ValueError(f"8-bit I,Q stream must have shape (n_samples, 2), got {a.shape}")
+    elif a.ndim > 3 or (nfft is not None and a.shape[-2] != nfft):
+        want = "(N, 2) or (B, N, 2)" if nfft is None else f"({nfft}, 2) or (B, {nfft}, 2)"
+        raise ValueError(f"8-bit I,Q frames must have shape {want}, got {a.shape}")
+    return a
+
+
+def _iq8_format(a: np.ndarray) -> int:
+    """The C format code of a checked 8-bit array: int8 is signed, uint8 unsigned."""
+    return IQ8_SIGNED if a.dtype == np.int8 else IQ8_UNSIGNED
+
+
+def iq8_to_c64(a) -> np.ndarray:
+    """What the 8-bit entry points compute on, as complex64: ``I + 1j*Q`` for int8 pairs, ``(I - 127.5) + 1j*(Q - 127.5)`` for
+    uint8 pairs (127.5: the mid-scale of 0...255); exact in float32."""
+    x = _as_ci8(np.ascontiguousarray(a))
+    f = x.astype(np.float32) - (np.float32(0.0) if x.dtype == np.int8 else np.float32(127.5))
+    return np.ascontiguousarray(f).view(np.complex64)[..., 0]
 
 
 def _as_iq2_c64(iq2) -> np.ndarray:
@@ -338,10 +378,20 @@ class _Mode(NamedTuple):
     sk_host: str                # mean power and spectral kurtosis per k frames: host arrays
     sk_device: str              # ... device pointers
     sk_timed_each: str          # ... timed launches
+    iq8: bool = False           # 8-bit I,Q pairs in: the entry points take the format right after the input pointer
 
     def stream(self, iq) -> np.ndarray:
-        """One contiguous stream as the entry points read it: ``(n,)`` complex64, or checked ``(n, 2)`` int16."""
+        """One contiguous stream as the entry points read it: ``(n,)`` complex64, or checked ``(n, 2)`` int16 / int8 / uint8."""
+        if self.iq8:
+            return _as_ci8(iq, stream=True)
         return _as_ci16(iq, stream=True) if self.ci16 else _as_c64(iq).reshape(-1)
+
+    def entry(self, name: str, fmt: Optional[int] = None):
+        """The C entry point ``name``; of an 8-bit mode, with the format ``fmt`` bound in behind the input pointer."""
+        fn = getattr(lib(), name)
+        if not self.iq8:
+            return fn
+        return lambda handle, iq, *rest: fn(handle, iq, c_int(int(fmt)), *rest)
 
 
 class _Integ(NamedTuple):
@@ -360,6 +410,9 @@ _CI16 = _Mode(True, False, "sdrk_exec_host_ci16", "sdrk_exec_fft_host_ci16", "sd
               "sdrk_exec_device_ci16_timed_each", "sdrk_exec_host_integrated_ci16", "sdrk_exec_device_integrated_ci16",
               "sdrk_exec_device_integrated_ci16_timed_each",
               "sdrk_exec_host_sk_ci16", "sdrk_exec_device_sk_ci16", "sdrk_exec_device_sk_ci16_timed_each")
+_CI8 = _Mode(False, False, "sdrk_exec_host_ci8", "sdrk_exec_fft_host_ci8", "sdrk_exec_device_ci8",
+             "sdrk_exec_device_ci8_timed_each", "sdrk_exec_host_integrated_ci8", "sdrk_exec_device_integrated_ci8",
+             "sdrk_exec_device_integrated_ci8_timed_each", "", "", "", iq8=True)      # (no spectral-kurtosis form)
 _PFB = _Mode(False, True, "sdrk_exec_host_pfb", "sdrk_exec_fft_host_pfb", "sdrk_exec_device_pfb",
              "sdrk_exec_device_pfb_timed_each", "sdrk_exec_host_pfb_integrated", "sdrk_exec_device_pfb_integrated",
              "sdrk_exec_device_pfb_integrated_timed_each",
@@ -562,7 +615,7 @@ class SpectrumPlan:
         shape = (rows, self.nfft)
         res = np.empty(shape, dtype=np.complex64) if spectra else self._out_array(out, shape, np.float32)
         if rows:
-            fn = getattr(lib(), m.host_fft if spectra else m.host_db)
+            fn = m.entry(m.host_fft if spectra else m.host_db, _iq8_format(x) if m.iq8 else None)
             self._run_host(fn, x, rows, self.nfft if hop is None else int(hop), res)
         return res
 
@@ -576,7 +629,7 @@ class SpectrumPlan:
         res = np.empty((groups, 2, self.nfft) if i.sk else (groups, self.nfft), dtype=np.float32)
         if groups:
             with self._lock:
-                check(getattr(lib(), m.sk_host if i.sk else m.int_host)(
+                check(m.entry(m.sk_host if i.sk else m.int_host, _iq8_format(x) if m.iq8 else None)(
                     self.handle, x.ctypes.data_as(c_void_p), c_size_t(groups), c_size_t(int(i.k)),
                     c_size_t(self.nfft if hop is None else int(hop)), *codes, c_float(i.scale), res.ctypes.data_as(c_void_p)))
         return res
@@ -599,19 +652,19 @@ class SpectrumPlan:
         return [c_void_p(d_iq), c_size_t(n), c_size_t(int(i.k)), c_size_t(stride), *codes, c_float(i.scale), c_void_p(d_out)]
 
     def _exec_device(self, m: _Mode, d_iq: int, n: int, d_out: int, frame_stride: Optional[int], stream: int,
-                     i: Optional[_Integ] = None, *, what: str = "") -> None:
+                     i: Optional[_Integ] = None, *, what: str = "", fmt: Optional[int] = None) -> None:
         args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
         with self._lock:
             fn = m.device if i is None else (m.sk_device if i.sk else m.int_device)
-            check(getattr(lib(), fn)(self.handle, *args, c_void_p(stream) if stream else None))
+            check(m.entry(fn, fmt)(self.handle, *args, c_void_p(stream) if stream else None))
 
     def _exec_device_timed_each(self, m: _Mode, d_iq: int, n: int, d_out: int, launches: int, frame_stride: Optional[int],
-                                i: Optional[_Integ] = None, *, what: str = "") -> list:
+                                i: Optional[_Integ] = None, *, what: str = "", fmt: Optional[int] = None) -> list:
         args = self._device_args(m, d_iq, n, d_out, frame_stride, i, what)
         ms = (c_float * int(launches))()
         with self._lock:
             fn = m.timed_each if i is None else (m.sk_timed_each if i.sk else m.int_timed_each)
-            check(getattr(lib(), fn)(self.handle, *args, int(launches), ms))
+            check(m.entry(fn, fmt)(self.handle, *args, int(launches), ms))
         return [float(v) for v in ms]
 
     # -- int16 I,Q input (float32 plans; same bits as the complex64 calls on the widened samples) --------------
@@ -656,6 +709,47 @@ class SpectrumPlan:
                                frame_stride: Optional[int] = None) -> float:
         """The same, all launches together (the sum of the per-launch times)."""
         return float(sum(self.exec_device_ci16_timed_each(d_iq, n_frames, d_out, launches, frame_stride=frame_stride)))
+
+    # -- 8-bit I,Q input, SigMF ci8 (int8) / cu8 (uint8): the array's dtype is the format; float32 plans; the same bits as
+    #    the complex64 calls on iq8_to_c64 of the samples --------------------------------------------------------------
+    def _frames_ci8(self, iq):
+        x = _as_ci8(iq, self.nfft)
+        self._float32_only("8-bit I,Q input")
+        return (x.reshape(1, self.nfft, 2), True) if x.ndim == 2 else (x, False)
+
+    def spectrum_db_ci8(self, iq, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """float32 rows of 8-bit I,Q frames ``(nfft, 2)`` or ``(B, nfft, 2)``, int8 (ci8) or uint8 (cu8): bit-identical to
+        ``spectrum_db`` on ``iq8_to_c64(iq)``."""
+        x, one = self._frames_ci8(iq)
+        res = self._out_array(out, (self.nfft,) if one else x.shape[:2], np.float32)
+        if x.shape[0]:
+            self._run_host(_CI8.entry(_CI8.host_db, _iq8_format(x)), x, x.shape[0], self.nfft, res)
+        return res
+
+    def fft_ci8(self, iq) -> np.ndarray:
+        """complex64 spectrum of 8-bit I,Q frames: bit-identical to ``fft`` on the widened samples."""
+        x, one = self._frames_ci8(iq)
+        out = np.empty(x.shape[:2], dtype=np.complex64)
+        if x.shape[0]:
+            self._run_host(_CI8.entry(_CI8.host_fft, _iq8_format(x)), x, x.shape[0], self.nfft, out)
+        return out[0] if one else out
+
+    def stft_db_ci8(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Spectrogram rows over one contiguous 8-bit I,Q stream ``(n_samples, 2)``; rows as ``stft_db``."""
+        return self._host_rows(_CI8, iq, hop, out, what="8-bit I,Q input")
+
+    def exec_device_ci8(self, d_iq: int, n_frames: int, d_out: int, *, unsigned: bool = False,
+                        frame_stride: Optional[int] = None, stream: int = 0) -> None:
+        """Device pointers: 8-bit I,Q in (2 bytes per sample; ``unsigned``: cu8, else ci8) / float32 rows out, asynchronous
+        on ``stream`` (0: the plan's stream); any number of frames."""
+        self._exec_device(_CI8, d_iq, n_frames, d_out, frame_stride, stream, what="8-bit I,Q input",
+                          fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_ci8_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *, unsigned: bool = False,
+                                   frame_stride: Optional[int] = None) -> list:
+        """``exec_device_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_timed_each(_CI8, d_iq, n_frames, d_out, launches, frame_stride, what="8-bit I,Q input",
+                                            fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
 
     def welch_psd(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
         """Averaged periodogram of one contiguous stream, float32 ``(nfft,)``:
@@ -746,6 +840,31 @@ class SpectrumPlan:
         """``exec_device_integrated_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
         return self._exec_device_timed_each(_CI16, d_iq, n_groups, d_out, launches, frame_stride,
                                             _Integ(k, detector, out, scale), what="integrate_ci16")
+
+    # ... from 8-bit I,Q (int8: ci8, uint8: cu8): the bits of the complex64 three on the widened samples, from a quarter of
+    # the input bytes
+    def integrate_ci8(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                      scale: float = 1.0) -> np.ndarray:
+        """``integrate`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)``, int8 or uint8: bit-identical to
+        ``integrate`` on ``iq8_to_c64(iq)``; no scale is applied to the samples.  At nfft = 4096 the bytes are read inside
+        the reducing transform."""
+        return self._host_integrated(_CI8, iq, hop, _Integ(k, detector, out, scale), what="integrate_ci8")
+
+    def exec_device_integrated_ci8(self, d_iq: int, n_groups: int, k: int, d_out: int, *, unsigned: bool = False,
+                                   frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                   scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: 8-bit I,Q in (2 bytes per sample; ``unsigned``: cu8, else ci8), ``n_groups`` float32 rows out,
+        asynchronous on ``stream`` (0: the plan's stream); any number of frames."""
+        self._exec_device(_CI8, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale),
+                          what="integrate_ci8", fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_integrated_ci8_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                              unsigned: bool = False, frame_stride: Optional[int] = None,
+                                              detector: str = "mean", out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_integrated_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_timed_each(_CI8, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale), what="integrate_ci8",
+                                            fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
 
     # -- polyphase filter bank: T blocks folded under a prototype in front of the transform (float32, rectangular plans) ----
     def set_pfb(self, h) -> int:
@@ -1347,6 +1466,11 @@ class SpectrumPlan:
         units of the integer samples: no scale is applied to them)."""
         return self._welch_streamed(_CI16, "welch_psd_streamed_ci16", iq, sample_rate, hop)
 
+    def welch_psd_streamed_ci8(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
+        """``welch_psd_streamed`` over an 8-bit I,Q stream ``(n_samples, 2)``, int8 or uint8: the same bits as on the widened
+        samples (in units of the integer samples: no scale is applied to them)."""
+        return self._welch_streamed(_CI8, "welch_psd_streamed_ci8", iq, sample_rate, hop)
+
     # -- device pointers (bench / pipelines that keep data resident) -------------
     def exec_device(self, d_iq: int, n_frames: int, d_out: int, *, frame_stride: Optional[int] = None,
                     stream: int = 0) -> None:
@@ -1525,6 +1649,43 @@ def stft_db_ci16(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = N
     """``stft_db`` over one contiguous int16 I,Q stream ``(n_samples, 2)``: the same rows, bit for bit."""
     x = _as_ci16(iq, stream=True)
     return _cached_plan(int(nfft), window, eps, shift, device).stft_db_ci16(x, hop)
+
+
+def spectrum_db_ci8(iq, *, window: WindowArg = None, eps: float = 1e-12, shift: bool = True, device: int = 0,
+                    out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``spectrum_db`` for 8-bit I,Q frames ``(N, 2)`` or ``(B, N, 2)``: int8 (SigMF ``ci8``, a HackRF) or uint8 (``cu8``, an
+    RTL-SDR; mid-scale 127.5) — the dtype is the format.  float32 rows with exactly the bits of
+    ``spectrum_db(iq8_to_c64(iq))``, from a quarter of the input bytes.  No scaling to full scale; one device."""
+    x = _as_ci8(iq)
+    return _cached_plan(int(x.shape[-2]), window, eps, shift, device).spectrum_db_ci8(x, out=out)
+
+
+def fft_ci8(iq, *, window: WindowArg = None, shift: bool = False, device: int = 0) -> np.ndarray:
+    """``fft_c64`` for 8-bit I,Q frames ``(N, 2)`` or ``(B, N, 2)``: the same bits as on the widened samples."""
+    x = _as_ci8(iq)
+    return _cached_plan(int(x.shape[-2]), window, 1e-12, shift, device).fft_ci8(x)
+
+
+def stft_db_ci8(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,
+                shift: bool = True, device: int = 0) -> np.ndarray:
+    """``stft_db`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)``: the same rows, bit for bit."""
+    x = _as_ci8(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).stft_db_ci8(x, hop)
+
+
+def integrated_db_ci8(iq, nfft: int, k: int, hop: Optional[int] = None, detector: str = "mean", window: WindowArg = None,
+                      eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """``integrated_db`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)``: the same rows, bit for bit, as on
+    ``iq8_to_c64(iq)``, from a quarter of the input bytes."""
+    x = _as_ci8(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).integrate_ci8(x, k, hop, detector, "db")
+
+
+def welch_psd_streamed_ci8(iq, nfft: int, sample_rate: float, hop: Optional[int] = None, window: WindowArg = "hann",
+                           shift: bool = True, device: int = 0) -> np.ndarray:
+    """``welch_psd_streamed`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
+    x = _as_ci8(iq, stream=True)
+    return _cached_plan(int(nfft), window, 1e-12, shift, device).welch_psd_streamed_ci8(x, sample_rate, hop)
 
 
 def fft_c128(samples, *, window: WindowArg = None, shift: bool = False, device: int = 0) -> np.ndarray:

@@ -31,6 +31,7 @@ from .spectrum import (  # noqa: E402
     fft_c64,
     fft_c128,
     fft_ci16,
+    fft_ci8,
     fir_bank,
     fir_filter,
     freq_axis,
@@ -38,6 +39,7 @@ from .spectrum import (  # noqa: E402
     freq_word_hz,
     integrated_db,
     integrated_db_ci16,
+    integrated_db_ci8,
     pfb_db,
     pfb_db_ci16,
     pfb_integrated_db,
@@ -50,11 +52,14 @@ from .spectrum import (  # noqa: E402
     spectral_kurtosis_ci16,
     spectrum_db,
     spectrum_db_ci16,
+    spectrum_db_ci8,
     stft_db,
     stft_db_ci16,
+    stft_db_ci8,
     welch_psd,
     welch_psd_streamed,
     welch_psd_streamed_ci16,
+    welch_psd_streamed_ci8,
 )
 from .waterfall import WaterfallBuffer  # noqa: E402
 from .hostmem import is_pinned, pinned_empty, registered  # noqa: E402
@@ -79,6 +84,7 @@ __all__ = [
     "fft_c64",
     "fft_c128",
     "fft_ci16",
+    "fft_ci8",
     "fir_bank",
     "fir_filter",
     "freq_axis",
@@ -86,6 +92,7 @@ __all__ = [
     "freq_word_hz",
     "integrated_db",
     "integrated_db_ci16",
+    "integrated_db_ci8",
     "is_pinned",
     "library_path",
     "pfb_db",
@@ -102,9 +109,12 @@ __all__ = [
     "spectral_kurtosis_ci16",
     "spectrum_db",
     "spectrum_db_ci16",
+    "spectrum_db_ci8",
     "stft_db",
     "stft_db_ci16",
+    "stft_db_ci8",
     "welch_psd",
     "welch_psd_streamed",
     "welch_psd_streamed_ci16",
+    "welch_psd_streamed_ci8",
 ]
