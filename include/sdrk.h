@@ -190,7 +190,10 @@ int sdrk_exec_host(sdrk_plan* plan, const void* iq_c64, size_t n_frames,
                    size_t frame_stride, float* out_db);
 
 /* Device in / device out, asynchronous on `stream` (a hipStream_t, or NULL for
- * the plan's own stream).  Same layout rules as sdrk_exec_host. */
+ * the plan's own stream).  Same layout rules as sdrk_exec_host.  An nfft = 4096
+ * call of about 10^5 frames or more is enqueued as several back-to-back launches of
+ * about 65536 frames each (same rows; the kernel's time per frame grows with the
+ * length of a launch: csrc/f4k_split.h). */
 int sdrk_exec_device(sdrk_plan* plan, const void* d_iq_c64, size_t n_frames,
                      size_t frame_stride, float* d_out_db, void* stream);
 

@@ -14,6 +14,7 @@
 #include <new>
 #include <vector>
 
+#include "f4k_split.h"
 #include "kernels.h"
 #include "plan_internal.h"
 
@@ -176,9 +177,19 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
                                       static_cast<char*>(d_out) + f0 * (size_t)N * out_elem, p->num_cus, stream);
             if (e != hipSuccess) break;
         }
-    } else if (p->nfft == 4096)
-        e = sdrk::launch_fft4096(a);
-    else if (sdrk::fft_lds_supports(p->nfft))
+    } else if (p->nfft == 4096) {
+        // A long call goes out as back-to-back launches of about F4K_SPLIT_FRAMES frames each (see there): the frames are
+        // independent, so the rows are the same bits whichever launch computes them.
+        const size_t parts = f4k_split_parts(n_frames);
+        const size_t per = (n_frames + parts - 1) / parts;
+        const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+        for (size_t f0 = 0; f0 < n_frames && e == hipSuccess; f0 += per) {
+            a.d_iq = static_cast<const float2*>(d_iq) + f0 * frame_stride;
+            a.d_out = static_cast<char*>(d_out) + f0 * (size_t)4096 * out_elem;
+            a.n_frames = n_frames - f0 < per ? n_frames - f0 : per;
+            e = sdrk::launch_fft4096(a);
+        }
+    } else if (sdrk::fft_lds_supports(p->nfft))
         e = sdrk::launch_fft_lds(a);
     else if (p->nfft < 4096)
         e = sdrk::launch_fft_small(a);
