@@ -332,8 +332,9 @@ int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t 
  * int16.  Per-frame rows / spectra and the integrated spectra have an 8-bit form; nfft = 4096 reads the bytes inside the
  * transform (2 bytes per sample in), every other length is widened on the device in chunks of at most 64 MiB first.  Each
  * entry point has the signature and the refusals of its _ci16 twin, and refuses an f64 plan and a format other than the two
- * with SDRK_ERR_INVALID; a plan that has refused still works.  The filter bank, spectral kurtosis, cross-spectra, FIR / channel
- * bank / DDC, Welch, features and waterfall entry points have no 8-bit form. */
+ * with SDRK_ERR_INVALID; a plan that has refused still works.  The down-converter has an 8-bit form in a section of its own
+ * (sdrk_exec_*_downconv_iq8, below); the filter bank, spectral kurtosis, cross-spectra, bin-tuned FIR / channel bank, Welch,
+ * features and waterfall entry points have none. */
 enum sdrk_iq8_format { SDRK_IQ8_SIGNED = 0, SDRK_IQ8_UNSIGNED = 1 };
 int sdrk_exec_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db);
 int sdrk_exec_fft_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
@@ -703,6 +704,38 @@ int sdrk_exec_host_ddcbank(sdrk_plan* plan, const void* prefix_c64, const void* 
 int sdrk_exec_host_ddcbank_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, int n_chan,
                                 const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride,
                                 size_t* n_out);
+
+/* ---- the down-converter from 8-bit input: ci8 / cu8 recordings, 2 bytes per sample ----
+ * The single call and the bank of the section above reading interleaved 8-bit I,Q as a HackRF (ci8) or an RTL-SDR (cu8) writes
+ * it, the bytes read inside the overlap-save transform: 2*4096/L + 8/D bytes per input sample, where int16 moves 4*4096/L and
+ * complex64 8*4096/L.  `iq8_format` (SDRK_IQ8_SIGNED / SDRK_IQ8_UNSIGNED, as for the 8-bit spectra) sits right after the samples
+ * pointer; every other argument, sdrk_ddc_outputs and every refusal are those of the _ci16 twin (the timed entries: of the
+ * complex64 ones), and a format other than the two returns SDRK_ERR_INVALID with the message of the 8-bit spectra.  Buffers need
+ * 2-byte alignment only.
+ * Promised: an 8-bit call returns the bits of the complex64 call on the widened samples (x[n] as the 8-bit section defines it),
+ * for every tap count, freq_word, decim, index0 and n_chan, device and host entries alike, however a host call is chunked.  That
+ * includes the last block of a call: positions past n_in count as +0.0 + 0.0i for both formats, as they do for complex64 (and
+ * not as byte 0, which is -127.5 for cu8).
+ * Host entries, NULL prefix: M - 1 samples of byte value 0 for SDRK_IQ8_SIGNED and of byte value 0x80 for SDRK_IQ8_UNSIGNED.
+ * No cu8 byte widens to zero; 0x80 is the nearer mid-scale byte and widens to +0.5 + 0.5i (byte 0 would mean -127.5 - 127.5i).
+ * So a cu8 host call with a NULL prefix equals the complex64 host call given M - 1 samples of 0.5 + 0.5i as its prefix, and a
+ * ci8 one the complex64 call with a NULL prefix.
+ * The bin-tuned FIR / channel-bank calls have no 8-bit form: a freq_word on a bin with a power-of-two decim gives their bits. */
+int sdrk_exec_device_downconv_iq8(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word, int decim,
+                                  uint64_t index0, void* d_out_c64, void* stream);
+int sdrk_exec_device_downconv_iq8_timed_each(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word,
+                                             int decim, uint64_t index0, void* d_out_c64, int launches, float* each_ms);
+int sdrk_exec_host_downconv_iq8(sdrk_plan* plan, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n,
+                                uint32_t freq_word, int decim, uint64_t sample0, void* out_c64, size_t* n_out);
+int sdrk_exec_device_downconvbank_iq8(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, int n_chan,
+                                      const uint32_t* freq_word, int decim, uint64_t index0, void* d_out_c64, size_t out_stride,
+                                      void* stream);
+int sdrk_exec_device_downconvbank_iq8_timed_each(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, int n_chan,
+                                                 const uint32_t* freq_word, int decim, uint64_t index0, void* d_out_c64,
+                                                 size_t out_stride, int launches, float* each_ms);
+int sdrk_exec_host_downconvbank_iq8(sdrk_plan* plan, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n, int n_chan,
+                                    const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride,
+                                    size_t* n_out);
 
 /* ---- measurement probes (bench harness; no reference counterpart) ----------
  * sdrk_stream_ceiling_probe: a plain streaming kernel with the spectrum path's traffic

@@ -234,6 +234,13 @@ SYMBOLS = [
     ("sdrk_exec_device_ddcbank_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_ddcbank", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("sdrk_exec_host_ddcbank_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
+    # ... from 8-bit I,Q (SigMF ci8 / cu8): the format (SDRK_IQ8_*) right after the samples pointer
+    ("sdrk_exec_device_downconv_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_downconv_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_downconv_iq8", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_device_downconvbank_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_downconvbank_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_downconvbank_iq8", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
 ]
 
 _lib = None

@@ -10,6 +10,7 @@ plots (scripts/process_sigmf_data.py:188-189).  ``extract`` tunes to ``center_fr
 ``sample_rate/4096``), low-passes, decimates by D and writes the channel as a cf32_le SigMF recording at ``sample_rate/D``;
 several offsets are extracted in one pass over the recording and written as ``BASE_0``, ``BASE_1``, ...  With ``--exact`` the
 digital down-converter does it: F is tuned to the nearest 32-bit frequency word (``sample_rate/2^32``) and D is any integer in 1..256.
+A ``ci16_le``, ``ci8`` or ``cu8`` recording is pushed as it is stored (4 and 2 bytes per sample), with or without ``--exact``.
 All transforms run through libsdrk.
 """
 from __future__ import annotations
@@ -32,8 +33,9 @@ EXTRACT_PIECE = 1 << 22            # samples per ChannelStream.push of `extract`
 
 
 def _extract(args, sigmf_io, spectrum) -> int:
-    """One channel of a single-channel cf32_le / ci16_le recording -> a cf32_le recording at sample_rate / decim."""
-    samples, meta = sigmf_io.read_sigmf(args.path, native=True)
+    """One channel of a single-channel recording -> a cf32_le recording at sample_rate / decim.  ci16_le, ci8 and cu8 samples are
+    pushed as the recording holds them (4 and 2 bytes per sample), everything else as complex64."""
+    samples, meta = sigmf_io.read_sigmf(args.path, native="all")
     g = meta.get("global", {})
     if int(g.get("core:num_channels", 1)) != 1:
         print(f"extract takes a single-channel recording; this one has core:num_channels = {g.get('core:num_channels')}",

@@ -3,7 +3,9 @@
 // held by the plan as the polyphase prototype is (kernels_ols.h has the block geometry); and of the channel bank
 // (sdrk_exec_*_chanbank*): C tuned channels from one pass over the input through ols_bank.hip (kernels_ols_bank.h); and of the
 // digital down-converter (sdrk_ddc_outputs, sdrk_exec_*_ddc*, sdrk_exec_*_ddcbank*): the same two calls tuned by a 32-bit frequency
-// word and decimated by any integer, through ddc4096.hip (kernels_ddc.h), with a chunk loop of its own on the same SlotPipe.
+// word and decimated by any integer, through ddc4096.hip (kernels_ddc.h), with a chunk loop of its own on the same SlotPipe; and of
+// the same from interleaved 8-bit I,Q (sdrk_exec_*_downconv_iq8, sdrk_exec_*_downconvbank_iq8) through downconv_iq8.hip: one more
+// input format of that loop and of ddc_launch.
 //
 // A device call is one launch on the caller's stream.  The numpy boundary runs the same launches on the virtual stream
 // prefix || iq in chunks of whole blocks through sdrk_host_pipeline.hip's SlotPipe, one loop (host_fir_chunks) for the single
@@ -279,8 +281,12 @@ int check_ddc_device(const sdrk_plan* p, bool bank, const void* d_in, size_t n_i
     return SDRK_OK;
 }
 
+// What a down-converter call reads: complex64, int16 pairs, or byte pairs of an 8-bit format (in >= 0: the SDRK_IQ8_* value).
+constexpr int DDC_IN_C64 = -2, DDC_IN_CI16 = -1;
+size_t ddc_in_elem(int in) { return in == DDC_IN_C64 ? sizeof(float2) : in == DDC_IN_CI16 ? 4 : 2; }
+
 // One launch: the outputs i < max_blocks L (0: all) of the valid convolution of n_in samples, for every channel.
-int ddc_launch(sdrk_plan* p, bool i16, bool bank, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+int ddc_launch(sdrk_plan* p, int in, bool bank, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
                uint64_t index0, void* d_out, size_t out_stride, size_t max_blocks, hipStream_t stream) {
     sdrk::DdcArgs a;
     a.d_in = d_in;
@@ -298,27 +304,30 @@ int ddc_launch(sdrk_plan* p, bool i16, bool bank, const void* d_in, size_t n_in,
     a.num_cus = p->num_cus;
     a.stream = stream;
     if (sdrk::ddc_launch_outputs(a) == 0) return SDRK_OK;   // nothing kept: a successful no-op
-    const hipError_t e = bank ? (i16 ? sdrk::launch_ddcbank_i16(a) : sdrk::launch_ddcbank(a)) : (i16 ? sdrk::launch_ddc_i16(a) : sdrk::launch_ddc(a));
+    hipError_t e;
+    if (in == DDC_IN_C64) e = bank ? sdrk::launch_ddcbank(a) : sdrk::launch_ddc(a);
+    else if (in == DDC_IN_CI16) e = bank ? sdrk::launch_ddcbank_i16(a) : sdrk::launch_ddc_i16(a);
+    else e = bank ? sdrk::launch_downconvbank_iq8(a, in) : sdrk::launch_downconv_iq8(a, in);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "DDC kernel launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;
 }
 
-int exec_device_ddc(bool i16, bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+int exec_device_ddc(int in, bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
                     uint64_t index0, void* d_out, size_t out_stride, void* stream) {
     int st = check_ddc_device(p, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride);
     if (st != SDRK_OK) return st;
     HIP_TRY(hipSetDevice(p->device));
-    return ddc_launch(p, i16, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0,
+    return ddc_launch(p, in, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0,
                       stream ? static_cast<hipStream_t>(stream) : p->stream);
 }
 
-int exec_device_ddc_timed(bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
+int exec_device_ddc_timed(int in, bool bank, sdrk_plan* p, const void* d_in, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
                           uint64_t index0, void* d_out, size_t out_stride, int launches, float* each_ms) {
     if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
     int st = check_ddc_device(p, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride);
     if (st != SDRK_OK) return st;
     return timed_each(p, launches, each_ms, [&] {
-        return ddc_launch(p, false, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0, p->stream);
+        return ddc_launch(p, in, bank, d_in, n_in, n_chan, freq_word, decim, index0, d_out, out_stride, 0, p->stream);
     });
 }
 
@@ -328,7 +337,7 @@ int exec_device_ddc_timed(bool bank, sdrk_plan* p, const void* d_in, size_t n_in
 // max_blocks L outputs) and the mixer's phase and the keeping follow the stream index, which the chunk's launch is handed as its
 // index0, so the chunking does not show in the bits.  A block yields L / D outputs or one more, so the outputs of a chunk are
 // counted, not multiplied out: chunk [b0, b0 + nb) starts at output ddc_count(b0 L) and holds ddc_count of its own.
-int exec_host_ddc(size_t in_elem, bool bank, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int n_chan,
+int exec_host_ddc(int in, bool bank, sdrk_plan* p, const void* prefix, const void* iq, size_t n, int n_chan,
                   const uint32_t* freq_word, int decim, uint64_t sample0, void* out, size_t out_stride, size_t* n_out) {
     int st = check_ddc_call(p, decim);
     if (st == SDRK_OK && bank) st = check_ddc_chans(n_chan, freq_word);
@@ -339,6 +348,8 @@ int exec_host_ddc(size_t in_elem, bool bank, sdrk_plan* p, const void* prefix, c
     if (bank && out_stride < need) return fail(SDRK_ERR_INVALID, "out_stride=%zu: a plane holds up to %zu outputs of a channel", out_stride, need);
     if (n == 0) return SDRK_OK;
     if (!iq || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
+    const size_t in_elem = ddc_in_elem(in);
+    const int pad = in == SDRK_IQ8_UNSIGNED ? 0x80 : 0;   // the byte of a NULL prefix: 0x80 is mid-scale for unsigned bytes (+0.5)
     uint32_t words[sdrk::DDC_MAX_CHAN];   // read before the call returns: the launches below see this copy
     memcpy(words, freq_word, (size_t)n_chan * sizeof(uint32_t));
     const size_t M = (size_t)p->fir_taps, L = (size_t)sdrk::ols_block_len(p->fir_taps), N = sdrk::OLS_N, planes = (size_t)n_chan;
@@ -359,19 +370,19 @@ int exec_host_ddc(size_t in_elem, bool bank, sdrk_plan* p, const void* prefix, c
         HostSlot* s = nullptr;
         st = pipe.acquire(chunk_in, chunk_out, s);
         if (st != SDRK_OK) return st;
-        // samples V[t0 .. t0 + cn): the part below M - 1 from the prefix (NULL: zeros), the rest from iq
+        // samples V[t0 .. t0 + cn): the part below M - 1 from the prefix (NULL: zeros; 0x80 bytes for cu8), the rest from iq
         char* dst = static_cast<char*>(s->h_in);
         size_t done = 0;
         if (t0 < M - 1) {
             done = M - 1 - t0 < cn ? M - 1 - t0 : cn;
             if (prefix) memcpy(dst, static_cast<const char*>(prefix) + t0 * in_elem, done * in_elem);
-            else memset(dst, 0, done * in_elem);
+            else memset(dst, pad, done * in_elem);
         }
         if (done < cn)
             memcpy(dst + done * in_elem, static_cast<const char*>(iq) + (t0 + done - (M - 1)) * in_elem, (cn - done) * in_elem);
         st = pipe.upload(*s, s->h_in, cn * in_elem);
         if (st == SDRK_OK)
-            st = pipe.submit(*s, ddc_launch(p, in_elem == 4, bank, s->d_in, cn, n_chan, words, decim, sample0 + t0, s->d_out, co, nb, p->stream),
+            st = pipe.submit(*s, ddc_launch(p, in, bank, s->d_in, cn, n_chan, words, decim, sample0 + t0, s->d_out, co, nb, p->stream),
                              {ChunkOut::Planes, static_cast<char*>(out) + o0 * sizeof(float2), co * sizeof(float2), planes,
                               out_stride * sizeof(float2)});
         if (st != SDRK_OK) return st;
@@ -490,52 +501,93 @@ size_t sdrk_ddc_outputs(size_t n_in, int taps, int decim, uint64_t index0) {
 
 int sdrk_exec_device_ddc(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
                          void* d_out_c64, void* stream) {
-    return exec_device_ddc(false, false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
+    return exec_device_ddc(DDC_IN_C64, false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
 }
 
 int sdrk_exec_device_ddc_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
                               void* d_out_c64, void* stream) {
-    return exec_device_ddc(true, false, p, d_in_ci16, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
+    return exec_device_ddc(DDC_IN_CI16, false, p, d_in_ci16, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
 }
 
 int sdrk_exec_device_ddc_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
                                     void* d_out_c64, int launches, float* each_ms) {
-    return exec_device_ddc_timed(false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, launches, each_ms);
+    return exec_device_ddc_timed(DDC_IN_C64, false, p, d_in_c64, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, launches, each_ms);
 }
 
 int sdrk_exec_host_ddc(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, uint32_t freq_word, int decim,
                        uint64_t sample0, void* out_c64, size_t* n_out) {
-    return exec_host_ddc(sizeof(float2), false, p, prefix_c64, iq_c64, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
+    return exec_host_ddc(DDC_IN_C64, false, p, prefix_c64, iq_c64, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
 }
 
 int sdrk_exec_host_ddc_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, uint32_t freq_word, int decim,
                             uint64_t sample0, void* out_c64, size_t* n_out) {
-    return exec_host_ddc(4, false, p, prefix_ci16, iq_ci16, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
+    return exec_host_ddc(DDC_IN_CI16, false, p, prefix_ci16, iq_ci16, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
 }
 
 int sdrk_exec_device_ddcbank(sdrk_plan* p, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
                              uint64_t index0, void* d_out_c64, size_t out_stride, void* stream) {
-    return exec_device_ddc(false, true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
+    return exec_device_ddc(DDC_IN_C64, true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
 }
 
 int sdrk_exec_device_ddcbank_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, int n_chan, const uint32_t* freq_word, int decim,
                                   uint64_t index0, void* d_out_c64, size_t out_stride, void* stream) {
-    return exec_device_ddc(true, true, p, d_in_ci16, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
+    return exec_device_ddc(DDC_IN_CI16, true, p, d_in_ci16, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
 }
 
 int sdrk_exec_device_ddcbank_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, int n_chan, const uint32_t* freq_word,
                                         int decim, uint64_t index0, void* d_out_c64, size_t out_stride, int launches, float* each_ms) {
-    return exec_device_ddc_timed(true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, launches, each_ms);
+    return exec_device_ddc_timed(DDC_IN_C64, true, p, d_in_c64, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, launches, each_ms);
 }
 
 int sdrk_exec_host_ddcbank(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, int n_chan, const uint32_t* freq_word,
                            int decim, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
-    return exec_host_ddc(sizeof(float2), true, p, prefix_c64, iq_c64, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
+    return exec_host_ddc(DDC_IN_C64, true, p, prefix_c64, iq_c64, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
 }
 
 int sdrk_exec_host_ddcbank_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, int n_chan,
                                 const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride, size_t* n_out) {
-    return exec_host_ddc(4, true, p, prefix_ci16, iq_ci16, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
+    return exec_host_ddc(DDC_IN_CI16, true, p, prefix_ci16, iq_ci16, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
+}
+
+// ---- the down-converter from interleaved 8-bit I,Q (SigMF ci8 / cu8): the entries above with the format behind the samples ----
+int sdrk_exec_device_downconv_iq8(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word, int decim,
+                                  uint64_t index0, void* d_out_c64, void* stream) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_ddc(iq8_format, false, p, d_in_iq8, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, stream);
+}
+
+int sdrk_exec_device_downconv_iq8_timed_each(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word,
+                                             int decim, uint64_t index0, void* d_out_c64, int launches, float* each_ms) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_ddc_timed(iq8_format, false, p, d_in_iq8, n_in, 1, &freq_word, decim, index0, d_out_c64, 0, launches, each_ms);
+}
+
+int sdrk_exec_host_downconv_iq8(sdrk_plan* p, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n, uint32_t freq_word,
+                                int decim, uint64_t sample0, void* out_c64, size_t* n_out) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_ddc(iq8_format, false, p, prefix_iq8, iq_iq8, n, 1, &freq_word, decim, sample0, out_c64, 0, n_out);
+}
+
+int sdrk_exec_device_downconvbank_iq8(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, int n_chan,
+                                      const uint32_t* freq_word, int decim, uint64_t index0, void* d_out_c64, size_t out_stride,
+                                      void* stream) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_ddc(iq8_format, true, p, d_in_iq8, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, stream);
+}
+
+int sdrk_exec_device_downconvbank_iq8_timed_each(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, int n_chan,
+                                                 const uint32_t* freq_word, int decim, uint64_t index0, void* d_out_c64,
+                                                 size_t out_stride, int launches, float* each_ms) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_ddc_timed(iq8_format, true, p, d_in_iq8, n_in, n_chan, freq_word, decim, index0, d_out_c64, out_stride, launches,
+                                 each_ms);
+}
+
+int sdrk_exec_host_downconvbank_iq8(sdrk_plan* p, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n, int n_chan,
+                                    const uint32_t* freq_word, int decim, uint64_t sample0, void* out_c64, size_t out_stride,
+                                    size_t* n_out) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_ddc(iq8_format, true, p, prefix_iq8, iq_iq8, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
 }
 
 }  // extern "C"

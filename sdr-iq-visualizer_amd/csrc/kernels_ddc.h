@@ -81,7 +81,7 @@ __host__ __device__ __forceinline__ OlsC ddc_mix(OlsC v, OlsC W, uint32_t phase)
 
 // One launch: a single channel (n_chan = 1, out_stride ignored) or the bank (plane c at d_out + c out_stride).
 struct DdcArgs {
-    const void* d_in = nullptr;          // complex64, or int16 I,Q pairs
+    const void* d_in = nullptr;          // complex64, or int16 / 8-bit I,Q pairs
     size_t n_in = 0;                     // samples, >= taps
     int taps = 0;                        // M
     int decim = 1;                       // D: any integer in 1 .. 256
@@ -101,6 +101,10 @@ hipError_t launch_ddc(const DdcArgs& a);           // complex64 samples, freq_wo
 hipError_t launch_ddc_i16(const DdcArgs& a);       // int16 I,Q: the same bits on the widened samples
 hipError_t launch_ddcbank(const DdcArgs& a);       // C planes, plane c = launch_ddc with freq_word[c]
 hipError_t launch_ddcbank_i16(const DdcArgs& a);
+// downconv_iq8.hip: interleaved 8-bit I,Q (2 bytes per sample), fmt = IQ8_SIGNED / IQ8_UNSIGNED of kernels_ci8.h: the bits of
+// launch_ddc / launch_ddcbank on the widened samples, the padding past n_in included (+0.0, also for unsigned bytes)
+hipError_t launch_downconv_iq8(const DdcArgs& a, int fmt);
+hipError_t launch_downconvbank_iq8(const DdcArgs& a, int fmt);
 
 // blocks, valid-convolution outputs and kept outputs of a launch: all of them, or what max_blocks leaves (valid arguments only)
 inline size_t ddc_launch_blocks(const DdcArgs& a) {

@@ -11,9 +11,11 @@ from .spectrum import (fft_c64, fft_ci16, freq_axis, integrated_db, integrated_d
                        spectrum_db, spectrum_db_ci16, stft_db, stft_db_ci16, welch_psd, welch_psd_streamed,
                        welch_psd_streamed_ci16)
 from .spectrum import (fft_ci8, integrated_db_ci8, spectrum_db_ci8, stft_db_ci8, welch_psd_streamed_ci8)  # noqa: F401
+from .spectrum import ddc_bank_ci8, ddc_ci8  # noqa: F401
 from .waterfall import WaterfallBuffer  # noqa: F401
 
 __all__ = ["spectrum_db", "fft_c64", "freq_axis", "process_frame", "stft_db", "welch_psd", "WaterfallBuffer",
            "spectrum_db_ci16", "fft_ci16", "stft_db_ci16", "integrated_db", "welch_psd_streamed",
            "integrated_db_ci16", "welch_psd_streamed_ci16",
-           "spectrum_db_ci8", "fft_ci8", "stft_db_ci8", "integrated_db_ci8", "welch_psd_streamed_ci8"]
+           "spectrum_db_ci8", "fft_ci8", "stft_db_ci8", "integrated_db_ci8", "welch_psd_streamed_ci8",
+           "ddc_ci8", "ddc_bank_ci8"]

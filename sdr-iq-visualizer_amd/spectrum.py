@@ -1318,16 +1318,29 @@ class SpectrumPlan:
                 raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
         return x, pre
 
-    def _host_ddc(self, sym: str, x: np.ndarray, prefix, word, decim: int, sample0: int) -> np.ndarray:
+    def _ddc_input_ci8(self, iq, prefix):
+        m = self._fir_ready()
+        x = _as_ci8(iq, stream=True)
+        pre = None
+        if prefix is not None and m > 1:
+            pre = _as_ci8(prefix, stream=True)
+            if pre.dtype != x.dtype:
+                raise ValueError(f"8-bit I,Q prefix must have the dtype of iq ({x.dtype}), got {pre.dtype}")
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} samples before iq, got {pre.shape[0]}")
+        return x, pre
+
+    def _host_ddc(self, sym: str, x: np.ndarray, prefix, word, decim: int, sample0: int, fmt: Optional[int] = None) -> np.ndarray:
         decim, word = _ddc_decim(decim), _ddc_word(word)
         if int(sample0) < 0:
             raise ValueError("sample0 must be >= 0")
         n = int(x.shape[0])
         out = np.empty((n + decim - 1) // decim, dtype=np.complex64)
         n_out = c_size_t(0)
+        samples = [x.ctypes.data_as(c_void_p)] if fmt is None else [x.ctypes.data_as(c_void_p), c_int(fmt)]   # (8-bit: the format)
         with self._lock:
             check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
-                                      x.ctypes.data_as(c_void_p), c_size_t(n), _ffi.c_uint32(word), decim,
+                                      *samples, c_size_t(n), _ffi.c_uint32(word), decim,
                                       _ffi.c_uint64(int(sample0)), out.ctypes.data_as(c_void_p), byref(n_out)))
         return out[: n_out.value]
 
@@ -1346,7 +1359,8 @@ class SpectrumPlan:
         x, pre = self._ddc_input(iq, prefix, True)
         return self._host_ddc("sdrk_exec_host_ddc_ci16", x, pre, freq_word, decim, sample0)
 
-    def _host_ddc_bank(self, sym: str, x: np.ndarray, prefix, freq_words, decim: int, sample0: int) -> np.ndarray:
+    def _host_ddc_bank(self, sym: str, x: np.ndarray, prefix, freq_words, decim: int, sample0: int,
+                       fmt: Optional[int] = None) -> np.ndarray:
         decim, words = _ddc_decim(decim), _ddc_words(freq_words)
         if int(sample0) < 0:
             raise ValueError("sample0 must be >= 0")
@@ -1354,9 +1368,10 @@ class SpectrumPlan:
         stride = (n + decim - 1) // decim
         out = np.empty((len(words), stride), dtype=np.complex64)
         n_out = c_size_t(0)
+        samples = [x.ctypes.data_as(c_void_p)] if fmt is None else [x.ctypes.data_as(c_void_p), c_int(fmt)]   # (8-bit: the format)
         with self._lock:
             check(getattr(lib(), sym)(self.handle, prefix.ctypes.data_as(c_void_p) if prefix is not None else None,
-                                      x.ctypes.data_as(c_void_p), c_size_t(n), len(words), words, decim,
+                                      *samples, c_size_t(n), len(words), words, decim,
                                       _ffi.c_uint64(int(sample0)), out.ctypes.data_as(c_void_p), c_size_t(stride), byref(n_out)))
         return np.ascontiguousarray(out[:, : n_out.value])
 
@@ -1371,6 +1386,19 @@ class SpectrumPlan:
         """``ddc_bank`` on interleaved int16 I,Q of shape ``(n, 2)``: the bits of ``ddc_bank`` on the widened samples."""
         x, pre = self._ddc_input(iq, prefix, True)
         return self._host_ddc_bank("sdrk_exec_host_ddcbank_ci16", x, pre, freq_words, decim, sample0)
+
+    def ddc_ci8(self, iq, freq_word: int, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``ddc`` on interleaved 8-bit I,Q of shape ``(n, 2)``, int8 (SigMF ci8) or uint8 (cu8) — the dtype is the format —
+        read as they are, 2 bytes per sample: the bits of ``ddc`` on ``iq8_to_c64(iq)``.  ``prefix``: ``(M - 1, 2)`` of the same
+        dtype; None means bytes of 0 for int8 and of 128 for uint8 (the mid-scale byte: ``+0.5 + 0.5j``; no uint8 byte is zero)."""
+        x, pre = self._ddc_input_ci8(iq, prefix)
+        return self._host_ddc("sdrk_exec_host_downconv_iq8", x, pre, freq_word, decim, sample0, fmt=_iq8_format(x))
+
+    def ddc_bank_ci8(self, iq, freq_words, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``ddc_bank`` on interleaved 8-bit I,Q of shape ``(n, 2)`` (int8 or uint8, as ``ddc_ci8``): the bits of ``ddc_bank`` on
+        the widened samples."""
+        x, pre = self._ddc_input_ci8(iq, prefix)
+        return self._host_ddc_bank("sdrk_exec_host_downconvbank_iq8", x, pre, freq_words, decim, sample0, fmt=_iq8_format(x))
 
     def ddc_outputs(self, n_in: int, decim: int = 1, index0: int = 0) -> int:
         """Samples ``exec_device_ddc`` writes for ``n_in`` input samples whose first valid output has stream index ``index0``:
@@ -1408,6 +1436,24 @@ class SpectrumPlan:
         check(lib().sdrk_exec_device_ddc_timed_each(*args, int(launches), each))
         return list(each)
 
+    def _device_ddc_ci8_args(self, args: list, unsigned: bool) -> list:
+        """The argument list of a device call with the 8-bit format behind the input pointer."""
+        return [*args[:2], c_int(IQ8_UNSIGNED if unsigned else IQ8_SIGNED), *args[2:]]
+
+    def exec_device_ddc_ci8(self, d_in: int, n_in: int, d_out: int, freq_word: int, *, unsigned: bool = False, decim: int = 1,
+                            index0: int = 0, stream: int = 0) -> None:
+        """``exec_device_ddc`` on 8-bit I,Q input (2 bytes per sample; ``unsigned``: cu8, else ci8)."""
+        args = self._device_ddc_ci8_args(self._device_ddc_args(d_in, n_in, freq_word, decim, index0, d_out), unsigned)
+        check(lib().sdrk_exec_device_downconv_iq8(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_ci8_timed_each(self, d_in: int, n_in: int, d_out: int, freq_word: int, launches: int = 1, *,
+                                       unsigned: bool = False, decim: int = 1, index0: int = 0) -> list:
+        """``exec_device_ddc_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_ddc_ci8_args(self._device_ddc_args(d_in, n_in, freq_word, decim, index0, d_out), unsigned)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_downconv_iq8_timed_each(*args, int(launches), each))
+        return list(each)
+
     def _device_ddc_bank_args(self, d_in: int, n_in: int, d_out: int, freq_words, decim: int, index0: int, out_stride) -> list:
         words = _ddc_words(freq_words)
         n_out = self.ddc_outputs(n_in, decim, index0)
@@ -1437,6 +1483,21 @@ class SpectrumPlan:
         args = self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride)
         each = (c_float * int(launches))()
         check(lib().sdrk_exec_device_ddcbank_timed_each(*args, int(launches), each))
+        return list(each)
+
+    def exec_device_ddc_bank_ci8(self, d_in: int, n_in: int, d_out: int, freq_words, *, unsigned: bool = False, decim: int = 1,
+                                 index0: int = 0, out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """``exec_device_ddc_bank`` on 8-bit I,Q input (2 bytes per sample; ``unsigned``: cu8, else ci8)."""
+        args = self._device_ddc_ci8_args(self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride), unsigned)
+        check(lib().sdrk_exec_device_downconvbank_iq8(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_ddc_bank_ci8_timed_each(self, d_in: int, n_in: int, d_out: int, freq_words, launches: int = 1, *,
+                                            unsigned: bool = False, decim: int = 1, index0: int = 0,
+                                            out_stride: Optional[int] = None) -> list:
+        """``exec_device_ddc_bank_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_ddc_ci8_args(self._device_ddc_bank_args(d_in, n_in, d_out, freq_words, decim, index0, out_stride), unsigned)
+        each = (c_float * int(launches))()
+        check(lib().sdrk_exec_device_downconvbank_iq8_timed_each(*args, int(launches), each))
         return list(each)
 
     def window_power(self) -> float:
@@ -1966,11 +2027,65 @@ def ddc_bank(iq, taps, offsets_hz, sample_rate: float, decim: int = 1, *, device
     return plan.ddc_bank(iq, words, decim=decim)
 
 
+def ddc_ci8(iq, taps, offset_hz: float, sample_rate: float, decim: int = 1, *, device: int = 0) -> np.ndarray:
+    """``ddc`` on interleaved 8-bit I,Q of shape ``(n, 2)``, int8 (SigMF ci8) or uint8 (cu8), read as they are (2 bytes per
+    sample): ``SpectrumPlan.ddc_ci8`` on a cached plan that holds ``taps``; the bits of ``ddc`` on ``iq8_to_c64(iq)`` — for uint8
+    with the stream before ``iq`` taken as bytes of 128 (``+0.5 + 0.5j``), the nearest a cu8 stream comes to silence."""
+    _ddc_decim(decim)
+    word = freq_word(offset_hz, sample_rate)
+    x = _as_ci8(iq, stream=True)
+    return _cached_fir_plan(taps, device).ddc_ci8(x, word, decim=decim)
+
+
+def ddc_bank_ci8(iq, taps, offsets_hz, sample_rate: float, decim: int = 1, *, device: int = 0) -> np.ndarray:
+    """``ddc_bank`` on interleaved 8-bit I,Q of shape ``(n, 2)`` (int8 or uint8, as ``ddc_ci8``): row ``c`` carries the bits of
+    ``ddc_ci8(iq, taps, offsets_hz[c], sample_rate, decim)``."""
+    _ddc_decim(decim)
+    words = [freq_word(f, sample_rate) for f in np.asarray(offsets_hz, dtype=np.float64).reshape(-1)]
+    _ddc_words(words)
+    x = _as_ci8(iq, stream=True)
+    return _cached_fir_plan(taps, device).ddc_bank_ci8(x, words, decim=decim)
+
+
+_NARROW = (np.int16, np.int8, np.uint8)
+
+
+def _stream_piece(who: str, iq, tail) -> np.ndarray:
+    """A piece pushed into a stream as the array its plan call takes: complex64, or int16 / int8 / uint8 ``(n, 2)`` as they
+    are; one kind throughout a stream (``tail``: the samples kept so far, None before the first)."""
+    if isinstance(iq, np.ndarray) and iq.dtype in _NARROW:
+        x = _as_ci16(iq, stream=True) if iq.dtype == np.int16 else _as_ci8(iq, stream=True)
+    else:
+        x = _as_c64(iq).reshape(-1)
+    if tail is not None and tail.dtype != x.dtype:
+        raise ValueError(f"a {who} takes complex, int16, int8 or uint8 pieces, not both: one kind throughout "
+                         f"(so far {tail.dtype}, now {x.dtype})")
+    return x
+
+
+def _stream_tail(tail, x: np.ndarray, keep: int):
+    """The last ``keep`` samples of tail || x.  Before the first piece the tail is silence: zeros, and for uint8 the mid-scale
+    byte 128 (no cu8 byte widens to zero; the C entries take a NULL prefix the same way)."""
+    if not keep:
+        return tail
+    if tail is None:
+        tail = np.zeros(keep, np.complex64) if x.dtype == np.complex64 else np.full((keep, 2), 128 if x.dtype == np.uint8 else 0, x.dtype)
+    return np.ascontiguousarray(np.concatenate((tail, x))[-keep:])
+
+
+def _bin_word(shift_bins: int) -> int:
+    """The frequency word of a whole bin: with a power-of-two decimation and a stream index that is a multiple of it, the DDC call
+    then returns the bits of the FIR call."""
+    return ((int(shift_bins) % FIR_BLOCK) << 20) & 0xFFFFFFFF
+
+
 class ChannelStream:
     """One channel out of a stream that arrives in pieces: tuned to ``offset_hz`` from the centre, low-passed by ``taps``,
     decimated by ``decim``.  The offset is rounded to a whole bin of ``sample_rate/4096`` (``shift_bins``; ``tuned_hz`` is the
-    frequency actually tuned).  ``push(iq)`` takes pieces of any length (complex64, or int16 ``(n, 2)`` throughout) and returns
-    the complex64 output samples they complete; the last ``M - 1`` input samples and the stream index are kept between calls,
+    frequency actually tuned).  ``push(iq)`` takes pieces of any length (complex64, or int16 / int8 / uint8 ``(n, 2)``, one kind
+    throughout; 8-bit pieces are read as they are by the 8-bit down-converter call with the bin's frequency word, which cuts its
+    blocks from the piece's first sample where the FIR call cuts them from the first kept one: the FIR call's bits for a piece
+    that starts on a multiple of ``decim``, its error bound otherwise) and returns the complex64 output samples they complete; the last ``M - 1`` input samples and the stream index are kept between calls,
     so filter and mixer run on as over one stream.  ``plan``: a float32 ``SpectrumPlan(4096)`` to use (its FIR filter is
     replaced), or None for one of the stream's own."""
 
@@ -1991,20 +2106,16 @@ class ChannelStream:
         self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
 
     def push(self, iq) -> np.ndarray:
-        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
-        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
-        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
-            raise ValueError("a ChannelStream takes complex or int16 pieces, not both")
+        x = _stream_piece("ChannelStream", iq, self._tail)
         n = int(x.shape[0])
         if n == 0:
             return np.empty(0, dtype=np.complex64)
-        run = self.plan.fir_ci16 if ci16 else self.plan.fir
-        out = run(x, decim=self.decim, shift_bins=self.shift_bins, prefix=self._tail, sample0=self.sample_index)
-        keep = self.ntaps - 1
-        if keep:
-            if self._tail is None:
-                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
-            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+        if x.dtype.itemsize == 1:
+            out = self.plan.ddc_ci8(x, _bin_word(self.shift_bins), decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        else:
+            run = self.plan.fir_ci16 if x.dtype == np.int16 else self.plan.fir
+            out = run(x, decim=self.decim, shift_bins=self.shift_bins, prefix=self._tail, sample0=self.sample_index)
+        self._tail = _stream_tail(self._tail, x, self.ntaps - 1)
         self.sample_index += n
         return out
 
@@ -2043,20 +2154,17 @@ class ChannelBankStream:
         self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
 
     def push(self, iq) -> np.ndarray:
-        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
-        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
-        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
-            raise ValueError("a ChannelBankStream takes complex or int16 pieces, not both")
+        x = _stream_piece("ChannelBankStream", iq, self._tail)
         n = int(x.shape[0])
         if n == 0:
             return np.empty((len(self.shift_bins), 0), dtype=np.complex64)
-        run = self.plan.fir_bank_ci16 if ci16 else self.plan.fir_bank
-        out = run(x, self.shift_bins, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
-        keep = self.ntaps - 1
-        if keep:
-            if self._tail is None:
-                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
-            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+        if x.dtype.itemsize == 1:                          # (8-bit pieces: the down-converter call with the bins' words)
+            out = self.plan.ddc_bank_ci8(x, [_bin_word(s) for s in self.shift_bins], decim=self.decim, prefix=self._tail,
+                                         sample0=self.sample_index)
+        else:
+            run = self.plan.fir_bank_ci16 if x.dtype == np.int16 else self.plan.fir_bank
+            out = run(x, self.shift_bins, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._tail = _stream_tail(self._tail, x, self.ntaps - 1)
         self.sample_index += n
         return out
 
@@ -2086,19 +2194,16 @@ class _DdcStreamBase:
         self.sample_index = 0                              # stream index of the next input sample
         self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
 
-    def _piece(self, iq):
-        ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
-        x = _as_ci16(iq, stream=True) if ci16 else _as_c64(iq).reshape(-1)
-        if self._tail is not None and (self._tail.dtype == np.int16) != ci16:
-            raise ValueError(f"a {type(self).__name__} takes complex or int16 pieces, not both")
-        return x, ci16
+    def _piece(self, iq) -> np.ndarray:
+        return _stream_piece(type(self).__name__, iq, self._tail)
 
-    def _advance(self, x, ci16: bool) -> None:
-        keep = self.ntaps - 1
-        if keep:
-            if self._tail is None:
-                self._tail = np.zeros((keep, 2), np.int16) if ci16 else np.zeros(keep, np.complex64)
-            self._tail = np.ascontiguousarray(np.concatenate((self._tail, x))[-keep:])
+    def _run(self, x: np.ndarray, bank: bool):
+        """The plan call of a piece's kind."""
+        kind = "" if x.dtype == np.complex64 else "_ci16" if x.dtype == np.int16 else "_ci8"
+        return getattr(self.plan, ("ddc_bank" if bank else "ddc") + kind)
+
+    def _advance(self, x: np.ndarray) -> None:
+        self._tail = _stream_tail(self._tail, x, self.ntaps - 1)
         self.sample_index += int(x.shape[0])
 
     def close(self) -> None:
@@ -2115,7 +2220,8 @@ class _DdcStreamBase:
 class DdcStream(_DdcStreamBase):
     """``ChannelStream`` as a digital down-converter: tuned to ``offset_hz`` to the nearest 32-bit frequency word (``freq_word``;
     ``tuned_hz`` is that word's frequency, within ``sample_rate / 2^33`` of the request) and decimated by ANY integer ``decim``
-    in 1..256.  ``push(iq)`` takes pieces of any length (complex64, or int16 ``(n, 2)`` throughout) and returns the output
+    in 1..256.  ``push(iq)`` takes pieces of any length (complex64, or int16 / int8 / uint8 ``(n, 2)``, one kind throughout;
+    8-bit pieces are read as they are, and a uint8 stream starts from M - 1 pairs of byte 128) and returns the output
     samples whose stream index is a multiple of ``decim`` — however many fall into the piece, none included."""
 
     def __init__(self, plan, taps, decim: int, offset_hz: float, sample_rate: float, *, device: int = 0):
@@ -2125,12 +2231,11 @@ class DdcStream(_DdcStreamBase):
         self.tuned_hz = freq_word_hz(word, self.sample_rate)
 
     def push(self, iq) -> np.ndarray:
-        x, ci16 = self._piece(iq)
+        x = self._piece(iq)
         if x.shape[0] == 0:
             return np.empty(0, dtype=np.complex64)
-        run = self.plan.ddc_ci16 if ci16 else self.plan.ddc
-        out = run(x, self.freq_word, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
-        self._advance(x, ci16)
+        out = self._run(x, False)(x, self.freq_word, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._advance(x)
         return out
 
 
@@ -2148,10 +2253,9 @@ class DdcBankStream(_DdcStreamBase):
         self.tuned_hz = [freq_word_hz(w, self.sample_rate) for w in words]
 
     def push(self, iq) -> np.ndarray:
-        x, ci16 = self._piece(iq)
+        x = self._piece(iq)
         if x.shape[0] == 0:
             return np.empty((len(self.freq_words), 0), dtype=np.complex64)
-        run = self.plan.ddc_bank_ci16 if ci16 else self.plan.ddc_bank
-        out = run(x, self.freq_words, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
-        self._advance(x, ci16)
+        out = self._run(x, True)(x, self.freq_words, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._advance(x)
         return out

@@ -27,6 +27,8 @@ from .spectrum import (  # noqa: E402
     cross_spectrum,
     ddc,
     ddc_bank,
+    ddc_bank_ci8,
+    ddc_ci8,
     ddc_taps,
     fft_c64,
     fft_c128,
@@ -78,6 +80,8 @@ __all__ = [
     "cross_spectrum",
     "ddc",
     "ddc_bank",
+    "ddc_bank_ci8",
+    "ddc_ci8",
     "ddc_taps",
     "device_count",
     "device_info",
