@@ -27,11 +27,31 @@
 // The kernel is persistent (grid-stride over frames) and software-pipelined:
 // the next frame's 16 loads per thread are in flight while the current frame is
 // transformed, so each resident workgroup keeps 32 KiB of HBM reads outstanding.
+// fft4096_ticket_kernel is the same frame body under another order of the frames: a workgroup takes its next frame
+// from a counter in device memory (f4k_ticket.h) instead of stepping by the grid.
 #include "fft4096_core.h"
 
 namespace sdrk {
 
-// fft4096_ci16_kernel (fft4096_ci16.hip) is this function with another input policy: a change here is made there too.
+#ifdef SDRK_F4K_TIMELINE
+// Experiment build only (experiments/f4k_order): one 16-byte record per frame — the shared real-time counter (100 MHz) when
+// the frame's loads were issued, the frame, the workgroup — into the buffer sdrk_f4k_timeline() names, if it names one.
+__device__ uint4* f4k_timeline_buf = nullptr;
+#define F4K_TIMELINE_LOAD() uint4* const f4k_tl = f4k_timeline_buf
+#define F4K_TIMELINE_MARK(fr)                                                                                   \
+    do {                                                                                                        \
+        if (f4k_tl && tid == 0 && (fr) < n_frames) {                                                            \
+            const unsigned long long f4k_t = wall_clock64();                                                    \
+            f4k_tl[fr] = make_uint4((unsigned)f4k_t, (unsigned)(f4k_t >> 32), (unsigned)(fr), blockIdx.x);      \
+        }                                                                                                       \
+    } while (0)
+#else
+#define F4K_TIMELINE_LOAD() (void)0
+#define F4K_TIMELINE_MARK(fr) (void)0
+#endif
+
+// fft4096_ci16_kernel (fft4096_ci16.hip) and the ci8 kernel are this function with another input policy: a change here is made
+// there too — except the ticket order of fft4096_ticket_kernel below, which only the complex64 input has so far.
 //
 // (Tried and dropped, A/B on the same buffers: two frames prefetched (2 % slower, again in round 5 at 140 VGPRs), a sqrt-free
 // log epilogue (1.5 % slower), and sending the row through LDS once more so that it leaves as four 16-byte stores
@@ -66,11 +86,13 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kernel(
 
     const size_t first = blockIdx.x;
     const size_t step = gridDim.x;
+    F4K_TIMELINE_LOAD();
 
     // Software pipeline: each workgroup keeps the loads of its next frame in flight while it transforms the
     // current one.  (Two frames ahead — 64 KiB per workgroup in flight — measured 2.5 % slower against the
     // same-buffers copy: 1.055x instead of 1.030x its time.)
     auto issue = [&](In::word (&x)[16], size_t fr) {
+        F4K_TIMELINE_MARK(fr);
         if (fr >= n_frames) fr = first;  // harmless re-read past the end
         In::issue(x, iq + fr * frame_stride, tid);
     };
@@ -89,6 +111,95 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kernel(
     for (size_t f = first; f < n_frames; f += step) process(nxt, f);
 }
 
+// The same frames in ticket order (f4k_ticket.h): workgroup b draws from head b % heads, and a ticket is `frames` consecutive
+// frames.  One lane draws: f4k_ticket_depth tickets with the first atomic, before the prologue's barrier, and one more at the
+// top of every iteration whose prefetch reaches the last frame of a ticket, ahead of that iteration's prefetch loads, so that
+// the wait for those loads at the top of the next iteration has covered it.  At the next such iteration the lane puts the value
+// into one of two LDS slots (alternating: a wave that is through the frame's last barrier may write the next slot while another
+// still reads this one); every wave reads it behind the transform's four barriers and makes it wave-uniform.  A ticket is thus
+// drawn some iterations before its first frame is prefetched, nothing waits or polls for it, and the frame body has no barrier
+// more than the grid-stride form.  A workgroup leaves at its first frame at or past the end; the draws that remain in flight
+// are part of what the host expects of the heads.
+template <bool HAS_WINDOW, int EPILOGUE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ticket_kernel(
+    const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift, unsigned* __restrict__ heads, const sdrk_host::F4kTicketBases bases,
+    const sdrk_host::F4kTicketForm form) {
+    typedef F4kInC64 In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    __shared__ unsigned ticket_slot[2];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    const unsigned hx = blockIdx.x & (form.heads - 1);
+    const unsigned depth = sdrk_host::f4k_ticket_depth(form);
+    // (+ the lane: 0 in the one lane that draws.  An address the compiler takes for wave-uniform makes it rewrite the atomic as
+    // "one elected lane adds, then everybody reads the first lane", which waits for the returned value where it is issued.)
+    unsigned* const head = heads + hx * sdrk_host::F4K_TICKET_HEAD_WORDS + __lane_id();
+    const unsigned base = bases.base[hx];
+    unsigned drawn = 0;   // lane 0: the head's value at the youngest ticket this workgroup holds
+    if (tid == 0) drawn = __hip_atomic_fetch_add(head, depth, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    if (tid == 0) {
+        ticket_slot[0] = drawn;
+        drawn += depth - 1;
+    }
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+    F4K_TIMELINE_LOAD();
+
+    auto first_of = [&](unsigned head_value) { return sdrk_host::f4k_ticket_first_frame(form, head_value - base, hx); };
+    const unsigned h0 = __builtin_amdgcn_readfirstlane(ticket_slot[0]);
+    const size_t in_ticket = form.frames - 1;
+    // cur: the frame to transform, its loads in flight; nx: the frame to prefetch; tn: the first frame of the ticket behind nx's
+    size_t cur = first_of(h0), nx = in_ticket ? cur + 1 : first_of(h0 + 1), tn = first_of(h0 + depth - 2);
+    unsigned par = 1;
+
+    auto issue = [&](In::word (&x)[16], size_t fr) {
+        F4K_TIMELINE_MARK(fr);
+        if (fr >= n_frames) fr = 0;  // harmless re-read past the end
+        In::issue(x, iq + fr * frame_stride, tid);
+    };
+    In::word nxt[16];
+    issue(nxt, cur);
+    while (cur < n_frames) {
+        const bool last_of_ticket = ((nx + 1) & in_ticket) == 0;   // the prefetch reaches the end of a ticket: tn is next, and a draw
+        if (last_of_ticket && tid == 0) {
+            ticket_slot[par] = drawn;
+            drawn = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        In::to_owners(nxt, lds, tid);
+        cf v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = In::widen(nxt[j]);
+        issue(nxt, nx);
+        f4k_windowed_transform<HAS_WINDOW>(v, lds, tw256, tw1, lds_win, A, tid);
+        size_t after = nx + 1;
+        if (last_of_ticket) {
+            after = tn;
+            tn = first_of(__builtin_amdgcn_readfirstlane(ticket_slot[par]));
+            par ^= 1;
+        }
+        f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + cur * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                voff_out, xor_k2, eps);
+        cur = nx;
+        nx = after;
+    }
+}
+
+unsigned f4k_max_blocks(int num_cus) { return f4k_grid(num_cus, F4K_WAVES, (size_t)-1); }
+
 hipError_t launch_fft4096(const LaunchArgs& a) {
     if (a.n_frames == 0) return hipSuccess;
     dim3 g(f4k_grid(a.num_cus, F4K_WAVES, a.n_frames)), b(F4K_THREADS);
@@ -106,4 +217,31 @@ hipError_t launch_fft4096(const LaunchArgs& a) {
     return hipGetLastError();
 }
 
+hipError_t launch_fft4096_ticket(const LaunchArgs& a, unsigned* d_heads, const sdrk_host::F4kTicketBases& bases,
+                                 sdrk_host::F4kTicketForm form, unsigned grid) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (!d_heads || grid == 0 || grid % sdrk_host::F4K_TICKET_MAX_HEADS || !sdrk_host::f4k_ticket_form_ok(form)) return hipErrorInvalidValue;
+    dim3 g(grid), b(F4K_THREADS);
+    const float2* iq = static_cast<const float2*>(a.d_iq);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(W, E)                                                                            \
+    hipLaunchKernelGGL((fft4096_ticket_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,    \
+                       a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, bases, form)
+    if (a.epilogue == EPI_LOGPSD) {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
+    } else {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_COMPLEX); else SDRK_LAUNCH(false, EPI_COMPLEX);
+    }
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
 }  // namespace sdrk
+
+#ifdef SDRK_F4K_TIMELINE
+// Experiment build only: the device buffer (one uint4 per frame of the launches to come) the time line goes to; NULL ends it.
+extern "C" int sdrk_f4k_timeline(void* d_records) {
+    uint4* p = static_cast<uint4*>(d_records);
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(sdrk::f4k_timeline_buf), &p, sizeof p);
+}
+#endif

@@ -7,6 +7,8 @@
 
 #include <atomic>
 
+#include "f4k_ticket.h"
+
 // SDRK_PHASE("name"): a comment in the generated assembly that tools/phase_budget.py cuts a kernel's instruction stream at
 // (builds with -DSDRK_PHASE_MARKS only: the memory clobber would otherwise fence the scheduler in the shipped code)
 #ifdef SDRK_PHASE_MARKS
@@ -101,6 +103,11 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, size_t lds_bytes, std::
 }
 
 hipError_t launch_fft4096(const LaunchArgs& a);
+// The same transform with the frames dealt by ticket (f4k_ticket.h): d_heads = the plan's heads, bases = where they stand,
+// grid = f4k_ticket_grid(f4k_max_blocks(num_cus), n_frames).  The caller advances its bases and keeps such launches apart.
+unsigned f4k_max_blocks(int num_cus);   // workgroups of a full fft4096 grid
+hipError_t launch_fft4096_ticket(const LaunchArgs& a, unsigned* d_heads, const sdrk_host::F4kTicketBases& bases,
+                                 sdrk_host::F4kTicketForm form, unsigned grid);
 hipError_t launch_fft_small(const LaunchArgs& a);   // 2 <= nfft <= 2048: Stockham radix-2 in LDS (N = 2, 4, 8 and far-apart frames)
 bool fft_lds_supports(int nfft);                     // 16 .. 16384 except 4096: registers + LDS, one pass over HBM
 hipError_t launch_fft_lds(const LaunchArgs& a);

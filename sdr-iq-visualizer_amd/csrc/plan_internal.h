@@ -134,6 +134,18 @@ struct sdrk_plan {
     float2* d_fir_h = nullptr;
     int fir_taps = 0;
     int fir_assign = 0;
+    // N = 4096, frames dealt by ticket (f4k_ticket.h, fft4096_ticket_kernel): f4k_order = SDRK_F4K_ORDER at creation;
+    // d_f4k_heads = the eight heads, never reset; f4k_bases = where they stand behind every launch enqueued so far.  Two
+    // ticketed launches of a plan must not overlap: f4k_ev follows the last one (on f4k_last), and a call on another stream
+    // waits for it.  f4k_parts: SDRK_F4K_PARTS, launches per call in either order (developer use; 0: f4k_ticket_parts / f4k_split_parts).
+    int f4k_order = sdrk_host::F4K_ORDER_AUTO;
+    sdrk_host::F4kTicketForm f4k_form = sdrk_host::F4K_TICKET_FORM;   // SDRK_F4K_TICKET_FORM (A/B work)
+    unsigned* d_f4k_heads = nullptr;
+    sdrk_host::F4kTicketBases f4k_bases = {};
+    hipEvent_t f4k_ev = nullptr;
+    hipStream_t f4k_last = nullptr;
+    bool f4k_recorded = false;
+    size_t f4k_parts = 0;
 };
 
 namespace sdrk_host {

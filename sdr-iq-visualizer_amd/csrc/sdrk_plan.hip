@@ -180,14 +180,31 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
     } else if (p->nfft == 4096) {
         // A long call goes out as back-to-back launches of about F4K_SPLIT_FRAMES frames each (see there): the frames are
         // independent, so the rows are the same bits whichever launch computes them.
-        const size_t parts = f4k_split_parts(n_frames);
+        // In the ticket order (f4k_ticket.h) the launches draw from the plan's heads, one launch after the other: a call on
+        // another stream than the last one waits for it, and the host's bases move with every launch enqueued.
+        const size_t max_blocks = sdrk::f4k_max_blocks(p->num_cus);
+        const bool ticket = p->d_f4k_heads && f4k_ticket_takes(p->f4k_order, max_blocks, n_frames, F4K_TICKET_DEFAULT);
+        size_t parts = p->f4k_parts ? p->f4k_parts : (ticket ? f4k_ticket_parts(n_frames) : f4k_split_parts(n_frames));
+        if (p->f4k_parts && parts > n_frames) parts = n_frames ? n_frames : 1;
         const size_t per = (n_frames + parts - 1) / parts;
         const size_t out_elem = epilogue == sdrk::EPI_LOGPSD ? sizeof(float) : sizeof(float2);
+        if (ticket && p->f4k_recorded && p->f4k_last != stream) e = hipStreamWaitEvent(stream, p->f4k_ev, 0);
         for (size_t f0 = 0; f0 < n_frames && e == hipSuccess; f0 += per) {
             a.d_iq = static_cast<const float2*>(d_iq) + f0 * frame_stride;
             a.d_out = static_cast<char*>(d_out) + f0 * (size_t)4096 * out_elem;
             a.n_frames = n_frames - f0 < per ? n_frames - f0 : per;
-            e = sdrk::launch_fft4096(a);
+            if (ticket) {
+                const unsigned grid = f4k_ticket_grid(max_blocks, a.n_frames);
+                e = sdrk::launch_fft4096_ticket(a, p->d_f4k_heads, p->f4k_bases, p->f4k_form, grid);
+                if (e == hipSuccess) f4k_ticket_advance(p->f4k_form, p->f4k_bases, a.n_frames, grid);
+            } else {
+                e = sdrk::launch_fft4096(a);
+            }
+        }
+        if (ticket && e == hipSuccess) {
+            e = hipEventRecord(p->f4k_ev, stream);
+            p->f4k_last = stream;
+            p->f4k_recorded = true;
         }
     } else if (sdrk::fft_lds_supports(p->nfft))
         e = sdrk::launch_fft_lds(a);
@@ -401,6 +418,25 @@ int sdrk_plan_create_ex(int device, int nfft, size_t max_batch, int window_kind,
         for (int m = 0; m < nfft; ++m) t[m] = twiddle(m, nfft);
         PLAN_TRY(hipMalloc((void**)&p->d_twiddle, sizeof(float2) * nfft));
         PLAN_TRY(hipMemcpy(p->d_twiddle, t.data(), sizeof(float2) * nfft, hipMemcpyHostToDevice));
+        if (nfft == 4096) {
+            // The heads of the ticket order, one 128-byte line each.  They start a few hundred tickets short of the 32-bit
+            // wrap: every plan that lives for more than a launch or two crosses it, so the wrap is no rare path.
+            if (const char* env = getenv("SDRK_F4K_ORDER"))   // "stride" / "ticket": either loop at any size (f4k_ticket_takes)
+                p->f4k_order = env[0] == 't' ? F4K_ORDER_TICKET : (env[0] == 's' ? F4K_ORDER_STRIDE : F4K_ORDER_AUTO);
+            if (const char* env = getenv("SDRK_F4K_PARTS")) {   // launches per call, either order: developer use (tools/f4k_ticket_launches.py)
+                long v = atol(env);
+                if (v >= 1 && v <= 4096) p->f4k_parts = (size_t)v;
+            }
+            if (const char* env = getenv("SDRK_F4K_TICKET_FORM")) {   // "<heads>x<frames per ticket>": A/B work
+                F4kTicketForm f = {0, 0};
+                if (sscanf(env, "%ux%u", &f.heads, &f.frames) == 2 && f4k_ticket_form_ok(f)) p->f4k_form = f;
+            }
+            std::vector<uint32_t> h(F4K_TICKET_MAX_HEADS * F4K_TICKET_HEAD_WORDS, 0u);
+            for (unsigned x = 0; x < F4K_TICKET_MAX_HEADS; ++x) h[x * F4K_TICKET_HEAD_WORDS] = p->f4k_bases.base[x] = 0xFFFFFE00u;
+            PLAN_TRY(hipMalloc((void**)&p->d_f4k_heads, h.size() * sizeof(uint32_t)));
+            PLAN_TRY(hipMemcpy(p->d_f4k_heads, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            PLAN_TRY(hipEventCreateWithFlags(&p->f4k_ev, hipEventDisableTiming));
+        }
     } else {
         // scratch between the two passes: up to 192 MiB of complex64 frames.  It has to stay in the 256 MiB
         // Infinity Cache between the col pass that writes it and the row pass that reads it, and per-launch
@@ -523,6 +559,9 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_pfb_h) (void)hipFree(p->d_pfb_h);
     p->pfb.release();
     if (p->d_fir_h) (void)hipFree(p->d_fir_h);
+    if (p->f4k_recorded) (void)hipEventSynchronize(p->f4k_ev);   // a ticketed launch on a caller's stream still draws from the heads
+    if (p->d_f4k_heads) (void)hipFree(p->d_f4k_heads);
+    if (p->f4k_ev) (void)hipEventDestroy(p->f4k_ev);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);
     for (auto& sl : p->slot) {
