@@ -66,6 +66,8 @@ def main():
     ap.add_argument("--frames", type=int, default=1 << 20)
     ap.add_argument("--short", type=int, default=65536)
     ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--orders", default="stride,ticket",
+                    help="comma-separated SDRK_F4K_ORDER values, each optionally with :<SDRK_F4K_TICKET_FORM> (ticket:rot4)")
     a = ap.parse_args()
     lib = _ffi.lib()
     _ffi.require_device(0)
@@ -83,8 +85,12 @@ def main():
     tl = torch.zeros((a.frames, 4), dtype=torch.int32, device="cuda")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as out:
-        for order in ("stride", "ticket"):
-            os.environ["SDRK_F4K_ORDER"] = order
+        for order in [o for o in a.orders.split(",") if o]:
+            os.environ["SDRK_F4K_ORDER"] = order.split(":")[0]
+            if ":" in order:
+                os.environ["SDRK_F4K_TICKET_FORM"] = order.split(":")[1]
+            else:
+                os.environ.pop("SDRK_F4K_TICKET_FORM", None)
             with SpectrumPlan(NFFT, window="hann", device=0) as plan:
                 warm_up_by_time(lambda: plan.exec_device_timed(d_in.value, a.frames, outs[0].value, 1))
                 for i, p in enumerate(outs):

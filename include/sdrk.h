@@ -745,6 +745,8 @@ int sdrk_exec_host_downconvbank_iq8(sdrk_plan* plan, const void* prefix_iq8, con
  * sdrk_copy_probe: a plain 1:1 copy of `bytes` (16 bytes per lane each way, non-temporal) from d_in to
  *   d_out, timed per launch — the shape MI355X_MICROARCH.md quotes 6.29 TB/s for; run on the same buffers it
  *   anchors the 2:1 probe above to a published figure (fastest of three grid sizes).  Bandwidth = 2 * bytes / time.
+ *   Both probes deal their frames (the copy: 16 KiB units) to the workgroups in the order an N = 4096 plan created
+ *   at that moment would take for a full grid (by ticket; SDRK_F4K_ORDER=stride keeps their grid-stride loops).
  * sdrk_host_link_probe: pinned-memory DMA rates in GB/s — `bytes` host-to-device, bytes/2
  *   device-to-host, and both at once (quoted on the upstream bytes): what the numpy
  *   boundary could reach at best.

@@ -5,6 +5,7 @@
 // (self.sdr.rx() on a PlutoSDR: 12-bit ADC codes on I and Q), generated from an
 // integer hash so that the numpy mirror in the host package (synth.py) produces
 // the same float32 bits with no device round trip.
+#include "f4k_deal.h"
 #include "kernels.h"
 #include "synth_hash.h"
 
@@ -190,6 +191,106 @@ hipError_t launch_copy_1to1(const void* d_in, void* d_out, size_t bytes, int num
     hipLaunchKernelGGL(copy_1to1_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const v4f*>(d_in),
                        static_cast<v4f*>(d_out), n_vec);
     return hipGetLastError();
+}
+
+// The two probes with their frames dealt as the flagship kernel's are (f4k_deal.h): the same bytes per frame by the same
+// instructions, one barrier per frame for the dealer's slot.  A grid-stride probe under a ticketed kernel is no ceiling: its
+// workgroups drift apart as the kernel's did (profiles/f4k_ticket/SUMMARY.md §0).  The copy's "frame" is the 1024 vectors a
+// workgroup moves per turn.
+template <class Deal>
+__global__ __launch_bounds__(256) void stream_mix_dealt_kernel(const v4f* __restrict__ in, v4f* __restrict__ out, size_t n_frames,
+                                                               const sdrk_host::F4kDealArgs da) {
+    __shared__ unsigned deal_slot[F4K_DEAL_SLOTS];
+    const int tid = threadIdx.x;
+    Deal deal = Deal::make(da, n_frames, deal_slot, tid);
+    deal.publish(tid);
+    __syncthreads();
+    deal.begin();
+    while (deal.more()) {
+        deal.top(tid);
+        const size_t f = deal.frame();
+        if (f < n_frames) {
+            const v4f* x = in + f * 2048;
+            v4f* o = out + f * 1024;
+            v4f v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = __builtin_nontemporal_load(&x[tid + 256 * j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[2 * j] + v[2 * j + 1], &o[tid + 256 * j]);
+        }
+        __syncthreads();
+        deal.step();
+    }
+    deal.leave(tid);
+}
+
+template <class Deal>
+__global__ __launch_bounds__(256) void copy_1to1_dealt_kernel(const v4f* __restrict__ in, v4f* __restrict__ out, size_t n_vec,
+                                                              const sdrk_host::F4kDealArgs da) {
+    __shared__ unsigned deal_slot[F4K_DEAL_SLOTS];
+    const int tid = threadIdx.x;
+    const size_t n_units = (n_vec + 1023) / 1024;
+    Deal deal = Deal::make(da, n_units, deal_slot, tid);
+    deal.publish(tid);
+    __syncthreads();
+    deal.begin();
+    while (deal.more()) {
+        deal.top(tid);
+        const size_t u = deal.frame();
+        if (u < n_units) {
+            const size_t i = u * 1024 + tid;
+            v4f v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (i + 256 * j < n_vec) v[j] = __builtin_nontemporal_load(&in[i + 256 * j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (i + 256 * j < n_vec) __builtin_nontemporal_store(v[j], &out[i + 256 * j]);
+        }
+        __syncthreads();
+        deal.step();
+    }
+    deal.leave(tid);
+}
+
+// One dealt launch of `n_units` units on a grid of at most `max_blocks`, or hipErrorNotSupported where the probe's choice
+// leaves the grid-stride loop in place (f4k_ticket_takes); the host's bases follow the launch.
+template <class Launch>
+static hipError_t launch_dealt(sdrk_host::F4kProbeDeal& pd, size_t max_blocks, size_t n_units, Launch&& launch) {
+    using namespace sdrk_host;
+    if (!pd.d_heads || !f4k_ticket_takes(pd.choice.order, max_blocks, n_units, F4K_TICKET_DEFAULT)) return hipErrorNotSupported;
+    const unsigned grid = f4k_ticket_grid(max_blocks, n_units);
+    const F4kDealArgs da = {pd.d_heads, pd.bases, pd.choice.form, pd.choice.rot_heads};
+    launch(grid, da, pd.choice.rot_heads != 0);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess && !pd.choice.rot_heads) f4k_ticket_advance(pd.choice.form, pd.bases, n_units, grid);
+    return e;
+}
+
+hipError_t launch_stream_mix_dealt(const void* d_in, void* d_out, size_t n_frames4096, int num_cus, hipStream_t stream,
+                                   sdrk_host::F4kProbeDeal& pd) {
+    if (n_frames4096 == 0) return hipSuccess;
+    const v4f* in = static_cast<const v4f*>(d_in);
+    v4f* out = static_cast<v4f*>(d_out);
+    const hipError_t e = launch_dealt(pd, (size_t)num_cus * 3, n_frames4096, [&](unsigned grid, const sdrk_host::F4kDealArgs& da, bool rot) {
+        if (rot) hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
+        else hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kTicketDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
+    });
+    return e == hipErrorNotSupported ? launch_stream_mix(d_in, d_out, n_frames4096, num_cus, stream) : e;
+}
+
+hipError_t launch_copy_1to1_dealt(const void* d_in, void* d_out, size_t bytes, int num_cus, int blocks_per_cu, hipStream_t stream,
+                                  sdrk_host::F4kProbeDeal& pd) {
+    const size_t n_vec = bytes / 16;
+    if (n_vec == 0) return hipSuccess;
+    const v4f* in = static_cast<const v4f*>(d_in);
+    v4f* out = static_cast<v4f*>(d_out);
+    const hipError_t e = launch_dealt(pd, (size_t)num_cus * blocks_per_cu, (n_vec + 1023) / 1024,
+                                      [&](unsigned grid, const sdrk_host::F4kDealArgs& da, bool rot) {
+        if (rot) hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
+        else hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kTicketDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
+    });
+    return e == hipErrorNotSupported ? launch_copy_1to1(d_in, d_out, bytes, num_cus, blocks_per_cu, stream) : e;
 }
 
 hipError_t launch_power_mean(const void* d_spec, size_t n_frames, int nfft, float scale, float* d_out,

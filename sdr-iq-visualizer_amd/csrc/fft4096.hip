@@ -28,7 +28,9 @@
 // the next frame's 16 loads per thread are in flight while the current frame is
 // transformed, so each resident workgroup keeps 32 KiB of HBM reads outstanding.
 // fft4096_ticket_kernel is the same frame body under another order of the frames: a workgroup takes its next frame
-// from a counter in device memory (f4k_ticket.h) instead of stepping by the grid.
+// from a counter in device memory (f4k_ticket.h) instead of stepping by the grid; fft4096_rot_kernel, what a full grid runs,
+// takes one frame per ticket from several such counters in rotation (f4k_rot.h).
+#include "f4k_deal.h"
 #include "fft4096_core.h"
 
 namespace sdrk {
@@ -198,6 +200,70 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_ticket_kernel(
     }
 }
 
+// The same frames in the "rot H" order (f4k_rot.h, dealt by F4kRotDeal of f4k_deal.h): one frame per ticket, `n_heads` heads
+// that start at zero, and the workgroup's draws go round the heads.  Lane 0 draws three tickets in the prologue and one more
+// at the top of every iteration, ahead of that iteration's prefetch loads; at the top of the next iteration the ticket is in
+// its register, goes into an LDS slot as a frame number and is read by every wave behind that iteration's barriers: three
+// tickets ahead of the frame transformed, and nothing waits or polls.  A frame at or past the end is skipped (one barrier in
+// place of the transform's, for the slot), F4K_ROT_NONE ends the loop, and the last workgroup out zeroes the heads.
+template <bool HAS_WINDOW, int EPILOGUE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_rot_kernel(
+    const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift, unsigned* __restrict__ heads, const unsigned n_heads) {
+    typedef F4kInC64 In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    __shared__ unsigned deal_slot[F4K_DEAL_SLOTS];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kRotDeal deal(heads, n_heads, n_frames, deal_slot, tid);
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    deal.publish(tid);
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+    F4K_TIMELINE_LOAD();
+
+    auto issue = [&](In::word (&x)[16], size_t fr) {
+        F4K_TIMELINE_MARK(fr);
+        if (fr >= n_frames) fr = 0;  // harmless re-read past the end
+        In::issue(x, iq + fr * frame_stride, tid);
+    };
+    In::word nxt[16];
+    deal.begin();
+    issue(nxt, deal.frame());   // the frame to transform has its loads in flight; deal.next() is the frame to prefetch
+    while (deal.more()) {
+        deal.top(tid);
+        const size_t cur = deal.frame();
+        if (cur < n_frames) {
+            In::to_owners(nxt, lds, tid);
+            cf v[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = In::widen(nxt[j]);
+            issue(nxt, deal.next());
+            f4k_windowed_transform<HAS_WINDOW>(v, lds, tw256, tw1, lds_win, A, tid);
+            deal.step();
+            f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + cur * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                    voff_out, xor_k2, eps);
+        } else {
+            issue(nxt, deal.next());
+            __syncthreads();
+            deal.step();
+        }
+    }
+    deal.leave(tid);
+}
+
 unsigned f4k_max_blocks(int num_cus) { return f4k_grid(num_cus, F4K_WAVES, (size_t)-1); }
 
 hipError_t launch_fft4096(const LaunchArgs& a) {
@@ -227,6 +293,26 @@ hipError_t launch_fft4096_ticket(const LaunchArgs& a, unsigned* d_heads, const s
 #define SDRK_LAUNCH(W, E)                                                                            \
     hipLaunchKernelGGL((fft4096_ticket_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,    \
                        a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, bases, form)
+    if (a.epilogue == EPI_LOGPSD) {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
+    } else {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_COMPLEX); else SDRK_LAUNCH(false, EPI_COMPLEX);
+    }
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_fft4096_rot(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (!d_heads || grid == 0 || grid % sdrk_host::F4K_TICKET_MAX_HEADS || !sdrk_host::f4k_rot_heads_ok(n_heads) ||
+        a.n_frames > sdrk_host::F4K_TICKET_MAX_FRAMES)
+        return hipErrorInvalidValue;
+    dim3 g(grid), b(F4K_THREADS);
+    const float2* iq = static_cast<const float2*>(a.d_iq);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(W, E)                                                                            \
+    hipLaunchKernelGGL((fft4096_rot_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,       \
+                       a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, n_heads)
     if (a.epilogue == EPI_LOGPSD) {
         if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
     } else {

@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "f4k_ticket.h"
+#include "f4k_rot.h"
 
 // SDRK_PHASE("name"): a comment in the generated assembly that tools/phase_budget.py cuts a kernel's instruction stream at
 // (builds with -DSDRK_PHASE_MARKS only: the memory clobber would otherwise fence the scheduler in the shipped code)
@@ -108,6 +109,9 @@ hipError_t launch_fft4096(const LaunchArgs& a);
 unsigned f4k_max_blocks(int num_cus);   // workgroups of a full fft4096 grid
 hipError_t launch_fft4096_ticket(const LaunchArgs& a, unsigned* d_heads, const sdrk_host::F4kTicketBases& bases,
                                  sdrk_host::F4kTicketForm form, unsigned grid);
+// ... and in the "rot H" order (f4k_rot.h): d_heads = F4K_ROT_WORDS words that every launch finds and leaves zero, n_heads = 2,
+// 4 or 8, the same grid.  No bases; the caller keeps launches on the same heads apart.
+hipError_t launch_fft4096_rot(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid);
 hipError_t launch_fft_small(const LaunchArgs& a);   // 2 <= nfft <= 2048: Stockham radix-2 in LDS (N = 2, 4, 8 and far-apart frames)
 bool fft_lds_supports(int nfft);                     // 16 .. 16384 except 4096: registers + LDS, one pass over HBM
 hipError_t launch_fft_lds(const LaunchArgs& a);
@@ -154,6 +158,12 @@ hipError_t launch_decimate_mip(const float* d_mip_ring, int nfft, int maxlen, in
                                float* d_out, hipStream_t stream);
 hipError_t launch_stream_mix(const void* d_in, void* d_out, size_t n_frames4096, int num_cus, hipStream_t stream);
 hipError_t launch_copy_1to1(const void* d_in, void* d_out, size_t bytes, int num_cus, int blocks_per_cu, hipStream_t stream);
+// The same two with their frames dealt in the order `pd` names (f4k_rot.h: F4kProbeDeal) where its choice takes a ticketed grid,
+// and as above elsewhere.  Launches on one F4kProbeDeal must not overlap on the device.
+hipError_t launch_stream_mix_dealt(const void* d_in, void* d_out, size_t n_frames4096, int num_cus, hipStream_t stream,
+                                   sdrk_host::F4kProbeDeal& pd);
+hipError_t launch_copy_1to1_dealt(const void* d_in, void* d_out, size_t bytes, int num_cus, int blocks_per_cu, hipStream_t stream,
+                                  sdrk_host::F4kProbeDeal& pd);
 hipError_t launch_power_mean(const void* d_spec, size_t n_frames, int nfft, float scale, float* d_out,
                              hipStream_t stream);
 

@@ -142,6 +142,10 @@ struct sdrk_plan {
     sdrk_host::F4kTicketForm f4k_form = sdrk_host::F4K_TICKET_FORM;   // SDRK_F4K_TICKET_FORM (A/B work)
     unsigned* d_f4k_heads = nullptr;
     sdrk_host::F4kTicketBases f4k_bases = {};
+    // the "rot H" order (f4k_rot.h): f4k_rot_heads = 2, 4 or 8 (SDRK_F4K_TICKET_FORM=rot<H>), 0 = f4k_form above;
+    // d_f4k_rot = its heads and exit counter, zero between launches
+    unsigned f4k_rot_heads = sdrk_host::F4K_ROT_DEFAULT_HEADS;
+    unsigned* d_f4k_rot = nullptr;
     hipEvent_t f4k_ev = nullptr;
     hipStream_t f4k_last = nullptr;
     bool f4k_recorded = false;

@@ -195,8 +195,12 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
             a.n_frames = n_frames - f0 < per ? n_frames - f0 : per;
             if (ticket) {
                 const unsigned grid = f4k_ticket_grid(max_blocks, a.n_frames);
-                e = sdrk::launch_fft4096_ticket(a, p->d_f4k_heads, p->f4k_bases, p->f4k_form, grid);
-                if (e == hipSuccess) f4k_ticket_advance(p->f4k_form, p->f4k_bases, a.n_frames, grid);
+                if (p->f4k_rot_heads) {
+                    e = sdrk::launch_fft4096_rot(a, p->d_f4k_rot, p->f4k_rot_heads, grid);
+                } else {
+                    e = sdrk::launch_fft4096_ticket(a, p->d_f4k_heads, p->f4k_bases, p->f4k_form, grid);
+                    if (e == hipSuccess) f4k_ticket_advance(p->f4k_form, p->f4k_bases, a.n_frames, grid);
+                }
             } else {
                 e = sdrk::launch_fft4096(a);
             }
@@ -421,16 +425,19 @@ int sdrk_plan_create_ex(int device, int nfft, size_t max_batch, int window_kind,
         if (nfft == 4096) {
             // The heads of the ticket order, one 128-byte line each.  They start a few hundred tickets short of the 32-bit
             // wrap: every plan that lives for more than a launch or two crosses it, so the wrap is no rare path.
-            if (const char* env = getenv("SDRK_F4K_ORDER"))   // "stride" / "ticket": either loop at any size (f4k_ticket_takes)
-                p->f4k_order = env[0] == 't' ? F4K_ORDER_TICKET : (env[0] == 's' ? F4K_ORDER_STRIDE : F4K_ORDER_AUTO);
+            // SDRK_F4K_ORDER: "stride" / "ticket", either loop at any size (f4k_ticket_takes); SDRK_F4K_TICKET_FORM:
+            // "<heads>x<frames per ticket>" or "rot<heads>" (f4k_rot.h), A/B work
+            const F4kChoice choice = f4k_choice(getenv("SDRK_F4K_ORDER"), getenv("SDRK_F4K_TICKET_FORM"));
+            p->f4k_order = choice.order;
+            p->f4k_form = choice.form;
+            p->f4k_rot_heads = choice.rot_heads;
             if (const char* env = getenv("SDRK_F4K_PARTS")) {   // launches per call, either order: developer use (tools/f4k_ticket_launches.py)
                 long v = atol(env);
                 if (v >= 1 && v <= 4096) p->f4k_parts = (size_t)v;
             }
-            if (const char* env = getenv("SDRK_F4K_TICKET_FORM")) {   // "<heads>x<frames per ticket>": A/B work
-                F4kTicketForm f = {0, 0};
-                if (sscanf(env, "%ux%u", &f.heads, &f.frames) == 2 && f4k_ticket_form_ok(f)) p->f4k_form = f;
-            }
+            PLAN_TRY(hipMalloc((void**)&p->d_f4k_rot, F4K_ROT_WORDS * sizeof(uint32_t)));
+            const std::vector<uint32_t> rot0(F4K_ROT_WORDS, 0u);
+            PLAN_TRY(hipMemcpy(p->d_f4k_rot, rot0.data(), rot0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             std::vector<uint32_t> h(F4K_TICKET_MAX_HEADS * F4K_TICKET_HEAD_WORDS, 0u);
             for (unsigned x = 0; x < F4K_TICKET_MAX_HEADS; ++x) h[x * F4K_TICKET_HEAD_WORDS] = p->f4k_bases.base[x] = 0xFFFFFE00u;
             PLAN_TRY(hipMalloc((void**)&p->d_f4k_heads, h.size() * sizeof(uint32_t)));
@@ -561,6 +568,7 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     if (p->d_fir_h) (void)hipFree(p->d_fir_h);
     if (p->f4k_recorded) (void)hipEventSynchronize(p->f4k_ev);   // a ticketed launch on a caller's stream still draws from the heads
     if (p->d_f4k_heads) (void)hipFree(p->d_f4k_heads);
+    if (p->d_f4k_rot) (void)hipFree(p->d_f4k_rot);
     if (p->f4k_ev) (void)hipEventDestroy(p->f4k_ev);
     if (p->s_h2d) (void)hipStreamSynchronize(p->s_h2d);
     if (p->s_d2h) (void)hipStreamSynchronize(p->s_d2h);

@@ -117,6 +117,29 @@ int timed_probe(int device, int launches, float* each_ms, const char* what, Laun
     return SDRK_OK;
 }
 
+// The heads of one ceiling-probe call: its launches take their frames in the order a plan created now would (f4k_rot.h:
+// f4k_choice), from heads of the call's own.  timed_probe waits for its launches, so they never overlap.
+struct ProbeHeads {
+    F4kProbeDeal deal;
+    int status = SDRK_OK;
+    explicit ProbeHeads(int device) {
+        deal.choice = f4k_choice(getenv("SDRK_F4K_ORDER"), getenv("SDRK_F4K_TICKET_FORM"));
+        if (deal.choice.order == F4K_ORDER_STRIDE) return;            // the grid-stride loops: no heads
+        status = check_device(device);
+        if (status != SDRK_OK) return;
+        const std::vector<uint32_t> zero(F4K_ROT_WORDS, 0u);
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipMalloc((void**)&deal.d_heads, zero.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(deal.d_heads, zero.data(), zero.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) status = fail(SDRK_ERR_HIP, "probe heads: %s", hipGetErrorString(e));
+    }
+    ~ProbeHeads() {
+        if (deal.d_heads) (void)hipFree(deal.d_heads);
+    }
+    ProbeHeads(const ProbeHeads&) = delete;
+    ProbeHeads& operator=(const ProbeHeads&) = delete;
+};
+
 }  // namespace
 
 // SDRK_PLAN_TUNE_STAGING: the numpy boundary's device staging (HOST_SLOTS chunk pairs of ~16 MiB in / 8 MiB out) allocated
@@ -354,8 +377,10 @@ int sdrk_stream_ceiling_probe(int device, const void* d_in, void* d_out, size_t 
                               float* each_ms) {
     if (!d_in || !d_out || !each_ms || launches < 1 || launches > 4096 || n_frames4096 == 0)
         return fail(SDRK_ERR_INVALID, "bad argument");
+    ProbeHeads heads(device);
+    if (heads.status != SDRK_OK) return heads.status;
     return timed_probe(device, launches, each_ms, "stream ceiling probe", [&](int cus, hipStream_t s) {
-        return sdrk::launch_stream_mix(d_in, d_out, n_frames4096, cus, s);
+        return sdrk::launch_stream_mix_dealt(d_in, d_out, n_frames4096, cus, s, heads.deal);
     });
 }
 
@@ -365,9 +390,11 @@ int sdrk_copy_probe(int device, const void* d_in, void* d_out, size_t bytes, int
     // the fastest of three grid sizes (by median): a ceiling should not depend on the probe's own launch shape
     std::vector<float> t((size_t)launches), best;
     float best_med = 0.0f;
+    ProbeHeads heads(device);
+    if (heads.status != SDRK_OK) return heads.status;
     for (int bpc : {3, 4, 16}) {
         int st = timed_probe(device, launches, t.data(), "copy probe", [&](int cus, hipStream_t s) {
-            return sdrk::launch_copy_1to1(d_in, d_out, bytes, cus, bpc, s);
+            return sdrk::launch_copy_1to1_dealt(d_in, d_out, bytes, cus, bpc, s, heads.deal);
         });
         if (st != SDRK_OK) return st;
         std::vector<float> sorted = t;

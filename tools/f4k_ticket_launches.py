@@ -9,6 +9,14 @@ order is also timed as the product issues it ("product": one call, cut by f4k_sp
 `--reps` spans.  One record per process is appended to the JSON list in --out (profiles/f4k_ticket/SUMMARY.md).
 
     python tools/f4k_ticket_launches.py --out profiles/f4k_ticket/launches.json
+
+--paired FORM,FORM,... (profiles/f4k_window/SUMMARY.md) measures forms of the ticket order against the product's 1x2 instead:
+two plans in the process per comparison, 1x2 and the other form (SDRK_F4K_TICKET_FORM at creation), on the same pair; whole
+calls of 2^20 frames alternate between the two, each timed by events of its own, and each side is the median of `--reps`
+(after one uncounted launch each).  The first comparison on every pair is 1x2 against a second 1x2 plan: its largest
+difference over the pairs and processes is what alternation alone produces.
+
+    python tools/f4k_ticket_launches.py --paired rot2,rot4,rot8 --out profiles/f4k_window/paired.json
 """
 import argparse
 import ctypes
@@ -29,8 +37,12 @@ NFFT = 4096
 PARTS = [1, 2, 4, 8, 16]
 
 
-def plan_of(order, parts):
+def plan_of(order, parts, form=None):
     os.environ["SDRK_F4K_ORDER"] = order
+    if form:
+        os.environ["SDRK_F4K_TICKET_FORM"] = form
+    else:
+        os.environ.pop("SDRK_F4K_TICKET_FORM", None)
     if parts:
         os.environ["SDRK_F4K_PARTS"] = str(parts)
     else:
@@ -45,6 +57,8 @@ def main():
     ap.add_argument("--outputs", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--label", default="")
+    ap.add_argument("--probe", default="", help="comma-separated forms to time the no-arithmetic 2:1 probe under, beside stride and 1x2")
+    ap.add_argument("--paired", default="", help="comma-separated forms to time against 1x2, launches alternating")
     a = ap.parse_args()
     lib = _ffi.lib()
     _ffi.require_device(0)
@@ -71,6 +85,60 @@ def main():
             e1.synchronize()
             t.append(e0.elapsed_time(e1))
         return round(statistics.median(t[1:]), 4)
+
+    def alternate(plan_a, plan_b, p):
+        ta, tb = [], []
+        for _ in range(a.reps + 1):                                                  # the first of each is not counted
+            for plan, t in ((plan_a, ta), (plan_b, tb)):
+                e0.record(stream)
+                plan.exec_device(d_in.value, frames, p.value, stream=stream.cuda_stream)
+                e1.record(stream)
+                e1.synchronize()
+                t.append(e0.elapsed_time(e1))
+        return round(statistics.median(ta[1:]), 4), round(statistics.median(tb[1:]), 4)
+
+    if a.probe:
+        # the no-arithmetic 2:1 probe (sdrk_stream_ceiling_probe) on every pair, grid-stride and in each form: median of `reps`
+        forms = ["stride", "1x2"] + [f for f in a.probe.split(",") if f]
+        rec = {"kind": "f4k_probe_forms", "frames": frames, "outputs": a.outputs, "reps": a.reps, "forms": forms,
+               "d_in": hex(d_in.value), "d_out": [hex(p.value) for p in outs], "label": a.label, "pid": os.getpid(), "pairs": []}
+        ms = (ctypes.c_float * a.reps)()
+        os.environ["SDRK_F4K_ORDER"] = "stride"
+        warm_up_by_time(lambda: _ffi.check(lib.sdrk_stream_ceiling_probe(0, d_in, outs[0], frames, 1, ms)))
+        for p in outs:
+            row = {}
+            for form in forms:
+                os.environ["SDRK_F4K_ORDER"] = "stride" if form == "stride" else "ticket"
+                os.environ["SDRK_F4K_TICKET_FORM"] = "1x2" if form == "stride" else form
+                _ffi.check(lib.sdrk_stream_ceiling_probe(0, d_in, p, frames, a.reps, ms))
+                row[form] = round(statistics.median(ms), 4)
+            rec["pairs"].append(row)
+        for p in outs:
+            lib.sdrk_dev_free(0, p)
+        lib.sdrk_dev_free(0, d_in)
+        append_record(a.out, rec)
+        print(json.dumps(rec), flush=True)
+        return
+
+    if a.paired:
+        forms = ["1x2"] + [f for f in a.paired.split(",") if f]
+        rec = {"kind": "f4k_ticket_paired", "frames": frames, "outputs": a.outputs, "reps": a.reps, "forms": forms,
+               "d_in": hex(d_in.value), "d_out": [hex(p.value) for p in outs], "label": a.label, "pid": os.getpid(), "pairs": []}
+        with plan_of("ticket", 1, "1x2") as base:
+            warm_up_by_time(lambda: base.exec_device_timed(d_in.value, frames, outs[0].value, 1))
+            for p in outs:
+                row = {}
+                for form in forms:
+                    with plan_of("ticket", 1, form) as other:
+                        base_ms, form_ms = alternate(base, other, p)
+                    row[form] = {"base_ms": base_ms, "form_ms": form_ms, "gain_ms": round(base_ms - form_ms, 4)}
+                rec["pairs"].append(row)
+        for p in outs:
+            lib.sdrk_dev_free(0, p)
+        lib.sdrk_dev_free(0, d_in)
+        append_record(a.out, rec)
+        print(json.dumps(rec), flush=True)
+        return
 
     rec = {"kind": "f4k_ticket_launches", "frames": frames, "outputs": a.outputs, "reps": a.reps, "parts": PARTS,
            "d_in": hex(d_in.value), "d_out": [hex(p.value) for p in outs], "label": a.label, "pid": os.getpid()}
