@@ -333,8 +333,8 @@ int sdrk_exec_host_integrated_ci16(sdrk_plan* plan, const void* iq_ci16, size_t 
  * transform (2 bytes per sample in), every other length is widened on the device in chunks of at most 64 MiB first.  Each
  * entry point has the signature and the refusals of its _ci16 twin, and refuses an f64 plan and a format other than the two
  * with SDRK_ERR_INVALID; a plan that has refused still works.  The down-converter has an 8-bit form in a section of its own
- * (sdrk_exec_*_downconv_iq8, below); the filter bank, spectral kurtosis, cross-spectra, bin-tuned FIR / channel bank, Welch,
- * features and waterfall entry points have none. */
+ * (sdrk_exec_*_downconv_iq8, below), the filter bank and spectral kurtosis in another (sdrk_exec_*_pfb_iq8, _kurtosis_iq8,
+ * below); the cross-spectra, bin-tuned FIR / channel bank, Welch, features and waterfall entry points have none. */
 enum sdrk_iq8_format { SDRK_IQ8_SIGNED = 0, SDRK_IQ8_UNSIGNED = 1 };
 int sdrk_exec_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db);
 int sdrk_exec_fft_host_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_frames, size_t frame_stride,
@@ -502,6 +502,53 @@ int sdrk_exec_device_pfb_sk_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci
                                             float* each_ms);
 int sdrk_exec_host_pfb_sk_ci16(sdrk_plan* plan, const void* iq_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                                int out_form, float scale, float* out);
+
+/* ---- filter bank and spectral kurtosis from 8-bit I,Q: ci8 / cu8, 2 bytes per sample ------
+ * The polyphase-filter-bank sections (per frame and integrated) and the spectral-kurtosis section (plain and behind the filter
+ * bank) on interleaved 8-bit I,Q as the 8-bit section above defines it: `iq8_format` (SDRK_IQ8_SIGNED / SDRK_IQ8_UNSIGNED)
+ * right after the samples pointer, x[n] the exact float32 conversion given there (mid-scale 127.5 for unsigned bytes, no
+ * scale), and every entry point returns the bits its complex64 counterpart returns for those widened samples — at every nfft
+ * of a float32 plan, every T in [1, 32], stride, frame or group count, K, detector, out_form, scale and shift, from the device
+ * entries and the host entries alike, however a host call is chunked.  Each entry point has the argument list of its _ci16
+ * twin plus the format; frame_stride counts samples; a PFB buffer holds (frames - 1)*frame_stride + T*nfft samples of 2 bytes
+ * each; frame starts need 2-byte alignment only, so any stride serves.  The refusals are the twins' (for the PFB forms a
+ * windowed plan, an f64 plan, a plan without a prototype; k_frames < 2 for the kurtosis forms), and a format other than the two,
+ * each SDRK_ERR_INVALID with a message; a plan that has refused still works.  (The kurtosis entries spell the word out: _sk names
+ * the complex64 / int16 family.)
+ * N = 4096 reads the bytes inside the transform: the filter bank folds them in the transform's registers (2 B/sample read from
+ * device memory at frame_stride = nfft, 4 or 4/K written), plain spectral kurtosis keeps both sums there (2 + 8/K).  Other
+ * lengths fold the bytes straight into the PFB staging (no widened copy of the stream), or widen chunks of at most 64 MiB for
+ * the plain kurtosis, and go on as the complex64 forms do.  Behind the filter bank the kurtosis folds and transforms through
+ * the per-frame route at every nfft, as its twins do.  The host entries move 2 B/sample over the link, through the copy
+ * engines.  Not provided: cross-spectra, Welch, waterfall appends, double precision. */
+int sdrk_exec_device_pfb_iq8(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_frames, size_t frame_stride,
+                             float* d_out_db, void* stream);
+int sdrk_exec_device_pfb_iq8_timed_each(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_frames, size_t frame_stride,
+                                        float* d_out_db, int launches, float* each_ms);
+int sdrk_exec_host_pfb_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db);
+int sdrk_exec_fft_host_pfb_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, size_t n_frames, size_t frame_stride,
+                               void* out_c64);
+int sdrk_exec_device_pfb_integrated_iq8(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                        size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_pfb_integrated_iq8_timed_each(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups,
+                                                   size_t k_frames, size_t frame_stride, int detector, int out_form, float scale,
+                                                   float* d_out, int launches, float* each_ms);
+int sdrk_exec_host_pfb_integrated_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                      size_t frame_stride, int detector, int out_form, float scale, float* out);
+int sdrk_exec_device_kurtosis_iq8(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                  size_t frame_stride, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_kurtosis_iq8_timed_each(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                             size_t frame_stride, int out_form, float scale, float* d_out, int launches,
+                                             float* each_ms);
+int sdrk_exec_host_kurtosis_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                size_t frame_stride, int out_form, float scale, float* out);
+int sdrk_exec_device_pfb_kurtosis_iq8(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                      size_t frame_stride, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_pfb_kurtosis_iq8_timed_each(sdrk_plan* plan, const void* d_iq8, int iq8_format, size_t n_groups,
+                                                 size_t k_frames, size_t frame_stride, int out_form, float scale, float* d_out,
+                                                 int launches, float* each_ms);
+int sdrk_exec_host_pfb_kurtosis_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                    size_t frame_stride, int out_form, float scale, float* out);
 
 /* ---- two-channel cross-spectra: auto and cross power over K frames in one pass ----------
  * What two coherent receive channels give that one cannot: the cross term, and from it coherence (a common signal under

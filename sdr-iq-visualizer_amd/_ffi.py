@@ -241,6 +241,23 @@ SYMBOLS = [
     ("sdrk_exec_device_downconvbank_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_void_p]),
     ("sdrk_exec_device_downconvbank_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_downconvbank_iq8", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_uint32), c_int, c_uint64, c_void_p, c_size_t, POINTER(c_size_t)]),
+    # filter bank and spectral kurtosis from 8-bit I,Q: the _ci16 twins' argument lists with the format after the samples pointer
+    ("sdrk_exec_device_pfb_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_pfb_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                    c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_integrated_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                               c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_integrated_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                  c_void_p]),
+    ("sdrk_exec_device_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_kurtosis_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    ("sdrk_exec_device_pfb_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_pfb_kurtosis_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_pfb_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
 ]
 
 _lib = None

@@ -158,7 +158,8 @@ def main(argv=None) -> int:
         return _extract(args, sigmf_io, spectrum)
     # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
     # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for.
-    # A ci8 / cu8 recording stays 8-bit for the spectrum row and the --integrate rows; every other option widens it on the host.
+    # A ci8 / cu8 recording stays 8-bit for the spectrum row and the --integrate, --pfb and --sk rows (2 bytes per sample over the
+    # link and into the kernels); only the Welch leg widens it on the host, for itself.
     samples, meta = sigmf_io.read_sigmf(args.path, native="all")
     pair = None
     if args.cross:   # both channels as they are stored (element n: sample n of channel 0, then of channel 1); the rest: channel 0
@@ -174,7 +175,7 @@ def main(argv=None) -> int:
     raw16 = samples if samples.dtype == np.int16 else None
     raw8 = np.ascontiguousarray(samples) if samples.dtype in (np.int8, np.uint8) else None
     if raw8 is not None:
-        samples = spectrum.iq8_to_c64(raw8) if (args.welch or args.pfb or args.sk) else raw8
+        samples = raw8
     n_samples = int(samples.shape[0])
     if n_samples < args.nfft:
         print(f"recording has {n_samples} samples, need {args.nfft}", file=sys.stderr)
@@ -195,6 +196,8 @@ def main(argv=None) -> int:
     if args.welch:
         if raw16 is not None:
             samples = raw16.astype(np.float32).view(np.complex64).reshape(-1)
+        elif raw8 is not None:
+            samples = spectrum.iq8_to_c64(raw8)
         pxx = spectrum.welch_psd(samples, args.welch, fs, device=args.device)
         results["welch_pxx"] = pxx
         results["welch_freqs"] = spectrum.freq_axis(args.welch, fs, fc)
@@ -217,9 +220,11 @@ def main(argv=None) -> int:
         report["integrated_rows"] = int(rows.shape[0])
         if rows.shape[0] == 0:
             print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no integrated row", file=sys.stderr)
-    if args.pfb:   # the prototype is the window: --window does not apply; an int16 recording goes in as it is
+    if args.pfb:   # the prototype is the window: --window does not apply; an int16 or 8-bit recording goes in as it is
         if raw16 is not None:
             rows = spectrum.pfb_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.pfb, device=args.device)
+        elif raw8 is not None:
+            rows = spectrum.pfb_db_ci8(raw8, args.nfft, args.pfb, device=args.device)
         else:
             rows = spectrum.pfb_db(samples, args.nfft, args.pfb, device=args.device)
         results["pfb_db"] = rows
@@ -231,17 +236,22 @@ def main(argv=None) -> int:
             if raw16 is not None:
                 rows = spectrum.pfb_integrated_db_ci16(np.ascontiguousarray(raw16), args.nfft, args.pfb, args.integrate,
                                                        detector=args.detector, device=args.device)
+            elif raw8 is not None:
+                rows = spectrum.pfb_integrated_db_ci8(raw8, args.nfft, args.pfb, args.integrate, detector=args.detector,
+                                                      device=args.device)
             else:
                 rows = spectrum.pfb_integrated_db(samples, args.nfft, args.pfb, args.integrate, detector=args.detector,
                                                   device=args.device)
             results["pfb_integrated_db"] = rows
             report["pfb_integrated_rows"] = int(rows.shape[0])
-    if args.sk:   # (behind the filter bank with --pfb; an int16 recording goes in as it is)
-        x = np.ascontiguousarray(raw16) if raw16 is not None else samples
+    if args.sk:   # (behind the filter bank with --pfb; an int16 or 8-bit recording goes in as it is)
+        x = np.ascontiguousarray(raw16) if raw16 is not None else raw8 if raw8 is not None else samples
         if args.pfb:
             mean_db, sk = spectrum.pfb_spectral_kurtosis(x, args.nfft, args.pfb, args.integrate, device=args.device)
         elif raw16 is not None:
             mean_db, sk = spectrum.spectral_kurtosis_ci16(x, args.nfft, args.integrate, window=args.window, device=args.device)
+        elif raw8 is not None:
+            mean_db, sk = spectrum.spectral_kurtosis_ci8(x, args.nfft, args.integrate, window=args.window, device=args.device)
         else:
             mean_db, sk = spectrum.spectral_kurtosis(x, args.nfft, args.integrate, window=args.window, device=args.device)
         lo, hi = spectrum.sk_limits(args.integrate)

@@ -13,6 +13,10 @@
 // the other lengths (plan_launch, ci16_api.hip's launch_ci16, pfb_api.hip's launch_pfb / launch_pfb_ci16, which keep their own
 // stagings and orderings).  The PFB entries refuse a plan without a prototype first (check_pfb_ready).
 //
+// The 8-bit forms (sdrk_exec_*_integrated_ci8, _pfb_integrated_iq8, _kurtosis_iq8, _pfb_kurtosis_iq8) bind the format into the
+// launchers of their IntIo (kernels_ci8.h): fft4096_kgroup_ci8.hip, pfb4096_iq8_groups.hip and sk4096_iq8.hip at N = 4096,
+// launch_ci8_fn / launch_pfb_iq8_fn elsewhere.
+//
 // The spectral-kurtosis entry points (sdrk_exec_*_sk, _sk_ci16, _pfb_sk, _pfb_sk_ci16) are the same call with the kernels of
 // kernels_sk.h behind it: per group two planes, the mean power and the estimator from S1 = sum p and S2 = sum p^2.  N = 4096
 // keeps the sums inside the transform (sk4096.hip); every other length, and the filter bank at every length (N = 4096 too: fold
@@ -62,6 +66,12 @@ IntIo ci8_io(int fmt) {
 IntIo pfb_io(const sdrk_plan* p) { return int_io(sizeof(float2), sdrk::launch_pfb4096_groups, launch_pfb, p); }
 IntIo pfb_ci16_io(const sdrk_plan* p) { return int_io(4, sdrk::launch_pfb4096_i16_groups, launch_pfb_ci16, p); }
 
+// 8-bit I,Q behind the filter bank: the format bound into both launchers, as ci8_io
+IntIo pfb_iq8_io(const sdrk_plan* p, int fmt) {
+    return fmt == SDRK_IQ8_SIGNED ? int_io(2, sdrk::launch_pfb4096_iq8_groups<SDRK_IQ8_SIGNED>, launch_pfb_iq8_fn(fmt), p)
+                                  : int_io(2, sdrk::launch_pfb4096_iq8_groups<SDRK_IQ8_UNSIGNED>, launch_pfb_iq8_fn(fmt), p);
+}
+
 // spectral kurtosis: the mode's IntIo with the SK kernels behind it (fused: the N = 4096 kernel, or none)
 IntIo sk_io(IntIo io, FusedFn fused) {
     io.fused = fused;
@@ -74,8 +84,13 @@ IntIo sk_io(IntIo io, FusedFn fused) {
 
 IntIo sk_c64_io() { return sk_io(c64_io(), sdrk::launch_sk4096); }
 IntIo sk_ci16_io() { return sk_io(ci16_io(), sdrk::launch_sk4096_i16); }
+IntIo sk_iq8_io(int fmt) {
+    return fmt == SDRK_IQ8_SIGNED ? sk_io(ci8_io(fmt), sdrk::launch_sk4096_iq8<SDRK_IQ8_SIGNED>)
+                                  : sk_io(ci8_io(fmt), sdrk::launch_sk4096_iq8<SDRK_IQ8_UNSIGNED>);
+}
 IntIo sk_pfb_io(const sdrk_plan* p) { return sk_io(pfb_io(p), nullptr); }
 IntIo sk_pfb_ci16_io(const sdrk_plan* p) { return sk_io(pfb_ci16_io(p), nullptr); }
+IntIo sk_pfb_iq8_io(const sdrk_plan* p, int fmt) { return sk_io(pfb_iq8_io(p, fmt), nullptr); }
 
 // two-channel cross-spectra: elements of 16 (complex64) or 8 (int16) bytes; always through the plan's plain complex64 transform
 IntIo xspec_io(size_t in_elem, FusedFn fused) {
@@ -190,6 +205,32 @@ int sdrk_exec_host_pfb_integrated_ci16(sdrk_plan* p, const void* iq_ci16, size_t
     return exec_host_integrated(pfb_ci16_io(p), p, iq_ci16, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
 }
 
+// 8-bit I,Q behind the filter bank: the plan's refusals first (the _ci16 twin's words), then the format's
+#define SDRK_PFB_IQ8_READY                                                                                                        \
+    if (int st = check_pfb_ready(p); st != SDRK_OK) return st;                                                                    \
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st
+
+int sdrk_exec_device_pfb_integrated_iq8(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                        size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream) {
+    SDRK_PFB_IQ8_READY;
+    return exec_device_integrated(pfb_iq8_io(p, iq8_format), p, d_iq8, n_groups, k_frames, frame_stride, detector, out_form, scale, d_out,
+                                  stream);
+}
+
+int sdrk_exec_device_pfb_integrated_iq8_timed_each(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                                   size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                   int launches, float* each_ms) {
+    SDRK_PFB_IQ8_READY;
+    return exec_device_integrated_timed_each(pfb_iq8_io(p, iq8_format), p, d_iq8, n_groups, k_frames, frame_stride, detector, out_form,
+                                             scale, d_out, launches, each_ms);
+}
+
+int sdrk_exec_host_pfb_integrated_iq8(sdrk_plan* p, const void* iq8, int iq8_format, size_t n_groups, size_t k_frames,
+                                      size_t frame_stride, int detector, int out_form, float scale, float* out) {
+    SDRK_PFB_IQ8_READY;
+    return exec_host_integrated(pfb_iq8_io(p, iq8_format), p, iq8, n_groups, k_frames, frame_stride, detector, out_form, scale, out);
+}
+
 // ---- spectral kurtosis: two planes per group (the detector of the shared call is the mean's, and is not read) ----
 
 #define SDRK_SK_ENTRIES(SUFFIX, IO, READY)                                                                                        \
@@ -219,6 +260,34 @@ SDRK_SK_ENTRIES(pfb_sk, sk_pfb_io(p), SDRK_PFB_READY)
 SDRK_SK_ENTRIES(pfb_sk_ci16, sk_pfb_ci16_io(p), SDRK_PFB_READY)
 #undef SDRK_PFB_READY
 #undef SDRK_SK_ENTRIES
+
+// the same three from 8-bit I,Q, the format right after the samples (spelled out: the _sk names are the complex64 / int16 family's)
+#define SDRK_KURTOSIS_IQ8_ENTRIES(SUFFIX, IO, READY)                                                                              \
+    int sdrk_exec_device_##SUFFIX(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames,              \
+                                  size_t frame_stride, int out_form, float scale, float* d_out, void* stream) {                  \
+        READY;                                                                                                                    \
+        return exec_device_integrated(IO, p, d_iq8, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale, d_out, stream); \
+    }                                                                                                                             \
+    int sdrk_exec_device_##SUFFIX##_timed_each(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_groups, size_t k_frames, \
+                                               size_t frame_stride, int out_form, float scale, float* d_out, int launches,       \
+                                               float* each_ms) {                                                                  \
+        READY;                                                                                                                    \
+        return exec_device_integrated_timed_each(IO, p, d_iq8, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale, \
+                                                 d_out, launches, each_ms);                                                       \
+    }                                                                                                                             \
+    int sdrk_exec_host_##SUFFIX(sdrk_plan* p, const void* iq8, int iq8_format, size_t n_groups, size_t k_frames,                  \
+                                size_t frame_stride, int out_form, float scale, float* out) {                                    \
+        READY;                                                                                                                    \
+        return exec_host_integrated(IO, p, iq8, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, out_form, scale, out);          \
+    }
+#define SDRK_IQ8_READY                                                                                                            \
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st
+
+SDRK_KURTOSIS_IQ8_ENTRIES(kurtosis_iq8, sk_iq8_io(iq8_format), SDRK_IQ8_READY)
+SDRK_KURTOSIS_IQ8_ENTRIES(pfb_kurtosis_iq8, sk_pfb_iq8_io(p, iq8_format), SDRK_PFB_IQ8_READY)
+#undef SDRK_IQ8_READY
+#undef SDRK_PFB_IQ8_READY
+#undef SDRK_KURTOSIS_IQ8_ENTRIES
 
 // ---- two-channel cross-spectra: four planes per group, always the scaled-power form (detector and out_form are not read) ----
 

@@ -37,6 +37,17 @@ struct IntegrateArgs;
 hipError_t launch_pfb4096_groups(const IntegrateArgs& a);
 hipError_t launch_pfb4096_i16_groups(const IntegrateArgs& a);   // pfb4096_i16_groups.hip: d_in points at int16 pairs
 
+// The three on interleaved 8-bit I,Q, 2 bytes per sample (pfb4096_iq8.hip, pfb_fold_iq8.hip, pfb4096_iq8_groups.hip): d_iq
+// points at byte pairs, frame_stride counts samples, fmt / FMT is an SDRK_IQ8_* value and x the conversion of kernels_ci8.h,
+// exact in float32, then the arithmetic above.  Where a host table holds the launcher the format is bound into it (explicitly
+// instantiated for the two formats), as kernels_ci8.h does.
+hipError_t launch_pfb4096_iq8(const LaunchArgs& a, int fmt, const float* d_h, int taps, int assign);
+template <int FMT>
+hipError_t launch_pfb_fold_iq8(const void* d_iq, size_t frame_stride, size_t n_frames, int nfft, const float* d_h, int taps,
+                               void* d_out, int num_cus, hipStream_t stream);
+template <int FMT>
+hipError_t launch_pfb4096_iq8_groups(const IntegrateArgs& a);
+
 #ifdef __HIPCC__
 typedef float pfb_v2f __attribute__((ext_vector_type(2)));
 // One tap of the fold on a complex sample: the product rounded, then the sum rounded.  Contraction is switched off here whatever

@@ -12,6 +12,10 @@ namespace sdrk {
 
 hipError_t launch_sk4096(const IntegrateArgs& a);       // complex64 samples
 hipError_t launch_sk4096_i16(const IntegrateArgs& a);   // interleaved int16 I,Q: the same bits on the widened samples
+// sk4096_iq8.hip: interleaved 8-bit I,Q of format FMT (an SDRK_IQ8_* value, bound in as kernels_ci8.h's launchers bind it;
+// explicitly instantiated for the two formats): the same bits on the widened samples
+template <int FMT>
+hipError_t launch_sk4096_iq8(const IntegrateArgs& a);
 hipError_t launch_sk_rows(const IntegrateArgs& a);      // complex64 spectra in staging (EPI_COMPLEX, the plan's shift order)
 // slices > 1: S1, S2 of group g = the partials[g * slices + s] added in ascending s in float64 and rounded to float32 once
 // (the argument list of launch_integrate_finalize; `detector` is not read)

@@ -3,6 +3,8 @@
 // gives their int16 forms (pfb4096_i16.hip, pfb4096_i16_groups.hip).  A policy names the sample type the stream pointer
 // counts in (`sample`), the word a loaded sample travels in (`word`), and issues, and widens at the point of use; everything
 // else — frame assignment, tap loop, one block in flight, transform, epilogue, unit bookkeeping — is the same text.
+// The bodies take the policy as an object too (`in`), for what its widen() needs at run time: the 8-bit policy's conversion
+// (F4kInPfbIq8; pfb4096_iq8.hip, pfb4096_iq8_groups.hip).  The other policies are empty, and compile as they did without it.
 #pragma once
 #include "fft4096_core.h"
 #include "kernels_integrate.h"
@@ -15,7 +17,7 @@ namespace sdrk {
 template <int EPILOGUE, class In>
 __device__ __forceinline__ void pfb4096_body(
     const typename In::sample* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw, size_t n_frames,
-    const float* __restrict__ h, int taps, const float2* __restrict__ tw4096, float eps, int shift, int assign) {
+    const float* __restrict__ h, int taps, const float2* __restrict__ tw4096, float eps, int shift, int assign, In in = In{}) {
     __shared__ float2 lds[f4k_lds_elems(false)];
     float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
     float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
@@ -54,7 +56,7 @@ __device__ __forceinline__ void pfb4096_body(
     auto take = [&](cf (&w)[16], float (&c)[16], size_t f, int t) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            w[j] = In::widen(nxt[j]);
+            w[j] = in.widen(nxt[j]);
             c[j] = cn[j];
         }
         if (t + 1 < taps) issue(f, t + 1); else issue(f + step, 0);
@@ -87,7 +89,7 @@ template <int DET, class In>
 __device__ __forceinline__ void pfb4096_groups_body(
     const typename In::sample* __restrict__ iq, size_t frame_stride, IntUnits c, float* __restrict__ out, float2* __restrict__ partials,
     const float2* __restrict__ carry_in, float2* __restrict__ carry_out, const float* __restrict__ h, int taps,
-    const float2* __restrict__ tw4096, int shift) {
+    const float2* __restrict__ tw4096, int shift, In in = In{}) {
     constexpr bool CMP_LDS = DET == INT_DET_MEAN;
     __shared__ float2 lds[f4k_lds_elems(CMP_LDS)];
     float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;
@@ -144,7 +146,7 @@ __device__ __forceinline__ void pfb4096_groups_body(
             auto take = [&](cf (&w)[16], float (&cw)[16], int t) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    w[j] = In::widen(nxt[j]);
+                    w[j] = in.widen(nxt[j]);
                     cw[j] = cn[j];
                 }
                 if (t + 1 < taps) issue(f, t + 1); else In::issue_samples(nxt, iq + (f_next - c.f0) * frame_stride, tid);

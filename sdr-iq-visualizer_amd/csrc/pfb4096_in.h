@@ -1,9 +1,11 @@
 // pfb4096_in.h — the input policies of the N = 4096 polyphase-filter-bank kernels (pfb4096_body.h), the PFB counterparts of
 // fft4096_core.h's F4kInC64 and fft4096_in_ci16.h's F4kInCi16: F4kInPfb reads complex64 (pfb4096.hip, pfb4096_groups.hip),
-// F4kInPfbI16 interleaved int16 I,Q (pfb4096_i16.hip, pfb4096_i16_groups.hip).
+// F4kInPfbI16 interleaved int16 I,Q (pfb4096_i16.hip, pfb4096_i16_groups.hip), F4kInPfbIq8 interleaved 8-bit I,Q of either
+// format (pfb4096_iq8.hip, pfb4096_iq8_groups.hip).
 #pragma once
 #include "fft4096_core.h"
 #include "kernels_ci16.h"
+#include "kernels_ci8.h"
 
 namespace sdrk {
 
@@ -58,6 +60,35 @@ struct F4kInPfbI16 {
     static __device__ __forceinline__ cf widen(word w) {
         float re, im;
         ci16_unpack(w, re, im);
+        return cf{re, im};
+    }
+};
+
+// The same for 8-bit I,Q (SigMF ci8 / cu8), 2 bytes per sample: each sample is one 16-bit load, zero-extended into its dword,
+// through a resource of exactly the block's 4096 * 2 bytes, so block starts need 2-byte alignment only (any hop, odd ones
+// too) and no load can leave the block.  Default cache policy, as above.  The policy is an object: it carries the call's
+// conversion (kernels_ci8.h: a run-time kernel argument, so a format adds no instantiation) to the point of use, where
+// x = ci8_unpack(word) exactly.  Coefficients first, for F4kInPfbI16's reason: the sample word is one dword here too.
+struct F4kInPfbIq8 {
+    typedef unsigned short sample;
+    typedef unsigned word;
+    Iq8Conv conv;
+    static __device__ __forceinline__ void issue_samples(word (&x)[16], const unsigned short* block, int tid) {
+        __amdgpu_buffer_rsrc_t r = frame_rsrc(block, F4K_N * 2);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b16(r, tid * 2, j * 512, 0);
+    }
+    static __device__ __forceinline__ void issue_coeffs(float (&c)[16], const float* hblock, int tid) {
+        F4kInPfb::issue_coeffs(c, hblock, tid);
+    }
+    static __device__ __forceinline__ void issue(word (&x)[16], float (&c)[16], const unsigned short* block, const float* hblock,
+                                                 int tid) {
+        issue_coeffs(c, hblock, tid);
+        issue_samples(x, block, tid);
+    }
+    __device__ __forceinline__ cf widen(word w) const {
+        float re, im;
+        ci8_unpack(w, conv, re, im);
         return cf{re, im};
     }
 };

@@ -1,15 +1,17 @@
 // pfb_api.hip — host side of the per-frame polyphase-filter-bank entry points of include/sdrk.h (sdrk_plan_set_pfb,
-// sdrk_plan_pfb_taps, sdrk_exec_*_pfb, sdrk_exec_*_pfb_ci16): a prototype filter of T * nfft coefficients folds T consecutive
-// blocks of a stream into each frame in front of the plan's transform (kernels_pfb.h has the exact arithmetic).  The stream is
-// complex64, or interleaved little-endian int16 I,Q at 4 bytes per sample: x[n] = float32(I[n]) + i float32(Q[n]) exactly, then
-// the bits of the complex64 call.  Sits in front of app/sdr/streamer.py:119-121; the reference has no counterpart.
+// sdrk_plan_pfb_taps, sdrk_exec_*_pfb, sdrk_exec_*_pfb_ci16, sdrk_exec_*_pfb_iq8): a prototype filter of T * nfft coefficients
+// folds T consecutive blocks of a stream into each frame in front of the plan's transform (kernels_pfb.h has the exact
+// arithmetic).  The stream is complex64, or interleaved little-endian int16 I,Q at 4 bytes per sample: x[n] = float32(I[n]) +
+// i float32(Q[n]) exactly, then the bits of the complex64 call; or interleaved 8-bit I,Q (ci8 / cu8) at 2 bytes per sample,
+// widened as kernels_ci8.h says, with the format bound into the launchers (launch_pfb_iq8_fn).  Sits in front of
+// app/sdr/streamer.py:119-121; the reference has no counterpart.
 //
-// N = 4096 is one launch on the caller's stream (pfb4096.hip, pfb4096_i16.hip: the fold in the transform's registers).  Every
-// other length (single-pass, two-pass with the persistent N = 65536 form, chirp-z) runs "fold a chunk of frames into plan-owned
-// complex64 staging (pfb_fold.hip, pfb_fold_i16.hip: no widened copy of an int16 stream), then plan_launch" on the same stream,
-// the staging capped at 64 MiB and cut at frame boundaries however many frames the call has.  The numpy boundary is
-// sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame: a chunk carries its (T - 1) * nfft
-// samples of overlap.
+// N = 4096 is one launch on the caller's stream (pfb4096.hip, pfb4096_i16.hip, pfb4096_iq8.hip: the fold in the transform's
+// registers).  Every other length (single-pass, two-pass with the persistent N = 65536 form, chirp-z) runs "fold a chunk of
+// frames into plan-owned complex64 staging (pfb_fold.hip, pfb_fold_i16.hip, pfb_fold_iq8.hip: no widened copy of an integer
+// stream), then plan_launch" on the same stream, the staging capped at 64 MiB and cut at frame boundaries however many frames
+// the call has.  The numpy boundary is sdrk_host_pipeline.hip's exec_host with an input span of T * nfft samples per frame: a
+// chunk carries its (T - 1) * nfft samples of overlap.
 // Integration over K folded frames is integrate_api.hip, with this file's launchers and checks.  Out of scope: double
 // precision, waterfall appends.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
@@ -135,6 +137,31 @@ int sdrk_host::launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, 
     return launch_pfb_any(p, d_in, 4, sdrk::launch_pfb_fold_i16, sdrk::launch_pfb4096_i16, n_frames, stride, d_out, epilogue, stream);
 }
 
+namespace {
+
+// 8-bit I,Q of format FMT (SDRK_IQ8_*): neither PfbFoldFn nor LaunchFn carries a format, so it is bound into the functions the
+// tables hold, as ci16_api.hip's launch_ci8_fn binds it.  2 bytes per sample in.
+template <int FMT>
+int launch_pfb_iq8_bound(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream) {
+    return launch_pfb_any(
+        p, d_in, 2, sdrk::launch_pfb_fold_iq8<FMT>,
+        [](const sdrk::LaunchArgs& a, const float* d_h, int taps, int assign) { return sdrk::launch_pfb4096_iq8(a, FMT, d_h, taps, assign); },
+        n_frames, stride, d_out, epilogue, stream);
+}
+
+// The refusals of an 8-bit PFB entry in front of the call's own: the plan's (the _ci16 twin's words), then the format's.
+int check_pfb_iq8(const sdrk_plan* p, int fmt) {
+    int st = check_pfb_ready(p);
+    if (st == SDRK_OK) st = check_iq8_format(p, fmt);
+    return st;
+}
+
+}  // namespace
+
+LaunchFn sdrk_host::launch_pfb_iq8_fn(int fmt) {
+    return fmt == SDRK_IQ8_SIGNED ? launch_pfb_iq8_bound<SDRK_IQ8_SIGNED> : launch_pfb_iq8_bound<SDRK_IQ8_UNSIGNED>;
+}
+
 extern "C" {
 
 int sdrk_plan_set_pfb(sdrk_plan* p, int taps, const float* h) {
@@ -197,6 +224,29 @@ int sdrk_exec_host_pfb_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_frames, 
 
 int sdrk_exec_fft_host_pfb_ci16(sdrk_plan* p, const void* iq_ci16, size_t n_frames, size_t frame_stride, void* out_c64) {
     return exec_host_pfb(4, launch_pfb_ci16, sdrk::EPI_COMPLEX, p, iq_ci16, n_frames, frame_stride, out_c64);
+}
+
+int sdrk_exec_device_pfb_iq8(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_frames, size_t frame_stride, float* d_out_db,
+                             void* stream) {
+    if (int st = check_pfb_iq8(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_frames(check_pfb_exec, launch_pfb_iq8_fn(iq8_format), p, d_iq8, n_frames, frame_stride, d_out_db, stream);
+}
+
+int sdrk_exec_device_pfb_iq8_timed_each(sdrk_plan* p, const void* d_iq8, int iq8_format, size_t n_frames, size_t frame_stride,
+                                        float* d_out_db, int launches, float* each_ms) {
+    if (int st = check_pfb_iq8(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_frames_timed_each(check_pfb_exec, launch_pfb_iq8_fn(iq8_format), p, d_iq8, n_frames, frame_stride, d_out_db,
+                                         launches, each_ms);
+}
+
+int sdrk_exec_host_pfb_iq8(sdrk_plan* p, const void* iq8, int iq8_format, size_t n_frames, size_t frame_stride, float* out_db) {
+    if (int st = check_pfb_iq8(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_pfb(2, launch_pfb_iq8_fn(iq8_format), sdrk::EPI_LOGPSD, p, iq8, n_frames, frame_stride, out_db);
+}
+
+int sdrk_exec_fft_host_pfb_iq8(sdrk_plan* p, const void* iq8, int iq8_format, size_t n_frames, size_t frame_stride, void* out_c64) {
+    if (int st = check_pfb_iq8(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_pfb(2, launch_pfb_iq8_fn(iq8_format), sdrk::EPI_COMPLEX, p, iq8, n_frames, frame_stride, out_c64);
 }
 
 }  // extern "C"

@@ -404,6 +404,9 @@ int check_iq8_format(const sdrk_plan* p, int fmt);
 // frames into the plan's PFB staging, at most 64 MiB, and runs the plan's transform on that.
 int launch_pfb(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
 int launch_pfb_ci16(sdrk_plan* p, const void* d_in, size_t n_frames, size_t stride, void* d_out, int epilogue, hipStream_t stream);
+// The same on interleaved 8-bit I,Q (2 bytes per sample) of format fmt (SDRK_IQ8_*, checked by the caller): the LaunchFn with
+// the format bound into it, as launch_ci8_fn.
+LaunchFn launch_pfb_iq8_fn(int fmt);
 // What every PFB entry point refuses: float64 or windowed plans; for any transform, per frame or integrated, also a plan
 // with no prototype set (check_pfb_ready); and for a per-frame one zero frames, NULL pointers, stride 0 with more than one
 // frame (the integrated calls leave those to integrate_call.h).

@@ -28,7 +28,8 @@ the float32 path — the result has the same bits as the complex64 call on the w
 No scale is applied (fold 1/32768 into a custom window, or add a constant to the dB rows).
 
 ``*_ci8`` take the 8-bit pairs of SigMF ``ci8`` (int8: ``x = I + 1j*Q``) and ``cu8`` (uint8: ``x = (I - 127.5) + 1j*(Q - 127.5)``)
-the same way — the array's dtype is the format — for per-frame rows / spectra and integrated spectra: the bits of the complex64
+the same way — the array's dtype is the format — for per-frame rows / spectra, integrated spectra, the polyphase filter bank
+(``pfb_*_ci8``) and spectral kurtosis (``spectral_kurtosis_ci8``, ``pfb_spectral_kurtosis_ci8``): the bits of the complex64
 call on ``iq8_to_c64(iq)``, from a quarter of the input bytes.
 
 ``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` / ``pfb_integrate`` and the module functions ``pfb_db`` and
@@ -412,7 +413,8 @@ _CI16 = _Mode(True, False, "sdrk_exec_host_ci16", "sdrk_exec_fft_host_ci16", "sd
               "sdrk_exec_host_sk_ci16", "sdrk_exec_device_sk_ci16", "sdrk_exec_device_sk_ci16_timed_each")
 _CI8 = _Mode(False, False, "sdrk_exec_host_ci8", "sdrk_exec_fft_host_ci8", "sdrk_exec_device_ci8",
              "sdrk_exec_device_ci8_timed_each", "sdrk_exec_host_integrated_ci8", "sdrk_exec_device_integrated_ci8",
-             "sdrk_exec_device_integrated_ci8_timed_each", "", "", "", iq8=True)      # (no spectral-kurtosis form)
+             "sdrk_exec_device_integrated_ci8_timed_each",
+             "sdrk_exec_host_kurtosis_iq8", "sdrk_exec_device_kurtosis_iq8", "sdrk_exec_device_kurtosis_iq8_timed_each", iq8=True)
 _PFB = _Mode(False, True, "sdrk_exec_host_pfb", "sdrk_exec_fft_host_pfb", "sdrk_exec_device_pfb",
              "sdrk_exec_device_pfb_timed_each", "sdrk_exec_host_pfb_integrated", "sdrk_exec_device_pfb_integrated",
              "sdrk_exec_device_pfb_integrated_timed_each",
@@ -421,6 +423,11 @@ _PFB_CI16 = _Mode(True, True, "sdrk_exec_host_pfb_ci16", "sdrk_exec_fft_host_pfb
                   "sdrk_exec_device_pfb_ci16_timed_each", "sdrk_exec_host_pfb_integrated_ci16",
                   "sdrk_exec_device_pfb_integrated_ci16", "sdrk_exec_device_pfb_integrated_ci16_timed_each",
                   "sdrk_exec_host_pfb_sk_ci16", "sdrk_exec_device_pfb_sk_ci16", "sdrk_exec_device_pfb_sk_ci16_timed_each")
+_PFB_CI8 = _Mode(False, True, "sdrk_exec_host_pfb_iq8", "sdrk_exec_fft_host_pfb_iq8", "sdrk_exec_device_pfb_iq8",
+                 "sdrk_exec_device_pfb_iq8_timed_each", "sdrk_exec_host_pfb_integrated_iq8",
+                 "sdrk_exec_device_pfb_integrated_iq8", "sdrk_exec_device_pfb_integrated_iq8_timed_each",
+                 "sdrk_exec_host_pfb_kurtosis_iq8", "sdrk_exec_device_pfb_kurtosis_iq8",
+                 "sdrk_exec_device_pfb_kurtosis_iq8_timed_each", iq8=True)
 
 
 class SpectrumPlan:
@@ -987,6 +994,51 @@ class SpectrumPlan:
         return self._exec_device_timed_each(_PFB_CI16, d_iq, n_groups, d_out, launches, frame_stride,
                                             _Integ(k, detector, out, scale))
 
+    # ... from 8-bit I,Q (int8: ci8, uint8: cu8): the bits of the seven on ``iq8_to_c64`` of the samples, from a quarter of the bytes
+    def pfb_db_ci8(self, iq, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``pfb_db`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 or uint8: bit-identical to ``pfb_db`` on
+        ``iq8_to_c64(iq)``; no scale is applied to the samples.  The bytes are read by the folding kernel itself (2 bytes per
+        sample over the link and from device memory)."""
+        return self._host_rows(_PFB_CI8, iq, hop, out)
+
+    def pfb_fft_ci8(self, iq, hop: Optional[int] = None) -> np.ndarray:
+        """``pfb_fft`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)``: the same bits as on the widened samples."""
+        return self._host_rows(_PFB_CI8, iq, hop, spectra=True)
+
+    def exec_device_pfb_ci8(self, d_iq: int, n_frames: int, d_out: int, *, unsigned: bool = False,
+                            frame_stride: Optional[int] = None, stream: int = 0) -> None:
+        """Device pointers: the raw 8-bit I,Q stream in (``(n_frames-1)*frame_stride + taps*nfft`` samples of 2 bytes;
+        ``unsigned``: cu8, else ci8; frame starts 2-byte aligned) / float32 rows out, asynchronous on ``stream`` (0: the
+        plan's stream); any number of frames."""
+        self._exec_device(_PFB_CI8, d_iq, n_frames, d_out, frame_stride, stream, fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_pfb_ci8_timed_each(self, d_iq: int, n_frames: int, d_out: int, launches: int = 1, *,
+                                       unsigned: bool = False, frame_stride: Optional[int] = None) -> list:
+        """``exec_device_pfb_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_timed_each(_PFB_CI8, d_iq, n_frames, d_out, launches, frame_stride,
+                                            fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def pfb_integrate_ci8(self, iq, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                          scale: float = 1.0) -> np.ndarray:
+        """``pfb_integrate`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 or uint8: bit-identical to
+        ``pfb_integrate`` on ``iq8_to_c64(iq)``.  At nfft = 4096 the bytes are read inside the folding, reducing transform."""
+        return self._host_integrated(_PFB_CI8, iq, hop, _Integ(k, detector, out, scale))
+
+    def exec_device_pfb_integrated_ci8(self, d_iq: int, n_groups: int, k: int, d_out: int, *, unsigned: bool = False,
+                                       frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                       scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: the raw 8-bit I,Q stream in (``(n_groups*k - 1)*frame_stride + taps*nfft`` samples of 2 bytes;
+        ``unsigned``: cu8, else ci8), ``n_groups`` float32 rows out, asynchronous on ``stream`` (0: the plan's stream)."""
+        self._exec_device(_PFB_CI8, d_iq, n_groups, d_out, frame_stride, stream, _Integ(k, detector, out, scale),
+                          fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_pfb_integrated_ci8_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                                  unsigned: bool = False, frame_stride: Optional[int] = None,
+                                                  detector: str = "mean", out: str = "db", scale: float = 1.0) -> list:
+        """``exec_device_pfb_integrated_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_timed_each(_PFB_CI8, d_iq, n_groups, d_out, launches, frame_stride,
+                                            _Integ(k, detector, out, scale), fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
     # -- spectral kurtosis: mean power and SK per k frames, both sums kept inside the transform (float32 plans) ----------
     def _host_sk(self, m: _Mode, iq, k: int, hop: Optional[int], out: str, scale: float, what: str = ""):
         planes = self._host_integrated(m, iq, hop, _Integ(k, "mean", out, scale, True), what=what)
@@ -1007,6 +1059,11 @@ class SpectrumPlan:
         ``float32(I) + 1j*float32(Q)``, from half the input bytes."""
         return self._host_sk(_CI16, iq, k, hop, out, scale, "spectral_kurtosis_ci16")
 
+    def spectral_kurtosis_ci8(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``spectral_kurtosis`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 (ci8) or uint8 (cu8):
+        bit-identical to it on ``iq8_to_c64(iq)``, from a quarter of the input bytes."""
+        return self._host_sk(_CI8, iq, k, hop, out, scale, "spectral_kurtosis_ci8")
+
     def pfb_spectral_kurtosis(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
         """``spectral_kurtosis`` of the polyphase-filter-bank frames of ``pfb_db`` (``set_pfb`` first; rectangular float32
         plans): fold and transform per frame, the sums down the columns of the staged spectra at every nfft."""
@@ -1017,12 +1074,17 @@ class SpectrumPlan:
         widened samples."""
         return self._host_sk(_PFB_CI16, iq, k, hop, out, scale)
 
+    def pfb_spectral_kurtosis_ci8(self, iq, k: int, hop: Optional[int] = None, out: str = "db", scale: float = 1.0):
+        """``pfb_spectral_kurtosis`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 or uint8: the same bits as
+        on ``iq8_to_c64(iq)``."""
+        return self._host_sk(_PFB_CI8, iq, k, hop, out, scale)
+
     def _exec_device_sk(self, m: _Mode, what: str, d_iq: int, n_groups: int, k: int, d_out: int, frame_stride, out: str,
-                        scale: float, stream: int = 0, launches: Optional[int] = None):
+                        scale: float, stream: int = 0, launches: Optional[int] = None, fmt: Optional[int] = None):
         i = _Integ(k, "mean", out, scale, True)
         if launches is None:
-            return self._exec_device(m, d_iq, n_groups, d_out, frame_stride, stream, i, what=what)
-        return self._exec_device_timed_each(m, d_iq, n_groups, d_out, launches, frame_stride, i, what=what)
+            return self._exec_device(m, d_iq, n_groups, d_out, frame_stride, stream, i, what=what, fmt=fmt)
+        return self._exec_device_timed_each(m, d_iq, n_groups, d_out, launches, frame_stride, i, what=what, fmt=fmt)
 
     def exec_device_sk(self, d_iq: int, n_groups: int, k: int, d_out: int, *, frame_stride: Optional[int] = None,
                        out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
@@ -1067,6 +1129,33 @@ class SpectrumPlan:
                                            frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0) -> list:
         """``exec_device_pfb_sk_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
         return self._exec_device_sk(_PFB_CI16, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, launches=launches)
+
+    def exec_device_sk_ci8(self, d_iq: int, n_groups: int, k: int, d_out: int, *, unsigned: bool = False,
+                           frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_sk`` from 8-bit I,Q (2 bytes per sample; ``unsigned``: cu8, else ci8; frame starts 2-byte aligned)."""
+        self._exec_device_sk(_CI8, "spectral_kurtosis_ci8", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream,
+                             fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_sk_ci8_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                      unsigned: bool = False, frame_stride: Optional[int] = None, out: str = "db",
+                                      scale: float = 1.0) -> list:
+        """``exec_device_sk_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_CI8, "spectral_kurtosis_ci8", d_iq, n_groups, k, d_out, frame_stride, out, scale,
+                                    launches=launches, fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_pfb_sk_ci8(self, d_iq: int, n_groups: int, k: int, d_out: int, *, unsigned: bool = False,
+                               frame_stride: Optional[int] = None, out: str = "db", scale: float = 1.0,
+                               stream: int = 0) -> None:
+        """``exec_device_pfb_sk`` from the raw 8-bit I,Q stream (2 bytes per sample; ``unsigned``: cu8, else ci8)."""
+        self._exec_device_sk(_PFB_CI8, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, stream,
+                             fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    def exec_device_pfb_sk_ci8_timed_each(self, d_iq: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                          unsigned: bool = False, frame_stride: Optional[int] = None, out: str = "db",
+                                          scale: float = 1.0) -> list:
+        """``exec_device_pfb_sk_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_sk(_PFB_CI8, "", d_iq, n_groups, k, d_out, frame_stride, out, scale, launches=launches,
+                                    fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
 
     # -- two-channel cross-spectra: auto and cross power per k frames, four sums kept inside the transform (float32 plans) --
     def _host_xspec(self, x: np.ndarray, ci16: bool, k: int, hop: Optional[int], scale: float, what: str) -> CrossSpectrum:
@@ -1856,7 +1945,7 @@ def _cached_pfb_plan(nfft: int, taps: int, prototype, eps: float, shift: bool, d
 
 def _pfb_integrated_db(m: _Mode, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device) -> np.ndarray:
     """The arguments are checked before a plan is made for the prototype."""
-    x = m.stream(iq) if m.ci16 else iq
+    x = m.stream(iq) if m.ci16 or m.iq8 else iq
     if int(k) < 1:
         raise ValueError("k must be >= 1")
     if hop is not None and int(hop) < 1:
@@ -1897,6 +1986,21 @@ def pfb_integrated_db_ci16(iq, nfft: int, taps: int, k: int, hop: Optional[int] 
     return _pfb_integrated_db(_PFB_CI16, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device)
 
 
+def pfb_db_ci8(iq, nfft: int, taps: int, hop: Optional[int] = None, prototype=None, *, eps: float = 1e-12,
+               shift: bool = True, device: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``pfb_db`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 (ci8) or uint8 (cu8): the same rows, bit for
+    bit, as on ``iq8_to_c64(iq)``, from a quarter of the input bytes; prototype and plan cache as for ``pfb_db``."""
+    x = _as_ci8(iq, stream=True)
+    return _cached_pfb_plan(int(nfft), int(taps), prototype, eps, shift, device).pfb_db_ci8(x, hop, out=out)
+
+
+def pfb_integrated_db_ci8(iq, nfft: int, taps: int, k: int, hop: Optional[int] = None, detector: str = "mean",
+                          prototype=None, *, eps: float = 1e-12, shift: bool = True, device: int = 0) -> np.ndarray:
+    """``pfb_integrated_db`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 or uint8: the same rows, bit for
+    bit, as on ``iq8_to_c64(iq)``, from a quarter of the input bytes."""
+    return _pfb_integrated_db(_PFB_CI8, iq, nfft, taps, k, hop, detector, prototype, eps, shift, device)
+
+
 def sk_limits(k: int, sigmas: float = 3.0):
     """``(lo, hi) = 1 -/+ sigmas * sqrt(4k^2 / ((k-1)(k+2)(k+3)))``: the band around 1 in which the spectral kurtosis of
     Gaussian noise over ``k`` frames lies (its standard deviation, Nita & Gary); bins outside are flagged as interference."""
@@ -1921,13 +2025,22 @@ def spectral_kurtosis_ci16(iq, nfft: int, k: int, hop: Optional[int] = None, win
     return _cached_plan(int(nfft), window, eps, shift, device).spectral_kurtosis_ci16(x, k, hop, out, scale)
 
 
+def spectral_kurtosis_ci8(iq, nfft: int, k: int, hop: Optional[int] = None, window: WindowArg = None, *, out: str = "db",
+                          scale: float = 1.0, eps: float = 1e-12, shift: bool = True, device: int = 0):
+    """``spectral_kurtosis`` over one contiguous 8-bit I,Q stream ``(n_samples, 2)`` int8 (ci8) or uint8 (cu8): the same bits
+    as on ``iq8_to_c64(iq)``."""
+    x = _as_ci8(iq, stream=True)
+    return _cached_plan(int(nfft), window, eps, shift, device).spectral_kurtosis_ci8(x, k, hop, out, scale)
+
+
 def pfb_spectral_kurtosis(iq, nfft: int, taps: int, k: int, hop: Optional[int] = None, prototype=None, *, out: str = "db",
                           scale: float = 1.0, eps: float = 1e-12, shift: bool = True, device: int = 0):
-    """``spectral_kurtosis`` of the polyphase-filter-bank frames of ``pfb_db`` (complex64, or int16 I,Q ``(n_samples, 2)``);
-    prototype and plan cache as for ``pfb_db``.  The arguments are checked before a plan is made for the prototype."""
-    ci16 = isinstance(iq, np.ndarray) and iq.dtype == np.int16
-    m = _PFB_CI16 if ci16 else _PFB
-    x = m.stream(iq) if ci16 else iq
+    """``spectral_kurtosis`` of the polyphase-filter-bank frames of ``pfb_db`` (complex64, or ``(n_samples, 2)`` int16 I,Q or
+    int8 / uint8 I,Q); prototype and plan cache as for ``pfb_db``.  The arguments are checked before a plan is made for the
+    prototype."""
+    dt = iq.dtype if isinstance(iq, np.ndarray) else None
+    m = _PFB_CI16 if dt == np.int16 else _PFB_CI8 if dt in (np.int8, np.uint8) else _PFB
+    x = iq if m is _PFB else m.stream(iq)
     if int(k) < 2:
         raise ValueError("k must be >= 2")
     if hop is not None and int(hop) < 1:
