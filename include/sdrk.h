@@ -582,7 +582,8 @@ int sdrk_exec_host_pfb_kurtosis_iq8(sdrk_plan* plan, const void* iq8, int iq8_fo
  * element through device memory from complex64, 8 + 16/K from int16.  Other lengths de-interleave chunks of frames, run the
  * plan's transform once per channel and reduce both spectra, in plan-owned staging of at most 64 MiB of spectra and 64 MiB of
  * split samples however long the stream is.
- * Not provided: filter-bank forms, double precision, more than two channels, waterfall appends. */
+ * Not provided: filter-bank forms, double precision, waterfall appends; more than two channels and 8-bit elements are the
+ * correlation-matrix calls' (sdrk_exec_*_corrmat*, the next section). */
 /* device in / device out (d_out: n_groups * 4 * nfft float32), asynchronous on `stream` (NULL: the plan's stream) */
 int sdrk_exec_device_xspec(sdrk_plan* plan, const void* d_iq2_c64, size_t n_groups, size_t k_frames, size_t frame_stride,
                            float scale, float* d_out, void* stream);
@@ -599,6 +600,69 @@ int sdrk_exec_device_xspec_ci16_timed_each(sdrk_plan* plan, const void* d_iq2_ci
                                            size_t frame_stride, float scale, float* d_out, int launches, float* each_ms);
 int sdrk_exec_host_xspec_ci16(sdrk_plan* plan, const void* iq2_ci16, size_t n_groups, size_t k_frames, size_t frame_stride,
                               float scale, float* out);
+
+/* ---- correlation matrix: 2..8 coherent channels per bin over K frames ----------------------
+ * What direction finding and interference nulling start from: the C x C cross-spectral matrix per bin,
+ * R[i][j] = <X_i * conj(X_j)> over K frames, for the four-channel transceiver boards and the five-dongle arrays on one clock
+ * that a two-channel call does not reach.  Every channel is transformed ONCE per frame (the F-X split of a correlator), where
+ * C(C-1)/2 two-channel calls transform each C - 1 times.
+ * Input: a stream of ELEMENTS.  Element n holds sample n of channel 0, then of channel 1, ... up to channel C - 1, for
+ * `channels` = C in 2..8 — what SigMF stores for core:num_channels = C.  complex64 form: 8*C bytes per element.  int16 form
+ * (_ci16): 4*C bytes, widened as the int16 calls do.  8-bit form (_iq8): 2*C bytes, `iq8_format` (SDRK_IQ8_SIGNED /
+ * SDRK_IQ8_UNSIGNED) right after the samples pointer, widened exactly as the package's iq8_to_c64 and the other 8-bit modes do (cu8:
+ * float32(byte) - 127.5).  The pointer is aligned to one sample of one channel — 8, 4 or 2 bytes — NOT to an element: C = 3
+ * or 5 make elements of 24, 12, 6 and 40, 20, 10 bytes.  Frame f starts at ELEMENT f*frame_stride (any stride >= 1) and covers
+ * nfft elements; group g is the frames [g*k_frames, (g+1)*k_frames); the buffer holds
+ * (n_groups*k_frames - 1)*frame_stride + nfft elements.
+ * Sums: X_c,f is the plan's transform of channel c of frame f (the plan's window, twiddles and shift order; the bits of the
+ * plan's own complex spectrum of the de-interleaved channel).  Per bin the C auto sums S_cc of fmaf(r, r, i*i), and for every
+ * pair i < j the sums Sre_ij + i*Sim_ij of X_i * conj(X_j) with every product rounded to float32 on its own — the expressions
+ * of the two-channel section above, written once in the library.  Plain float32 running sums in frame order, no floating-point
+ * atomics.  A group cut into slices has its slices' sums added in slice order in float64 and rounded to float32 once; the cut
+ * is the one the two-channel call makes for the same plan, n_groups and k_frames.
+ * Output: per group C*C planes of nfft float32, d_out[n_groups][C*C][nfft], in the plan's shift order: planes 0..C-1 are
+ * scale*S_cc/K; after them, for the pairs (0,1), (0,2), ..., (0,C-1), (1,2), ..., (C-2,C-1) in that order, two planes each:
+ * scale*Sre_ij/K, then scale*Sim_ij/K.  For C = 2 this is the two-channel layout.  There is no dB form; the plan's eps is
+ * not used; k_frames = 1 is allowed; a prototype set with sdrk_plan_set_pfb is ignored.
+ * Identities, as bit equalities: C = 2 returns what sdrk_exec_*_xspec returns for the same buffer; for any C and pair i < j the
+ * planes (i, j, re_ij, im_ij) are the two-channel call's on the stream built from channels i and j; the int16 and 8-bit forms
+ * return what the complex64 form returns for the widened elements; the host entry equals the device entry however it is
+ * chunked; permuting the channels permutes the planes, im negated (as a value) where a pair's order flips.
+ * Every float32 plan is served at every nfft, chirp-z lengths included.  N = 4096 reads the channels of a frame straight from
+ * the element stream, one workgroup per frame, and writes their spectra to staging (complex64 above 5 channels de-interleaves
+ * first: that measured faster); other lengths de-interleave chunks of frames and run the plan's transform once per channel.  A column kernel with the C*C sums of a bin in one thread's registers
+ * reduces the staged spectra.  Staging is plan-owned and bounded however long the stream is: at most 64 MiB of spectra and
+ * 64 MiB of split frames, or one frame of all C channels where that is larger.
+ * Refusals, each SDRK_ERR_INVALID with a message: channels outside 2..8, an f64 plan, n_groups = 0 or k_frames = 0 or their
+ * product out of range, frame_stride = 0, an element count or its byte size out of range, NULL pointers, an iq8_format that is
+ * neither.  A plan that has refused still works.
+ * Not provided: a filter-bank front end, double precision, waterfall appends, more than 8 channels, and direction-finding
+ * estimators (MUSIC, Capon, ...: numpy on the matrix). */
+/* device in / device out (d_out: n_groups * channels * channels * nfft float32), asynchronous on `stream` (NULL: the plan's) */
+int sdrk_exec_device_corrmat(sdrk_plan* plan, const void* d_iq_c64, int channels, size_t n_groups, size_t k_frames,
+                             size_t frame_stride, float scale, float* d_out, void* stream);
+/* the same, timed on the plan's stream: the milliseconds of each of `launches` calls (bench harness) */
+int sdrk_exec_device_corrmat_timed_each(sdrk_plan* plan, const void* d_iq_c64, int channels, size_t n_groups, size_t k_frames,
+                                        size_t frame_stride, float scale, float* d_out, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays), chunked at element boundaries through pinned staging */
+int sdrk_exec_host_corrmat(sdrk_plan* plan, const void* iq_c64, int channels, size_t n_groups, size_t k_frames,
+                           size_t frame_stride, float scale, float* out);
+/* the same three from int16 elements (4 * channels bytes per element) */
+int sdrk_exec_device_corrmat_ci16(sdrk_plan* plan, const void* d_iq_ci16, int channels, size_t n_groups, size_t k_frames,
+                                  size_t frame_stride, float scale, float* d_out, void* stream);
+int sdrk_exec_device_corrmat_ci16_timed_each(sdrk_plan* plan, const void* d_iq_ci16, int channels, size_t n_groups,
+                                             size_t k_frames, size_t frame_stride, float scale, float* d_out, int launches,
+                                             float* each_ms);
+int sdrk_exec_host_corrmat_ci16(sdrk_plan* plan, const void* iq_ci16, int channels, size_t n_groups, size_t k_frames,
+                                size_t frame_stride, float scale, float* out);
+/* the same three from 8-bit elements (2 * channels bytes per element) */
+int sdrk_exec_device_corrmat_iq8(sdrk_plan* plan, const void* d_iq8, int iq8_format, int channels, size_t n_groups,
+                                 size_t k_frames, size_t frame_stride, float scale, float* d_out, void* stream);
+int sdrk_exec_device_corrmat_iq8_timed_each(sdrk_plan* plan, const void* d_iq8, int iq8_format, int channels, size_t n_groups,
+                                            size_t k_frames, size_t frame_stride, float scale, float* d_out, int launches,
+                                            float* each_ms);
+int sdrk_exec_host_corrmat_iq8(sdrk_plan* plan, const void* iq8, int iq8_format, int channels, size_t n_groups, size_t k_frames,
+                               size_t frame_stride, float scale, float* out);
 
 /* ---- FIR filtering and channel extraction: tune, filter, decimate in one pass --------------
  * The way back from a spectrum to samples: tune to a channel seen in the waterfall, band-limit it, lower the rate, and hand the

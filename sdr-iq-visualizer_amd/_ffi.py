@@ -208,6 +208,16 @@ SYMBOLS = [
     ("sdrk_exec_device_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
     ("sdrk_exec_device_xspec_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_xspec_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
+    # correlation matrix of 2..8 channels: per group channels^2 planes (channels after the samples; iq8: after the format)
+    ("sdrk_exec_device_corrmat", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_corrmat_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_corrmat", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
+    ("sdrk_exec_device_corrmat_ci16", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_corrmat_ci16_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_corrmat_ci16", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
+    ("sdrk_exec_device_corrmat_iq8", c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_void_p]),
+    ("sdrk_exec_device_corrmat_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_corrmat_iq8", c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_size_t, c_float, c_void_p]),
     # FIR filtering and channel extraction: overlap-save in blocks of 4096, tune + filter + decimate (nfft = 4096 plans)
     ("sdrk_plan_set_fir", c_int, [c_void_p, c_int, c_void_p]),
     ("sdrk_plan_fir_taps", c_int, [c_void_p]),

@@ -1,6 +1,6 @@
 """Offline PSD of a SigMF recording on the GPU (BASELINE.json config 1).
 
-    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross]] [--pfb T] [--out rows.npz]
+    python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross] [--correlate]] [--pfb T] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F [F ...] --decim D [--exact] [--taps M] --out BASE
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
@@ -113,6 +113,11 @@ def main(argv=None) -> int:
                         "the auto and cross power of the two channels per K frames (arrays cross_paa, cross_pbb, cross, coherence, "
                         "phase); the report has the peak-coherence bin, its phase and the median coherence.  The other rows are "
                         "then channel 0's")
+    p.add_argument("--correlate", action="store_true",
+                   help="with --integrate K, on a recording of 2..8 channels (core:num_channels; cf32_le, ci16_le, ci8 or cu8): "
+                        "also write the correlation matrix of the channels per K frames (array corr_planes: channels^2 planes per "
+                        "row, spectrum.plane_index); the report has per pair the peak-coherence bin, its phase and the median "
+                        "coherence.  The other rows are then channel 0's")
     p.add_argument("--pfb", type=_positive, default=0, metavar="T",
                    help="also write polyphase-filter-bank dB rows: T blocks of --nfft samples folded under the default "
                         "prototype (spectrum.pfb_prototype), one row per --nfft samples (pfb_db); with --integrate K also one "
@@ -144,6 +149,8 @@ def main(argv=None) -> int:
         ap.error("--sk needs --integrate K with K >= 2")
     if args.cmd == "psd" and args.cross and args.integrate < 1:
         ap.error("--cross needs --integrate K")
+    if args.cmd == "psd" and args.correlate and args.integrate < 1:
+        ap.error("--correlate needs --integrate K")
 
     from . import sigmf_io, synth
     if args.cmd == "synth":
@@ -172,6 +179,16 @@ def main(argv=None) -> int:
             return 2
         pair, _ = sigmf_io.read_sigmf_channels(args.path)
         samples = np.ascontiguousarray(pair[:, 0])
+    multi = None
+    if args.correlate:   # every channel as stored (element n: sample n of channel 0, 1, ...); the rest: channel 0
+        g = meta.get("global", {})
+        nch, dt = int(g.get("core:num_channels", 1)), g.get("core:datatype", "cf32_le")
+        if not 2 <= nch <= 8 or dt not in ("cf32_le", "ci16_le", "ci8", "cu8") or args.path.endswith(".zip"):
+            print(f"--correlate needs a recording of 2..8 channels in cf32_le, ci16_le, ci8 or cu8 (core:num_channels, not "
+                  f"zipped); this one has core:num_channels = {nch}, core:datatype = {dt!r}", file=sys.stderr)
+            return 2
+        multi, _ = sigmf_io.read_sigmf_channels(args.path)
+        samples = np.ascontiguousarray(multi[:, 0])
     raw16 = samples if samples.dtype == np.int16 else None
     raw8 = np.ascontiguousarray(samples) if samples.dtype in (np.int8, np.uint8) else None
     if raw8 is not None:
@@ -275,6 +292,24 @@ def main(argv=None) -> int:
             report["cross_median_coherence"] = float(np.median(coh))
         else:
             print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no cross-spectrum row", file=sys.stderr)
+    if multi is not None:
+        plan = spectrum._cached_plan(args.nfft, args.window, 1e-12, True, args.device)
+        multi = np.ascontiguousarray(multi)
+        cm = (plan.correlate_ci16 if multi.dtype == np.int16 else plan.correlate_ci8 if multi.dtype in (np.int8, np.uint8)
+              else plan.correlate)(multi, args.integrate)
+        results["corr_planes"] = cm.planes
+        report["corr_channels"] = cm.channels
+        report["corr_rows"] = int(cm.planes.shape[0])
+        report["corr_pairs"] = []
+        if cm.planes.shape[0] == 0:
+            print(f"recording holds fewer than {args.integrate} frames of {args.nfft} samples: no correlation row", file=sys.stderr)
+        for i in range(cm.channels if cm.planes.shape[0] else 0):
+            for j in range(i + 1, cm.channels):
+                coh, phase = cm.coherence(i, j), cm.phase(i, j)
+                g, b = np.unravel_index(int(np.argmax(coh)), coh.shape)
+                report["corr_pairs"].append({"pair": [i, j], "peak_coherence": float(coh[g, b]), "peak_row": int(g),
+                                             "peak_freq_hz": float(freqs[b]), "peak_phase_rad": float(phase[g, b]),
+                                             "median_coherence": float(np.median(coh))})
     if args.out:
         np.savez_compressed(args.out, **results)
         report["out"] = args.out

@@ -27,6 +27,12 @@
 // group four planes from four sums per bin.  N = 4096 transforms both channels inside one kernel (xspec4096.hip); every other
 // length de-interleaves, runs the plan's transform once per channel and reduces both staged spectra (xspec_rows.hip).  The
 // interleaved layout is what lets the chunking of exec_host_integrated serve as it is: a chunk of elements holds both channels.
+//
+// The correlation-matrix entry points (sdrk_exec_*_corrmat, _corrmat_ci16, _corrmat_iq8) carry that to `channels` = 2..8 samples
+// per element (complex64, int16 or 8-bit; aligned to a sample) with the kernels of kernels_corrmat.h behind it: per group
+// channels^2 planes from as many sums per bin.  Every route is staged: N = 4096 writes the channels' spectra from the element
+// stream itself (corrmat4096.hip; complex64 above 5 channels de-interleaves first, which measured faster), every other length
+// de-interleaves and runs the plan's transform once per channel, and corrmat_rows.hip reduces the staged spectra.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -105,6 +111,45 @@ IntIo xspec_io(size_t in_elem, FusedFn fused) {
 
 IntIo xspec_c64_io() { return xspec_io(2 * sizeof(float2), sdrk::launch_xspec4096); }
 IntIo xspec_ci16_io() { return xspec_io(8, sdrk::launch_xspec4096_i16); }
+
+// correlation matrix of `channels` channels (checked by the caller) from samples of format fmt (a sdrk::CmFormat): always
+// through staged spectra, the plan's plain complex64 transform at the lengths without a reading kernel
+IntIo corrmat_io(int channels, int fmt) {
+    const size_t c = (size_t)channels;
+    IntIo io = int_io(c * sdrk::cm_sample_bytes(fmt), nullptr, launch_f32);
+    io.rows = nullptr;
+    io.finalize = nullptr;
+    io.planes = c * c;
+    io.state = c * c;
+    io.channels = channels;
+    io.fmt = fmt;
+    return io;
+}
+
+int cm_format_of_iq8(int iq8_format) { return iq8_format == SDRK_IQ8_SIGNED ? sdrk::CM_B8_SIGNED : sdrk::CM_B8_UNSIGNED; }
+
+// What the correlation-matrix entry points refuse before the shared checks: a channel count outside 2..8; and behind them
+// (the plan, the counts and the stride are sound by then) a stream whose element count or byte size does not fit a size_t.
+int check_corrmat_channels(int channels) {
+    if (channels < sdrk::CM_MIN_CHANNELS || channels > sdrk::CM_MAX_CHANNELS)
+        return fail(SDRK_ERR_INVALID, "channels = %d is outside %d..%d", channels, sdrk::CM_MIN_CHANNELS, sdrk::CM_MAX_CHANNELS);
+    return SDRK_OK;
+}
+
+int check_corrmat_extent(const IntIo& io, const sdrk_plan* p, size_t n_groups, size_t k, size_t stride) {
+    const size_t max = ~(size_t)0 >> 1, last = n_groups * k - 1, nfft = (size_t)p->nfft;
+    if (last != 0 && stride > (max - nfft) / last)
+        return fail(SDRK_ERR_INVALID, "(n_groups * k_frames - 1) * frame_stride + nfft elements is out of range");
+    const size_t elems = last * stride + nfft;
+    if (elems > max / io.in_elem || n_groups > max / (io.planes * nfft * sizeof(float)))
+        return fail(SDRK_ERR_INVALID, "%zu elements of %zu bytes, or the output, are out of range", elems, io.in_elem);
+    return SDRK_OK;
+}
+
+int check_corrmat(const IntIo& io, const sdrk_plan* p, const void* in, size_t n_groups, size_t k, size_t stride, const void* out) {
+    int st = check_call_args(io, p, in, n_groups, k, stride, SDRK_DET_MEAN, SDRK_INT_OUT_POWER, out);
+    return st == SDRK_OK ? check_corrmat_extent(io, p, n_groups, k, stride) : st;
+}
 
 }  // namespace
 
@@ -310,5 +355,49 @@ SDRK_KURTOSIS_IQ8_ENTRIES(pfb_kurtosis_iq8, sk_pfb_iq8_io(p, iq8_format), SDRK_P
 SDRK_XSPEC_ENTRIES(xspec, xspec_c64_io())
 SDRK_XSPEC_ENTRIES(xspec_ci16, xspec_ci16_io())
 #undef SDRK_XSPEC_ENTRIES
+
+// ---- correlation matrix of 2..8 channels: channels * channels planes per group, always the scaled-power form ----
+// (FMT_ARG: nothing, or the 8-bit format right after the samples; READY: its refusal; FMT: the sdrk::CmFormat)
+
+#define SDRK_CORRMAT_ENTRIES(SUFFIX, FMT_ARG, READY, FMT)                                                                          \
+    int sdrk_exec_device_##SUFFIX(sdrk_plan* p, const void* d_iq FMT_ARG, int channels, size_t n_groups, size_t k_frames,         \
+                                  size_t frame_stride, float scale, float* d_out, void* stream) {                                \
+        READY;                                                                                                                    \
+        if (int st = check_corrmat_channels(channels); st != SDRK_OK) return st;                                                  \
+        const IntIo io = corrmat_io(channels, FMT);                                                                               \
+        if (int st = check_corrmat(io, p, d_iq, n_groups, k_frames, frame_stride, d_out); st != SDRK_OK) return st;               \
+        return exec_device_integrated(io, p, d_iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, SDRK_INT_OUT_POWER, scale,    \
+                                      d_out, stream);                                                                             \
+    }                                                                                                                             \
+    int sdrk_exec_device_##SUFFIX##_timed_each(sdrk_plan* p, const void* d_iq FMT_ARG, int channels, size_t n_groups,             \
+                                               size_t k_frames, size_t frame_stride, float scale, float* d_out, int launches,    \
+                                               float* each_ms) {                                                                  \
+        READY;                                                                                                                    \
+        if (int st = check_corrmat_channels(channels); st != SDRK_OK) return st;                                                  \
+        const IntIo io = corrmat_io(channels, FMT);                                                                               \
+        if (int st = check_corrmat(io, p, d_iq, n_groups, k_frames, frame_stride, d_out); st != SDRK_OK) return st;               \
+        return exec_device_integrated_timed_each(io, p, d_iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN,                    \
+                                                 SDRK_INT_OUT_POWER, scale, d_out, launches, each_ms);                            \
+    }                                                                                                                             \
+    int sdrk_exec_host_##SUFFIX(sdrk_plan* p, const void* iq FMT_ARG, int channels, size_t n_groups, size_t k_frames,             \
+                                size_t frame_stride, float scale, float* out) {                                                  \
+        READY;                                                                                                                    \
+        if (int st = check_corrmat_channels(channels); st != SDRK_OK) return st;                                                  \
+        const IntIo io = corrmat_io(channels, FMT);                                                                               \
+        if (int st = check_corrmat(io, p, iq, n_groups, k_frames, frame_stride, out); st != SDRK_OK) return st;                   \
+        return exec_host_integrated(io, p, iq, n_groups, k_frames, frame_stride, SDRK_DET_MEAN, SDRK_INT_OUT_POWER, scale, out); \
+    }
+#define SDRK_NO_ARG
+#define SDRK_IQ8_ARG , int iq8_format
+#define SDRK_IQ8_READY                                                                                                            \
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st
+
+SDRK_CORRMAT_ENTRIES(corrmat, SDRK_NO_ARG, (void)0, sdrk::CM_C64)
+SDRK_CORRMAT_ENTRIES(corrmat_ci16, SDRK_NO_ARG, (void)0, sdrk::CM_S16)
+SDRK_CORRMAT_ENTRIES(corrmat_iq8, SDRK_IQ8_ARG, SDRK_IQ8_READY, cm_format_of_iq8(iq8_format))
+#undef SDRK_IQ8_READY
+#undef SDRK_IQ8_ARG
+#undef SDRK_NO_ARG
+#undef SDRK_CORRMAT_ENTRIES
 
 }  // extern "C"

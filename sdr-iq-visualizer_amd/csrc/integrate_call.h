@@ -7,6 +7,9 @@
 // The two-channel cross-spectrum calls (sdrk_exec_*_xspec*) are the same call once more: their input is a stream of elements
 // (both channels' sample n side by side), their unit state is four floats per bin, and their staged route de-interleaves a chunk
 // of frames (kernels_xspec.h) and runs the plan's transform once per channel before the column kernel takes both spectra.
+// The correlation-matrix calls (sdrk_exec_*_corrmat*) carry that to C = 2..8 channels per element: C * C floats of unit state
+// and as many planes, C spectra per frame in staging — written by corrmat4096.hip straight from the element stream at N = 4096,
+// by the split and the plan's transform elsewhere — and the column kernel of corrmat_rows.hip over them (kernels_corrmat.h).
 //
 // N = 4096 runs the fused kernel on the caller's samples: one launch, plus a finalize when the groups are too few to fill the
 // device and were cut into slices (integrate_split.h).  Every other length (chirp-z included) runs "the plan's own transform
@@ -18,6 +21,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+#include <cstring>
+
+#include "kernels_corrmat.h"
 #include "kernels_integrate.h"
 #include "kernels_xspec.h"
 #include "plan_internal.h"
@@ -43,6 +50,13 @@ struct IntIo {
     // staged route then splits each chunk's frames into packed complex64 frames per channel first, at most INT_STAGE_BYTES of
     // them beside at most INT_STAGE_BYTES of spectra, and `rows` is not used
     hipError_t (*rows2)(const sdrk::IntegrateArgs&, const float2*) = nullptr;
+    // C-channel element input (the correlation matrix; in_elem = channels * bytes of a sample of format `fmt`, a sdrk::CmFormat):
+    // state and planes are channels * channels, every route is staged — channels spectra per frame share the INT_STAGE_BYTES (one
+    // frame of all channels where that is more), N = 4096 fills them with launch_corrmat4096_spectra from the caller's elements,
+    // every other length splits into as much again and runs `transform` per channel — and launch_corrmat_rows /
+    // launch_corrmat_finalize stand where rows / rows2 / finalize do, which are not used
+    int channels = 0;
+    int fmt = 0;
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -55,6 +69,7 @@ struct IntCall {
     float scale = 1.0f;
     sdrk::IntSplit sp{1, 1};
     bool fused = false;          // the N = 4096 kernel of io.fused
+    bool direct = false;         // io.channels at N = 4096: the spectra kernel that reads the element stream itself
     size_t group_floats = 0;     // float32 per output group: io.planes * nfft
     size_t stage_frames = 0;     // generic route: frames per staging chunk
     unsigned launches = 0;       // reduction launches so far: picks the carry rows
@@ -100,10 +115,20 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
     c.scale = scale;
     c.stream = stream;
     const size_t nfft = (size_t)p->nfft;
-    c.fused = p->nfft == 4096 && !p->blu_inner && io.fused != nullptr;
+    const bool f4k = p->nfft == 4096 && !p->blu_inner;
+    c.fused = f4k && io.fused != nullptr;
+    // N = 4096 with channels: the spectra kernel that reads the elements itself, except where the split route measured faster
+    // (cm4k_reads_directly, kernels_corrmat.h).  SDRK_CORRMAT_ROUTE=split / =direct picks one for tools/bench_corrmat.py, which
+    // measures both; the bits are the same either way.
+    const char* const route = io.channels ? std::getenv("SDRK_CORRMAT_ROUTE") : nullptr;
+    c.direct = f4k && io.channels &&
+               (route && std::strcmp(route, "split") == 0    ? false
+                : route && std::strcmp(route, "direct") == 0 ? true
+                                                             : sdrk::cm4k_reads_directly(io.fmt, io.channels));
     c.group_floats = io.planes * nfft;
-    // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel
-    const size_t ways = c.fused ? 1 : (nfft + 255) / 256;
+    // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel.  The C-channel
+    // calls make the two-channel call's cut at every length, so that a pair's planes are that call's bits.
+    const size_t ways = c.fused || (f4k && io.channels) ? 1 : (nfft + 255) / 256;
     c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
     const size_t row = nfft * sizeof(float2);              // a staged spectrum
     const size_t state_row = nfft * io.state * sizeof(float);
@@ -113,15 +138,19 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
     if (st != SDRK_OK) return st;
     if (!c.fused) {
         // (two channels: both spectra of a frame share the 64 MiB, and the split frames take as much again behind them)
-        const size_t per_frame = io.rows2 ? 2 * row : row;
+        const size_t chans = io.channels ? (size_t)io.channels : io.rows2 ? 2 : 1;
+        const size_t per_frame = chans * row;
         c.stage_frames = INT_STAGE_BYTES / per_frame ? INT_STAGE_BYTES / per_frame : 1;
         if (c.stage_frames > n_groups * k) c.stage_frames = n_groups * k;
-        st = sg.reserve(1, c.stage_frames * (io.rows2 ? 4 * row : row));
+        // (element input: the split frames behind the spectra, unless the spectra kernel reads the elements itself)
+        st = sg.reserve(1, c.stage_frames * per_frame * (chans > 1 && !c.direct ? 2 : 1));
         if (st != SDRK_OK) return st;
     }
     c.carry[0] = static_cast<float2*>(sg.buf[0].d);
-    c.carry[1] = c.carry[0] + nfft * io.state / 2;
-    c.partials = c.carry[1] + nfft * io.state / 2;
+    // (rows of nfft * state floats: counted in floats, an odd nfft times an odd state is no whole number of float2)
+    float* const rows = static_cast<float*>(sg.buf[0].d);
+    c.carry[1] = reinterpret_cast<float2*>(rows + nfft * io.state);
+    c.partials = reinterpret_cast<float2*>(rows + 2 * nfft * io.state);
     return sg.enter(stream);   // one state and one staging per plan: a call on another stream waits for the last one's work
 }
 
@@ -174,6 +203,26 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
             a.d_in = spec0;
             a.in_stride = (size_t)p->nfft;
             e = c.io.rows2(a, spec1);
+        } else if (c.io.channels) {   // [spectra 0 .. C-1][frames 0 .. C-1 (split route)], stage_frames frames each
+            const size_t n = s1 - s0, plane = c.stage_frames * (size_t)p->nfft, chans = (size_t)c.io.channels;
+            float2* const spec = static_cast<float2*>(p->integ.buf[1].d);
+            if (c.direct) {
+                a.d_in = src;
+                a.in_stride = c.stride;
+                e = sdrk::launch_corrmat4096_spectra(a, c.io.fmt, c.io.channels, spec, plane);
+                if (e != hipSuccess) return fail(SDRK_ERR_HIP, "correlation-matrix spectra launch failed: %s", hipGetErrorString(e));
+            } else {
+                float2* const x = spec + chans * plane;
+                e = sdrk::launch_corrmat_split(src, c.io.fmt, c.io.channels, n, c.stride, p->nfft, x, plane, p->num_cus, c.stream);
+                if (e != hipSuccess) return fail(SDRK_ERR_HIP, "correlation-matrix split launch failed: %s", hipGetErrorString(e));
+                for (size_t ch = 0; ch < chans; ++ch) {
+                    int st = c.io.transform(p, x + ch * plane, n, (size_t)p->nfft, spec + ch * plane, sdrk::EPI_COMPLEX, c.stream);
+                    if (st != SDRK_OK) return st;
+                }
+            }
+            a.d_in = spec;
+            a.in_stride = (size_t)p->nfft;
+            e = sdrk::launch_corrmat_rows(a, c.io.channels, plane);
         } else {
             void* const d_stage = p->integ.buf[1].d;
             int st = c.io.transform(p, src, s1 - s0, c.stride, d_stage, sdrk::EPI_COMPLEX, c.stream);
@@ -190,8 +239,11 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
 // Split calls: every group's partial rows -> its row.
 inline int call_finalize(IntCall& c, float* d_out) {
     if (c.sp.slices == 1) return SDRK_OK;
-    const hipError_t e = c.io.finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector,
-                                     c.out_form, c.scale, c.p->eps, d_out, c.p->num_cus, c.stream);
+    const hipError_t e =
+        c.io.channels ? sdrk::launch_corrmat_finalize(reinterpret_cast<const float*>(c.partials), c.io.channels, c.n_groups, c.k,
+                                                      c.sp.slices, c.p->nfft, c.scale, d_out, c.p->num_cus, c.stream)
+                      : c.io.finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector, c.out_form, c.scale,
+                                      c.p->eps, d_out, c.p->num_cus, c.stream);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate finalize launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;
 }

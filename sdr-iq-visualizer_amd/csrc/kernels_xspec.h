@@ -38,15 +38,24 @@ struct XsState {
 // kernel and the host stand-in (tests/fake_xspec_kernels.cpp) all call it.  The build contracts within a statement
 // (-ffp-contract=on), so the four products of the cross term sit in statements of their own and are rounded to float32 before
 // they are added: swapping the channels then gives the exact conjugate, and two identical channels give im = 0 exactly.
-__host__ __device__ __forceinline__ void xs_accumulate(XsState& s, float ar, float ai, float br, float bi) {
-    const float paa = __builtin_fmaf(ar, ar, ai * ai);
-    const float pbb = __builtin_fmaf(br, br, bi * bi);
+// Its two terms stand on their own for the kernels that keep more than two channels (kernels_corrmat.h): xs_auto is |X|^2 of
+// one spectrum, xs_cross the two parts of A conj(B).
+__host__ __device__ __forceinline__ float xs_auto(float r, float i) { return __builtin_fmaf(r, r, i * i); }
+
+__host__ __device__ __forceinline__ void xs_cross(float ar, float ai, float br, float bi, float& cre, float& cim) {
     const float rr = ar * br;
     const float ii = ai * bi;
     const float ir = ai * br;
     const float ri = ar * bi;
-    const float cre = rr + ii;
-    const float cim = ir - ri;
+    cre = rr + ii;
+    cim = ir - ri;
+}
+
+__host__ __device__ __forceinline__ void xs_accumulate(XsState& s, float ar, float ai, float br, float bi) {
+    const float paa = xs_auto(ar, ai);
+    const float pbb = xs_auto(br, bi);
+    float cre, cim;
+    xs_cross(ar, ai, br, bi, cre, cim);
     s.aa += paa;
     s.bb += pbb;
     s.re += cre;

@@ -14,7 +14,8 @@ dependency here: the format is simple enough to read directly.  File I/O only â€
 signal processing in this module.
 
 Multi-channel recordings (``core:num_channels = C``, the channels' samples interleaved per sample instant, as a 2 x 2 front
-end delivers them): ``write_sigmf(..., num_channels=C)`` and ``read_sigmf_channels`` -> ``(n, C)``.  ``read_sigmf`` itself
+end delivers them): ``write_sigmf(..., num_channels=C)`` and ``read_sigmf_channels`` -> ``(n, C)`` (``(n, C, 2)`` for the
+integer formats, ci8 / cu8 included).  ``read_sigmf`` itself
 reads the data file as one stream whatever the channel count says.
 """
 from __future__ import annotations
@@ -98,8 +99,8 @@ def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float,
     """Write ``<base>.sigmf-data`` (cf32_le, or ci16_le on request: interleaved int16 I,Q from an int16 ``(n, 2)`` array or
     from integer-valued complex samples; or ci8 / cu8: interleaved bytes from an ``(n, 2)`` int8 / uint8 array or from complex
     samples the format holds exactly) and ``<base>.sigmf-meta``; returns both paths.
-    ``num_channels=C`` (> 1): ``samples`` is ``(n, C)`` complex (or ``(n, C, 2)`` int16), stored with the channels
-    interleaved per sample instant and ``core:num_channels = C`` in the metadata."""
+    ``num_channels=C`` (> 1): ``samples`` is ``(n, C)`` complex (or ``(n, C, 2)`` int16; for ci8 / cu8 ``(n, C, 2)`` int8 /
+    uint8, nothing else), stored with the channels interleaved per sample instant and ``core:num_channels = C`` in the metadata."""
     if datatype not in ("cf32_le", "ci16_le", "ci8", "cu8"):
         raise ValueError(f"write_sigmf writes 'cf32_le', 'ci16_le', 'ci8' or 'cu8', not {datatype!r}")
     num_channels = int(num_channels)
@@ -108,14 +109,16 @@ def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float,
     if num_channels > 1:
         shape = np.shape(samples)
         int16 = getattr(samples, "dtype", None) == np.int16
-        if len(shape) != (3 if int16 else 2) or shape[1] != num_channels:
+        if datatype in ("ci8", "cu8"):   # the bytes as they are: (n, C, 2) of the format's own dtype
+            if getattr(samples, "dtype", None) != _NATIVE[datatype] or len(shape) != 3 or shape[1:] != (num_channels, 2):
+                raise ValueError(f"datatype={datatype!r} with num_channels={num_channels} needs an (n, {num_channels}, 2) "
+                                 f"{np.dtype(_NATIVE[datatype]).name} array, got {getattr(samples, 'dtype', None)} of shape {shape}")
+        elif len(shape) != (3 if int16 else 2) or shape[1] != num_channels:
             raise ValueError(f"num_channels={num_channels} needs samples of shape (n, {num_channels})"
                              f"{' (or (n, C, 2) int16)' if int16 else ''}, got {shape}")
         meta_kw["num_channels"] = num_channels   # (C-order flattening below interleaves the channels)
     data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
     if datatype != "cf32_le":
-        if datatype != "ci16_le" and num_channels > 1:
-            raise ValueError(f"datatype={datatype!r} is written with one channel")
         (_to_ci16(samples) if datatype == "ci16_le" else _to_iq8(samples, datatype)).tofile(data_path)
         with open(meta_path, "w") as fh:
             json.dump(make_metadata(sample_rate, center_freq, datatype=datatype, **meta_kw), fh, indent=2)
@@ -199,7 +202,8 @@ def read_sigmf(path: str, max_samples: Optional[int] = None, native=False) -> Tu
 def read_sigmf_channels(path: str) -> Tuple[np.ndarray, dict]:
     """Read a recording (``.sigmf-meta``, ``.sigmf-data`` or base name) honouring ``core:num_channels = C`` (default 1):
     ``(samples, meta)`` with the samples in their own format and the channels de-interleaved by a reshape, not a copy â€”
-    ``(n, C)`` complex64 for ``cf32_le``, ``(n, C, 2)`` int16 for ``ci16_le``; a trailing partial sample instant is dropped.
+    ``(n, C)`` complex64 for ``cf32_le``, ``(n, C, 2)`` int16 for ``ci16_le``, ``(n, C, 2)`` int8 / uint8 for ``ci8`` /
+    ``cu8``; a trailing partial sample instant is dropped.
     ``meta`` as from ``read_sigmf``, plus ``meta['num_channels']``."""
     base = path
     for ext in (".sigmf-meta", ".sigmf-data"):
@@ -209,8 +213,8 @@ def read_sigmf_channels(path: str) -> Tuple[np.ndarray, dict]:
         meta = json.load(fh)
     g = meta.get("global", {})
     datatype, nch = g.get("core:datatype", "cf32_le"), int(g.get("core:num_channels", 1))
-    if datatype not in ("cf32_le", "ci16_le"):
-        raise ValueError(f"read_sigmf_channels reads 'cf32_le' or 'ci16_le', not {datatype!r}")
+    if datatype not in ("cf32_le", "ci16_le", "ci8", "cu8"):
+        raise ValueError(f"read_sigmf_channels reads 'cf32_le', 'ci16_le', 'ci8' or 'cu8', not {datatype!r}")
     if nch < 1:
         raise ValueError(f"core:num_channels is {nch}")
     per = nch if datatype == "cf32_le" else 2 * nch          # values of the file's dtype per sample instant
@@ -219,7 +223,7 @@ def read_sigmf_channels(path: str) -> Tuple[np.ndarray, dict]:
     if datatype == "cf32_le":
         samples = a.reshape(-1, nch).astype(np.complex64, copy=False)
     else:
-        samples = a.reshape(-1, nch, 2).astype(np.int16, copy=False)
+        samples = a.reshape(-1, nch, 2).astype(_NATIVE[datatype], copy=False)
     caps = meta.get("captures") or [{}]
     out = dict(meta)
     out["sample_rate"] = float(g.get("core:sample_rate", 1.0))

@@ -235,6 +235,105 @@ class CrossSpectrum(NamedTuple):
         return np.arctan2(self.cim.astype(np.float64), self.cre.astype(np.float64))
 
 
+CORRMAT_MIN_CHANNELS, CORRMAT_MAX_CHANNELS = 2, 8      # sdrk.h: channels of a correlation-matrix call
+
+
+def _corrmat_channels(c: int) -> int:
+    if not CORRMAT_MIN_CHANNELS <= int(c) <= CORRMAT_MAX_CHANNELS:
+        raise ValueError(f"a correlation matrix takes {CORRMAT_MIN_CHANNELS}..{CORRMAT_MAX_CHANNELS} channels, got {int(c)}")
+    return int(c)
+
+
+def _as_iqc_c64(iq) -> np.ndarray:
+    """C-channel complex64 elements ``(n, C)``, C-contiguous (a view where ``iq`` already is that), C in 2..8."""
+    x = np.asarray(iq)
+    if x.ndim != 2 or not np.issubdtype(x.dtype, np.complexfloating):
+        raise ValueError(f"multi-channel input must be a complex (n, C) array, got shape {x.shape} {x.dtype}")
+    _corrmat_channels(x.shape[1])
+    return _as_c64(x)
+
+
+def _as_iqc_int(iq, dtypes, name: str) -> np.ndarray:
+    """C-channel integer elements ``(n, C, 2)`` (channel, then I,Q) of one of ``dtypes``: checked, never converted."""
+    if not isinstance(iq, np.ndarray) or iq.dtype not in dtypes:
+        raise ValueError(f"multi-channel {name} input must be a numpy {' or '.join(np.dtype(d).name for d in dtypes)} array, got "
+                         f"{getattr(iq, 'dtype', type(iq).__name__)}")
+    if iq.ndim != 3 or iq.shape[2] != 2:
+        raise ValueError(f"multi-channel {name} input must have shape (n, C, 2) (channel, then I, Q), got {iq.shape}")
+    _corrmat_channels(iq.shape[1])
+    if not iq.flags.c_contiguous:
+        raise ValueError(f"multi-channel {name} input must be C-contiguous (I0 Q0 I1 Q1 ... per element)")
+    return iq
+
+
+def plane_index(channels: int, i: int, j: int) -> int:
+    """Where a correlation matrix of ``channels`` channels keeps ``(i, j)`` among its ``channels**2`` planes: the auto power
+    of channel ``i`` for ``i == j``, else the REAL plane of the pair ``(min, max)`` — its imaginary plane is the next one.
+    The autos come first, then the pairs (0,1), (0,2), ..., (0,C-1), (1,2), ..., (C-2,C-1), two planes each."""
+    c = _corrmat_channels(channels)
+    i, j = int(i), int(j)
+    if not (0 <= i < c and 0 <= j < c):
+        raise ValueError(f"channels ({i}, {j}) are not both in 0..{c - 1}")
+    if i == j:
+        return i
+    a, b = min(i, j), max(i, j)
+    return c + 2 * (a * c - a * (a + 1) // 2 + (b - a - 1))
+
+
+class CorrelationMatrix:
+    """What ``SpectrumPlan.correlate`` returns: one ``(groups, C*C, nfft)`` float32 array, per group of ``k`` frames and bin
+    ``scale/k`` times the sums of ``|X_c|^2`` (planes ``0..C-1``) and of ``Re`` and ``Im`` of ``X_i conj(X_j)`` for the pairs
+    ``i < j`` (``plane_index``).  The members derive the rest; direction-finding estimators are numpy on ``matrix()``."""
+
+    def __init__(self, planes: np.ndarray, channels: int):
+        c = _corrmat_channels(channels)
+        planes = np.asarray(planes)
+        if planes.ndim != 3 or planes.shape[1] != c * c:
+            raise ValueError(f"{c} channels take planes of shape (groups, {c * c}, nfft), got {planes.shape}")
+        self.planes = planes
+        self.channels = c
+
+    def auto(self, c: int) -> np.ndarray:
+        """The averaged power ``<|X_c|^2>`` of channel ``c``: a ``(groups, nfft)`` float32 view."""
+        return self.planes[:, plane_index(self.channels, c, c)]
+
+    def cross(self, i: int, j: int) -> np.ndarray:
+        """The averaged cross-spectrum ``<X_i conj(X_j)>`` as complex64 (a new array): the conjugate of ``cross(j, i)`` for
+        ``i > j``, the auto power for ``i == j``."""
+        q = plane_index(self.channels, i, j)
+        z = np.empty(self.planes[:, q].shape, dtype=np.complex64)
+        if i == j:
+            z.real, z.imag = self.planes[:, q], 0.0
+        else:
+            z.real = self.planes[:, q]
+            z.imag = self.planes[:, q + 1] if i < j else -self.planes[:, q + 1]
+        return z
+
+    def matrix(self) -> np.ndarray:
+        """The Hermitian matrix per group and bin: ``(groups, nfft, C, C)`` complex64 (a new array)."""
+        c = self.channels
+        m = np.empty((self.planes.shape[0], self.planes.shape[2], c, c), dtype=np.complex64)
+        for i in range(c):
+            for j in range(c):
+                m[:, :, i, j] = self.cross(i, j)
+        return m
+
+    def coherence(self, i: int, j: int) -> np.ndarray:
+        """Magnitude-squared coherence ``|R_ij|^2 / (R_ii R_jj)`` in float64: 1 where the two channels carry one signal, about
+        ``1/k`` on independent noise.  0 where the denominator is 0 (a dead bin), never NaN."""
+        z = self.cross(i, j).astype(np.complex128)
+        den = self.auto(i).astype(np.float64) * self.auto(j).astype(np.float64)
+        ok = np.isfinite(den) & (den > 0)
+        coh = np.zeros(den.shape, dtype=np.float64)
+        np.divide(z.real * z.real + z.imag * z.imag, den, out=coh, where=ok)
+        return np.where(np.isfinite(coh), coh, 0.0)
+
+    def phase(self, i: int, j: int) -> np.ndarray:
+        """The phase of ``<X_i conj(X_j)>`` in radians in float64: channel ``i``'s phase minus channel ``j``'s."""
+        z = self.cross(i, j)
+        return np.arctan2(z.imag.astype(np.float64), z.real.astype(np.float64))
+
+
 PFB_MAX_TAPS = 32                 # sdrk.h: taps of a prototype filter
 
 
@@ -1226,6 +1325,99 @@ class SpectrumPlan:
         return self._exec_device_xspec("sdrk_exec_device_xspec_ci16", d_iq2, n_groups, k, d_out, frame_stride, scale,
                                        launches=launches)
 
+    # -- correlation matrix of 2..8 channels per k frames: every channel transformed once, C*C sums per bin (float32 plans) --
+    _CORRMAT_SYMS = {"c64": "corrmat", "ci16": "corrmat_ci16", "ci8": "corrmat_iq8"}
+
+    def _host_corrmat(self, x: np.ndarray, form: str, k: int, hop: Optional[int], scale: float, what: str) -> np.ndarray:
+        self._float32_only(what)
+        c = int(x.shape[1])
+        groups = self._n_groups(self.nfft, x.shape[0], k, hop)
+        res = np.empty((groups, c * c, self.nfft), dtype=np.float32)
+        if groups:
+            fn = getattr(lib(), "sdrk_exec_host_" + self._CORRMAT_SYMS[form])
+            fmt = [c_int(_iq8_format(x))] if form == "ci8" else []
+            with self._lock:
+                check(fn(self.handle, x.ctypes.data_as(c_void_p), *fmt, c_int(c), c_size_t(groups), c_size_t(int(k)),
+                         c_size_t(self.nfft if hop is None else int(hop)), c_float(scale), res.ctypes.data_as(c_void_p)))
+        return res
+
+    def correlate(self, iq, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CorrelationMatrix:
+        """The correlation matrix of ``C`` = 2..8 coherent channels per ``k >= 1`` consecutive frames of one contiguous
+        ``C``-channel stream: a ``CorrelationMatrix`` over one ``(groups, C*C, nfft)`` float32 array.  ``iq`` is an ``(n, C)``
+        complex array (element ``n`` = sample ``n`` of channel 0, 1, ... ``C-1``: used as it is when complex64 and
+        C-contiguous).  Frames start every ``hop`` elements (default ``nfft``).  Every channel is transformed once per frame;
+        each pair's planes are the bits ``cross_spectrum`` gives for that pair."""
+        x = _as_iqc_c64(iq)
+        return CorrelationMatrix(self._host_corrmat(x, "c64", k, hop, scale, "correlate"), x.shape[1])
+
+    def correlate_ci16(self, iq, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CorrelationMatrix:
+        """``correlate`` over int16 elements, ``(n, C, 2)`` int16 (channel, then I, Q): bit-identical to it on the widened
+        elements, from half the bytes."""
+        x = _as_iqc_int(iq, (np.int16,), "ci16")
+        return CorrelationMatrix(self._host_corrmat(x, "ci16", k, hop, scale, "correlate_ci16"), x.shape[1])
+
+    def correlate_ci8(self, iq, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CorrelationMatrix:
+        """``correlate`` over 8-bit elements, ``(n, C, 2)`` int8 (ci8) or uint8 (cu8: ``byte - 127.5``); the dtype is the
+        format.  Bit-identical to ``correlate`` on ``iq8_to_c64`` of the elements, from a quarter of the bytes."""
+        x = _as_iqc_int(iq, (np.int8, np.uint8), "8-bit")
+        return CorrelationMatrix(self._host_corrmat(x, "ci8", k, hop, scale, "correlate_ci8"), x.shape[1])
+
+    def cross_spectrum_ci8(self, iq8, k: int, hop: Optional[int] = None, scale: float = 1.0) -> CrossSpectrum:
+        """``cross_spectrum`` over 8-bit elements, ``(n, 2, 2)`` int8 or uint8: served by the correlation-matrix call at two
+        channels, whose four planes are the two-channel layout; bit-identical to ``cross_spectrum`` on the widened pair."""
+        x = _as_iqc_int(iq8, (np.int8, np.uint8), "8-bit")
+        if x.shape[1] != 2:
+            raise ValueError(f"cross_spectrum_ci8 takes two channels, (n, 2, 2), got {x.shape}")
+        res = self._host_corrmat(x, "ci8", k, hop, scale, "cross_spectrum_ci8")
+        return CrossSpectrum(res[:, 0], res[:, 1], res[:, 2], res[:, 3])
+
+    def _exec_device_corrmat(self, form: str, d_iq: int, channels: int, n_groups: int, k: int, d_out: int, frame_stride,
+                             scale: float, stream: int = 0, launches: Optional[int] = None, unsigned: bool = False):
+        sym = "sdrk_exec_device_" + self._CORRMAT_SYMS[form]
+        args = self._xspec_device_args(sym, d_iq, n_groups, k, d_out, frame_stride, scale)
+        fmt = [c_int(IQ8_UNSIGNED if unsigned else IQ8_SIGNED)] if form == "ci8" else []
+        args = [args[0], *fmt, c_int(_corrmat_channels(channels)), *args[1:]]
+        with self._lock:
+            if launches is None:
+                return check(getattr(lib(), sym)(self.handle, *args, c_void_p(stream) if stream else None))
+            ms = (c_float * int(launches))()
+            check(getattr(lib(), sym + "_timed_each")(self.handle, *args, int(launches), ms))
+        return [float(v) for v in ms]
+
+    def exec_device_corrmat(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int, *,
+                            frame_stride: Optional[int] = None, scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: complex64 elements of ``channels`` samples in (``frame_stride`` counts elements; aligned to a
+        sample), ``n_groups * channels**2 * nfft`` float32 out, asynchronous on ``stream`` (0: the plan's stream)."""
+        self._exec_device_corrmat("c64", d_iq, channels, n_groups, k, d_out, frame_stride, scale, stream)
+
+    def exec_device_corrmat_timed_each(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int, launches: int = 1, *,
+                                       frame_stride: Optional[int] = None, scale: float = 1.0) -> list:
+        """``exec_device_corrmat`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_corrmat("c64", d_iq, channels, n_groups, k, d_out, frame_stride, scale, launches=launches)
+
+    def exec_device_corrmat_ci16(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int, *,
+                                 frame_stride: Optional[int] = None, scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_corrmat`` from int16 elements (``4 * channels`` bytes each)."""
+        self._exec_device_corrmat("ci16", d_iq, channels, n_groups, k, d_out, frame_stride, scale, stream)
+
+    def exec_device_corrmat_ci16_timed_each(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int,
+                                            launches: int = 1, *, frame_stride: Optional[int] = None,
+                                            scale: float = 1.0) -> list:
+        """``exec_device_corrmat_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_corrmat("ci16", d_iq, channels, n_groups, k, d_out, frame_stride, scale, launches=launches)
+
+    def exec_device_corrmat_ci8(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int, *, unsigned: bool = False,
+                                frame_stride: Optional[int] = None, scale: float = 1.0, stream: int = 0) -> None:
+        """``exec_device_corrmat`` from 8-bit elements (``2 * channels`` bytes each; ``unsigned``: cu8, else ci8)."""
+        self._exec_device_corrmat("ci8", d_iq, channels, n_groups, k, d_out, frame_stride, scale, stream, unsigned=unsigned)
+
+    def exec_device_corrmat_ci8_timed_each(self, d_iq: int, channels: int, n_groups: int, k: int, d_out: int,
+                                           launches: int = 1, *, unsigned: bool = False, frame_stride: Optional[int] = None,
+                                           scale: float = 1.0) -> list:
+        """``exec_device_corrmat_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._exec_device_corrmat("ci8", d_iq, channels, n_groups, k, d_out, frame_stride, scale, launches=launches,
+                                         unsigned=unsigned)
+
     # -- FIR filtering and channel extraction: tune, filter, decimate (float32 plans with nfft = 4096) -----------------------
     def set_fir(self, taps) -> int:
         """Set the FIR filter: 1..2049 complex taps (``channel_taps`` makes the usual low-pass); returns their number.  The plan
@@ -2059,6 +2251,25 @@ def cross_spectrum(a, b, nfft: int, k: int, hop: Optional[int] = None, window: W
     if isinstance(a, np.ndarray) and a.dtype == np.int16:
         return plan.cross_spectrum_ci16((a, b), k, hop, scale)
     return plan.cross_spectrum((a, b), k, hop, scale)
+
+
+def correlation_matrix(x, nfft: int, k: int, hop: Optional[int] = None, window: WindowArg = None, scale: float = 1.0, *,
+                       shift: bool = True, device: int = 0) -> CorrelationMatrix:
+    """The ``CorrelationMatrix`` of ``C`` = 2..8 coherent channels per ``k`` frames of ``nfft`` samples, accumulated on the
+    device with every channel transformed once (``SpectrumPlan.correlate``).  ``x`` is an ``(n, C)`` complex array, an
+    ``(n, C, 2)`` int16, int8 or uint8 array (the integer forms: the same bits from fewer bytes), or a list of ``C``
+    equal-length per-channel arrays, which is stacked into one element stream — a copy of all of them."""
+    if isinstance(x, (tuple, list)):
+        chans = [np.asarray(c) for c in x]
+        if not chans or any(c.shape != chans[0].shape or c.dtype != chans[0].dtype for c in chans):
+            raise ValueError("a channel list must hold arrays of one shape and dtype")
+        x = np.stack(chans, axis=1)
+    plan = _cached_plan(int(nfft), window, 1e-12, shift, device)
+    if isinstance(x, np.ndarray) and x.dtype == np.int16:
+        return plan.correlate_ci16(x, k, hop, scale)
+    if isinstance(x, np.ndarray) and x.dtype in (np.int8, np.uint8):
+        return plan.correlate_ci8(x, k, hop, scale)
+    return plan.correlate(x, k, hop, scale)
 
 
 def stft_db(iq, nfft: int, hop: Optional[int] = None, window: WindowArg = None, *, eps: float = 1e-12,
