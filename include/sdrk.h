@@ -1018,6 +1018,59 @@ int sdrk_waterfall_read_decimated_begin(sdrk_waterfall* wf, float* out, size_t m
 int sdrk_waterfall_read_decimated_end(sdrk_waterfall* wf);
 int sdrk_waterfall_clear(sdrk_waterfall* wf);
 
+/* ---- filter-and-sum beamformer: 1..8 coherent channels in, one channel out, one pass ----------
+ * Applies per-channel filters to a stream of C-channel ELEMENTS (one sample of every channel: I0 Q0 I1 Q1 ..., the layout of the
+ * correlation matrix calls) and returns the SUM, tuned and decimated as the down-converter does it:
+ *     v[i] = sum_c sum_t h_c,s[t] x_c[i + M - 1 - t]           h_c,s: channel c's taps, rotated to s as the DDC section says
+ * followed by that section's mixer and keeping.  A single complex weight per channel is h_c = conj(w_c) h (y = w^H x, then the
+ * shared filter h); per-channel taps also serve true-time-delay and frequency-dependent weights.  Per block of 4096 elements
+ * every channel is transformed once and ONE transform comes back: C + 1 transforms where C down-converter calls run 2 C, the
+ * stream read once at 8, 4 or 2 bytes per sample, nothing staged in device memory.
+ * The plan owns the filters: sdrk_plan_set_beam(plan, channels, ntaps, taps_c64) takes `channels` x `ntaps` complex64,
+ * row-major, 1 <= channels <= 8, 1 <= ntaps <= 2049, on float32 plans with nfft = 4096 (others: as sdrk_plan_set_fir refuses
+ * them).  Row c goes through sdrk_plan_set_fir's own computation, so H_c carries the bits that call gives h_c.  The beam filters
+ * and the FIR filter are separate state: neither call touches the other's.  sdrk_plan_beam_channels / sdrk_plan_beam_taps
+ * return C and M, 0 while no beam is set.  Not with work of the plan in flight.
+ * Calls: the argument lists of sdrk_exec_*_ddc / _ddc_ci16 / _downconv_iq8, with n_in, n and the prefix counted in ELEMENTS
+ * (a prefix is M - 1 elements); n_out = sdrk_ddc_outputs(n_in, M, decim, index0).  The stream needs the alignment of one sample.
+ * Arithmetic, per block and in this order for c = 0 .. C - 1: X_c = the plan's transform of channel c (widened), z_c = the
+ * product with H_c rotated by s, ROUNDED as the single-channel call rounds it; u = z_0, then u = u + z_c as plain float32 adds
+ * per component; then the transform again, the 2^-12 scaling, the mixer (none for freq_word == 0) and the keeping of the DDC.
+ * Positions at or past n_in count as +0.0 + 0.0i in every channel, for cu8 too.  Host entries, NULL prefix: M - 1 elements of
+ * byte 0, of byte 0x80 for SDRK_IQ8_UNSIGNED.
+ * Promised: C = 1 returns the bits of sdrk_exec_*_ddc* on a plan whose FIR filter is h_0; the int16 and 8-bit entries return
+ * the bits of the complex64 entry on the widened elements; a host entry returns the bits of the device entry on prefix || iq
+ * however it is chunked (SDRK_FIR_CHUNK_BLOCKS honoured; device memory does not grow with n); repeated calls return the same
+ * bits.  Not promised: equal bits between different cuts of one stream into calls, or between channel orders for C > 2.
+ * Refused with SDRK_ERR_INVALID and a message: no beam set (the message names sdrk_plan_set_beam), channels outside 1..8,
+ * ntaps outside 1..2049, decim outside 1..256, n_in < M, NULL pointers, an iq8_format other than the two (the 8-bit spectra's
+ * message), launches < 1; other plans as for the FIR call.  A plan that has refused still works.
+ * Not provided: several beams per call, more than 8 channels, other lengths, double precision. */
+int sdrk_plan_set_beam(sdrk_plan* plan, int channels, int ntaps, const void* taps_c64);
+int sdrk_plan_beam_channels(const sdrk_plan* plan);
+int sdrk_plan_beam_taps(const sdrk_plan* plan);
+/* device in / device out (d_out_c64: n_out complex64), asynchronous on `stream` (NULL: the plan's stream) */
+int sdrk_exec_device_beam(sdrk_plan* plan, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                          void* d_out_c64, void* stream);
+int sdrk_exec_device_beam_ci16(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                               void* d_out_c64, void* stream);
+int sdrk_exec_device_beam_iq8(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word, int decim,
+                              uint64_t index0, void* d_out_c64, void* stream);
+/* timed on the plan's stream: the milliseconds of each of `launches` launches (bench harness) */
+int sdrk_exec_device_beam_timed_each(sdrk_plan* plan, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim,
+                                     uint64_t index0, void* d_out_c64, int launches, float* each_ms);
+int sdrk_exec_device_beam_ci16_timed_each(sdrk_plan* plan, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim,
+                                          uint64_t index0, void* d_out_c64, int launches, float* each_ms);
+int sdrk_exec_device_beam_iq8_timed_each(sdrk_plan* plan, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word,
+                                         int decim, uint64_t index0, void* d_out_c64, int launches, float* each_ms);
+/* host in / host out (pageable or pinned caller arrays) */
+int sdrk_exec_host_beam(sdrk_plan* plan, const void* prefix_c64, const void* iq_c64, size_t n, uint32_t freq_word, int decim,
+                        uint64_t sample0, void* out_c64, size_t* n_out);
+int sdrk_exec_host_beam_ci16(sdrk_plan* plan, const void* prefix_ci16, const void* iq_ci16, size_t n, uint32_t freq_word, int decim,
+                             uint64_t sample0, void* out_c64, size_t* n_out);
+int sdrk_exec_host_beam_iq8(sdrk_plan* plan, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n,
+                            uint32_t freq_word, int decim, uint64_t sample0, void* out_c64, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

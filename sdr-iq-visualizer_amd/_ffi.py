@@ -268,6 +268,19 @@ SYMBOLS = [
     ("sdrk_exec_device_pfb_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_void_p]),
     ("sdrk_exec_device_pfb_kurtosis_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p, c_int, POINTER(c_float)]),
     ("sdrk_exec_host_pfb_kurtosis_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_float, c_void_p]),
+    # filter-and-sum beamformer: 1..8 coherent channels in, one down-converted channel out (the DDC's argument lists, in elements)
+    ("sdrk_plan_set_beam", c_int, [c_void_p, c_int, c_int, c_void_p]),
+    ("sdrk_plan_beam_channels", c_int, [c_void_p]),
+    ("sdrk_plan_beam_taps", c_int, [c_void_p]),
+    ("sdrk_exec_device_beam", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_beam_ci16", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_beam_iq8", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_void_p]),
+    ("sdrk_exec_device_beam_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_device_beam_ci16_timed_each", c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_device_beam_iq8_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_beam", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_host_beam_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    ("sdrk_exec_host_beam_iq8", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
 ]
 
 _lib = None

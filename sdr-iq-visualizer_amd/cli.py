@@ -2,6 +2,7 @@
 
     python -m sdr_iq_visualizer_amd.cli psd recording.sigmf-meta [--nfft 4096] [--welch 1024] [--integrate K [--sk] [--cross] [--correlate]] [--pfb T] [--out rows.npz]
     python -m sdr_iq_visualizer_amd.cli extract recording.sigmf-meta --offset-hz F [F ...] --decim D [--exact] [--taps M] --out BASE
+    python -m sdr_iq_visualizer_amd.cli extract multichannel.sigmf-meta --weights W.npy --offset-hz F --decim D [--exact] --out BASE
     python -m sdr_iq_visualizer_amd.cli synth out_base --frames 8 --nfft 4096      # write a test recording
 
 ``psd`` reproduces, for the first ``--nfft`` samples, the reference's live expression
@@ -35,6 +36,8 @@ EXTRACT_PIECE = 1 << 22            # samples per ChannelStream.push of `extract`
 def _extract(args, sigmf_io, spectrum) -> int:
     """One channel of a single-channel recording -> a cf32_le recording at sample_rate / decim.  ci16_le, ci8 and cu8 samples are
     pushed as the recording holds them (4 and 2 bytes per sample), everything else as complex64."""
+    if args.weights is not None:
+        return _extract_beam(args, sigmf_io, spectrum)
     samples, meta = sigmf_io.read_sigmf(args.path, native="all")
     g = meta.get("global", {})
     if int(g.get("core:num_channels", 1)) != 1:
@@ -64,6 +67,43 @@ def _extract(args, sigmf_io, spectrum) -> int:
     print(json.dumps({"wrote": list(paths), "samples_in": n, "samples_out": int(y.shape[0]), "sample_rate": fs / args.decim,
                       "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, **tuning,
                       "decim": args.decim, "taps": int(taps.shape[0])}))
+    return 0
+
+
+def _extract_beam(args, sigmf_io, spectrum) -> int:
+    """--weights W.npy: the channels of a 2..8-channel recording combined by a filter-and-sum beamformer into ONE cf32_le
+    recording at sample_rate / decim.  W holds (C,) weights (y = w^H x, then the default ddc_taps(decim) low-pass) or (C, M)
+    per-channel taps; the elements are pushed as the recording holds them (8, 4 or 2 bytes per sample)."""
+    if len(args.offset_hz) != 1:
+        print("extract --weights takes one --offset-hz", file=sys.stderr)
+        return 2
+    try:
+        samples, meta = sigmf_io.read_sigmf_channels(args.path)
+        nch = int(meta["num_channels"])
+        if not 2 <= nch <= spectrum.BEAM_MAX_CHANNELS:
+            raise ValueError(f"--weights needs a recording of 2..{spectrum.BEAM_MAX_CHANNELS} channels in cf32_le, ci16_le, ci8 or "
+                             f"cu8; this one has core:num_channels = {nch}")
+        w = np.load(args.weights)
+        if w.ndim not in (1, 2) or w.shape[0] != nch:
+            raise ValueError(f"{args.weights} must hold ({nch},) weights or ({nch}, M) taps, got shape {w.shape}")
+        filters = spectrum.beam_taps(w, spectrum.ddc_taps(args.decim, args.taps)) if w.ndim == 1 else w
+        fs, fc = float(meta["sample_rate"]), float(meta["center_freq"])
+        offset = args.offset_hz[0]
+        if not args.exact:                                   # a whole bin of sample_rate / 4096, as without --exact elsewhere
+            offset = round(offset / (fs / spectrum.FIR_BLOCK)) * (fs / spectrum.FIR_BLOCK)
+        ch = spectrum.BeamStream(None, filters, args.decim, offset, fs, device=args.device)
+    except ValueError as err:
+        print(f"extract: {err}", file=sys.stderr)
+        return 2
+    with ch:
+        n = int(samples.shape[0])
+        out = [ch.push(samples[at:at + EXTRACT_PIECE]) for at in range(0, n, EXTRACT_PIECE)]
+    y = np.concatenate(out) if out else np.empty(0, np.complex64)
+    paths = sigmf_io.write_sigmf(args.out, y, fs / args.decim, fc + ch.tuned_hz,
+                                 description=f"beam of {nch} channels at {ch.tuned_hz:+.1f} Hz of {fc:.1f} Hz, decimated by {args.decim}")
+    print(json.dumps({"wrote": list(paths), "samples_in": n, "samples_out": int(y.shape[0]), "sample_rate": fs / args.decim,
+                      "center_freq": fc + ch.tuned_hz, "tuned_offset_hz": ch.tuned_hz, "freq_word": ch.freq_word, "channels": nch,
+                      "decim": args.decim, "taps": int(filters.shape[1])}))
     return 0
 
 
@@ -135,6 +175,10 @@ def main(argv=None) -> int:
                    help="digital down-converter: tune each offset to the nearest 32-bit frequency word (sample_rate/2^32) instead "
                         "of a bin of sample_rate/4096, and allow any integer --decim; the report has freq_word for shift_bins")
     e.add_argument("--taps", type=_positive, default=None, help="filter length (default min(16*decim + 1, 2049))")
+    e.add_argument("--weights", default=None, metavar="W.npy",
+                   help="on a recording of 2..8 channels (core:num_channels; cf32_le, ci16_le, ci8 or cu8): combine the channels by "
+                        "a filter-and-sum beamformer into one recording.  W.npy holds (C,) complex weights (y = w^H x, then the "
+                        "default low-pass) or (C, M) per-channel taps; one --offset-hz, any integer --decim in 1..256")
     e.add_argument("--out", required=True, help="base name of the cf32_le SigMF recording to write")
     e.add_argument("--device", type=int, default=0)
     s = sub.add_parser("synth")

@@ -5,7 +5,8 @@
 // digital down-converter (sdrk_ddc_outputs, sdrk_exec_*_ddc*, sdrk_exec_*_ddcbank*): the same two calls tuned by a 32-bit frequency
 // word and decimated by any integer, through ddc4096.hip (kernels_ddc.h), with a chunk loop of its own on the same SlotPipe; and of
 // the same from interleaved 8-bit I,Q (sdrk_exec_*_downconv_iq8, sdrk_exec_*_downconvbank_iq8) through downconv_iq8.hip: one more
-// input format of that loop and of ddc_launch.
+// input format of that loop and of ddc_launch; and of the filter-and-sum beamformer (sdrk_plan_set_beam, sdrk_exec_*_beam*): C coherent
+// channels in, one down-converted channel out, through beamsum.hip (kernels_beam.h) and the down-converter's chunk loop.
 //
 // A device call is one launch on the caller's stream.  The numpy boundary runs the same launches on the virtual stream
 // prefix || iq in chunks of whole blocks through sdrk_host_pipeline.hip's SlotPipe, one loop (host_fir_chunks) for the single
@@ -21,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kernels_beam.h"
 #include "kernels_ddc.h"
 #include "kernels_ols_bank.h"
 #include "plan_internal.h"
@@ -331,6 +333,54 @@ int exec_device_ddc_timed(int in, bool bank, sdrk_plan* p, const void* d_in, siz
     });
 }
 
+// The chunk loop of the down-converter's host entries and of the beamformer's (below): the virtual stream V = prefix || iq of n + M - 1
+// units of in_elem bytes (a sample; for the beamformer an element, one sample of every channel), cut into chunks of whole blocks.
+// launch(d_in, cn, index0, d_out, co, nb) runs the first nb blocks of a chunk of cn units whose valid-convolution output 0 has
+// stream index index0, and writes co outputs a plane, packed; `pad` is the byte of a NULL prefix.
+template <class Launch>
+int host_ddc_chunks(size_t in_elem, int pad, int taps, sdrk_plan* p, const void* prefix, const void* iq, size_t n, size_t planes, int decim,
+                    uint64_t sample0, void* out, size_t out_stride, size_t* n_out, Launch launch) {
+    const size_t D = (size_t)decim, M = (size_t)taps, L = (size_t)sdrk::ols_block_len(taps), N = sdrk::OLS_N;
+    const size_t n_virt = n + M - 1, total_out = sdrk::ddc_count(n, decim, sample0);
+    if (total_out == 0) return SDRK_OK;
+    const size_t n_blocks = sdrk::ols_blocks(n_virt, taps), per = fir_chunk_blocks(L, in_elem);
+    const size_t chunk_in = ((per - 1) * L + N) * in_elem, chunk_out = planes * (per * L / D + 1) * sizeof(float2);
+    HIP_TRY(hipSetDevice(p->device));
+    SlotPipe pipe;
+    int st = pipe.open(p, "host pipeline");
+    if (st != SDRK_OK) return st;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += per) {
+        const size_t nb = n_blocks - b0 < per ? n_blocks - b0 : per;
+        const size_t t0 = b0 * L;
+        const size_t cn = (nb - 1) * L + N < n_virt - t0 ? (nb - 1) * L + N : n_virt - t0;
+        const size_t valid = nb * L < cn - M + 1 ? nb * L : cn - M + 1;
+        const size_t o0 = sdrk::ddc_count(t0, decim, sample0), co = sdrk::ddc_count(valid, decim, sample0 + t0);
+        HostSlot* s = nullptr;
+        st = pipe.acquire(chunk_in, chunk_out, s);
+        if (st != SDRK_OK) return st;
+        // units V[t0 .. t0 + cn): the part below M - 1 from the prefix (NULL: zeros; 0x80 bytes for cu8), the rest from iq
+        char* dst = static_cast<char*>(s->h_in);
+        size_t done = 0;
+        if (t0 < M - 1) {
+            done = M - 1 - t0 < cn ? M - 1 - t0 : cn;
+            if (prefix) memcpy(dst, static_cast<const char*>(prefix) + t0 * in_elem, done * in_elem);
+            else memset(dst, pad, done * in_elem);
+        }
+        if (done < cn)
+            memcpy(dst + done * in_elem, static_cast<const char*>(iq) + (t0 + done - (M - 1)) * in_elem, (cn - done) * in_elem);
+        st = pipe.upload(*s, s->h_in, cn * in_elem);
+        if (st == SDRK_OK)
+            st = pipe.submit(*s, launch(s->d_in, cn, sample0 + t0, s->d_out, co, nb),
+                             {ChunkOut::Planes, static_cast<char*>(out) + o0 * sizeof(float2), co * sizeof(float2), planes,
+                              out_stride * sizeof(float2)});
+        if (st != SDRK_OK) return st;
+    }
+    st = pipe.drain();
+    if (st != SDRK_OK) return st;
+    *n_out = total_out;
+    return SDRK_OK;
+}
+
 // The numpy boundary: the device entry on the virtual stream V = prefix || iq with index0 = sample0 (output j of the valid
 // convolution has stream index sample0 + j), in chunks of whole blocks through the plan's pinned staging slots.  Every block is
 // the 4096 samples it is in one device call on V (a chunk carries its last block's overlap and its launch is cut at
@@ -352,45 +402,112 @@ int exec_host_ddc(int in, bool bank, sdrk_plan* p, const void* prefix, const voi
     const int pad = in == SDRK_IQ8_UNSIGNED ? 0x80 : 0;   // the byte of a NULL prefix: 0x80 is mid-scale for unsigned bytes (+0.5)
     uint32_t words[sdrk::DDC_MAX_CHAN];   // read before the call returns: the launches below see this copy
     memcpy(words, freq_word, (size_t)n_chan * sizeof(uint32_t));
-    const size_t M = (size_t)p->fir_taps, L = (size_t)sdrk::ols_block_len(p->fir_taps), N = sdrk::OLS_N, planes = (size_t)n_chan;
-    const size_t n_virt = n + M - 1, total_out = sdrk::ddc_count(n, decim, sample0);
-    if (total_out == 0) return SDRK_OK;
-    const size_t n_blocks = sdrk::ols_blocks(n_virt, p->fir_taps), per = fir_chunk_blocks(L, in_elem);
-    const size_t chunk_in = ((per - 1) * L + N) * in_elem, chunk_out = planes * (per * L / D + 1) * sizeof(float2);
-    HIP_TRY(hipSetDevice(p->device));
-    SlotPipe pipe;
-    st = pipe.open(p, "host pipeline");
-    if (st != SDRK_OK) return st;
-    for (size_t b0 = 0; b0 < n_blocks; b0 += per) {
-        const size_t nb = n_blocks - b0 < per ? n_blocks - b0 : per;
-        const size_t t0 = b0 * L;
-        const size_t cn = (nb - 1) * L + N < n_virt - t0 ? (nb - 1) * L + N : n_virt - t0;
-        const size_t valid = nb * L < cn - M + 1 ? nb * L : cn - M + 1;
-        const size_t o0 = sdrk::ddc_count(t0, decim, sample0), co = sdrk::ddc_count(valid, decim, sample0 + t0);
-        HostSlot* s = nullptr;
-        st = pipe.acquire(chunk_in, chunk_out, s);
-        if (st != SDRK_OK) return st;
-        // samples V[t0 .. t0 + cn): the part below M - 1 from the prefix (NULL: zeros; 0x80 bytes for cu8), the rest from iq
-        char* dst = static_cast<char*>(s->h_in);
-        size_t done = 0;
-        if (t0 < M - 1) {
-            done = M - 1 - t0 < cn ? M - 1 - t0 : cn;
-            if (prefix) memcpy(dst, static_cast<const char*>(prefix) + t0 * in_elem, done * in_elem);
-            else memset(dst, pad, done * in_elem);
-        }
-        if (done < cn)
-            memcpy(dst + done * in_elem, static_cast<const char*>(iq) + (t0 + done - (M - 1)) * in_elem, (cn - done) * in_elem);
-        st = pipe.upload(*s, s->h_in, cn * in_elem);
-        if (st == SDRK_OK)
-            st = pipe.submit(*s, ddc_launch(p, in, bank, s->d_in, cn, n_chan, words, decim, sample0 + t0, s->d_out, co, nb, p->stream),
-                             {ChunkOut::Planes, static_cast<char*>(out) + o0 * sizeof(float2), co * sizeof(float2), planes,
-                              out_stride * sizeof(float2)});
-        if (st != SDRK_OK) return st;
+    return host_ddc_chunks(in_elem, pad, p->fir_taps, p, prefix, iq, n, (size_t)n_chan, decim, sample0, out, out_stride, n_out,
+                           [&](const void* d_in, size_t cn, uint64_t index0, void* d_out, size_t co, size_t nb) {
+                               return ddc_launch(p, in, bank, d_in, cn, n_chan, words, decim, index0, d_out, co, nb, p->stream);
+                           });
+}
+
+// H = DFT_4096(taps zero-padded) in float64, rounded once: exact table angles, H[k] = sum_t h[t] W4096^((k t) mod 4096).
+// `rows` filters of ntaps complex64 taps each, row-major -> rows x 4096 responses: sdrk_plan_set_fir's filter (one row) and every
+// row of sdrk_plan_set_beam's go through this one loop.
+std::vector<float2> fir_responses(const void* taps_c64, int rows, int ntaps) {
+    constexpr int N = sdrk::OLS_N;
+    std::vector<double> wr(N), wi(N);
+    for (int m = 0; m < N; ++m) {
+        const double ang = -2.0 * 3.14159265358979323846 * (double)m / (double)N;
+        wr[m] = cos(ang);
+        wi[m] = sin(ang);
     }
-    st = pipe.drain();
+    std::vector<float2> H((size_t)rows * N);
+    for (int r = 0; r < rows; ++r) {
+        const float* h = static_cast<const float*>(taps_c64) + (size_t)r * 2 * (size_t)ntaps;
+        for (int k = 0; k < N; ++k) {
+            double re = 0.0, im = 0.0;
+            for (int t = 0; t < ntaps; ++t) {
+                const int m = (k * t) & (N - 1);
+                const double hr = h[2 * t], hi = h[2 * t + 1];
+                re += hr * wr[m] - hi * wi[m];
+                im += hr * wi[m] + hi * wr[m];
+            }
+            H[(size_t)r * N + k] = make_float2((float)re, (float)im);
+        }
+    }
+    return H;
+}
+
+// ---- filter-and-sum beamformer: C coherent channels in, one channel out (kernels_beam.h) ----
+int check_beam_call(const sdrk_plan* p, int decim) {
+    int st = check_fir_plan(p);
     if (st != SDRK_OK) return st;
-    *n_out = total_out;
+    if (p->beam_channels < 1 || !p->d_beam_h) return fail(SDRK_ERR_INVALID, "no beam filters set: call sdrk_plan_set_beam first");
+    if (decim < 1 || decim > sdrk::DDC_MAX_DECIM) return fail(SDRK_ERR_INVALID, "decim=%d: must be in [1, %d]", decim, sdrk::DDC_MAX_DECIM);
     return SDRK_OK;
+}
+
+int check_beam_device(const sdrk_plan* p, const void* d_in, size_t n_in, int decim, const void* d_out) {
+    int st = check_beam_call(p, decim);
+    if (st != SDRK_OK) return st;
+    if (!d_in || !d_out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
+    if (n_in < (size_t)p->beam_taps)
+        return fail(SDRK_ERR_INVALID, "n_in=%zu: a valid convolution needs at least the %d taps", n_in, p->beam_taps);
+    return SDRK_OK;
+}
+
+// One launch: the outputs i < max_blocks L (0: all) of the valid convolution of n_in elements.  in: sdrk::BEAM_IN_* or SDRK_IQ8_*.
+int beam_launch(sdrk_plan* p, int in, const void* d_in, size_t n_in, uint32_t freq_word, int decim, uint64_t index0, void* d_out,
+                size_t max_blocks, hipStream_t stream) {
+    sdrk::BeamArgs a;
+    a.d_in = d_in;
+    a.n_in = n_in;
+    a.channels = p->beam_channels;
+    a.taps = p->beam_taps;
+    a.decim = decim;
+    a.freq_word = freq_word;
+    a.index0 = index0;
+    a.d_h = p->d_beam_h;
+    a.d_twiddle = p->d_twiddle;
+    a.d_out = static_cast<float2*>(d_out);
+    a.max_blocks = max_blocks;
+    a.num_cus = p->num_cus;
+    a.stream = stream;
+    if (sdrk::beam_launch_outputs(a) == 0) return SDRK_OK;   // nothing kept: a successful no-op
+    const hipError_t e = sdrk::launch_beamsum(a, in);
+    if (e != hipSuccess) return fail(SDRK_ERR_HIP, "beamformer kernel launch failed: %s", hipGetErrorString(e));
+    return SDRK_OK;
+}
+
+int exec_device_beam(int in, sdrk_plan* p, const void* d_in, size_t n_in, uint32_t freq_word, int decim, uint64_t index0, void* d_out,
+                     void* stream) {
+    int st = check_beam_device(p, d_in, n_in, decim, d_out);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    return beam_launch(p, in, d_in, n_in, freq_word, decim, index0, d_out, 0, stream ? static_cast<hipStream_t>(stream) : p->stream);
+}
+
+int exec_device_beam_timed(int in, sdrk_plan* p, const void* d_in, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                           void* d_out, int launches, float* each_ms) {
+    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
+    int st = check_beam_device(p, d_in, n_in, decim, d_out);
+    if (st != SDRK_OK) return st;
+    return timed_each(p, launches, each_ms, [&] { return beam_launch(p, in, d_in, n_in, freq_word, decim, index0, d_out, 0, p->stream); });
+}
+
+// The numpy boundary: the down-converter's chunk loop on elements of C samples.
+int exec_host_beam(int in, sdrk_plan* p, const void* prefix, const void* iq, size_t n, uint32_t freq_word, int decim, uint64_t sample0,
+                   void* out, size_t* n_out) {
+    int st = check_beam_call(p, decim);
+    if (st != SDRK_OK) return st;
+    if (!n_out) return fail(SDRK_ERR_INVALID, "n_out pointer is NULL");
+    *n_out = 0;
+    if (n == 0) return SDRK_OK;
+    if (!iq || !out) return fail(SDRK_ERR_INVALID, "input or output pointer is NULL");
+    const size_t in_elem = (size_t)p->beam_channels * sdrk::beam_sample_bytes(in);
+    const int pad = in == SDRK_IQ8_UNSIGNED ? 0x80 : 0;   // the byte of a NULL prefix, as for the 8-bit down-converter
+    return host_ddc_chunks(in_elem, pad, p->beam_taps, p, prefix, iq, n, 1, decim, sample0, out, 0, n_out,
+                           [&](const void* d_in, size_t cn, uint64_t index0, void* d_out, size_t, size_t nb) {
+                               return beam_launch(p, in, d_in, cn, freq_word, decim, index0, d_out, nb, p->stream);
+                           });
 }
 
 }  // namespace
@@ -402,26 +519,8 @@ int sdrk_plan_set_fir(sdrk_plan* p, int ntaps, const void* taps_c64) {
     if (st != SDRK_OK) return st;
     if (ntaps < 1 || ntaps > sdrk::OLS_MAX_TAPS) return fail(SDRK_ERR_INVALID, "ntaps=%d: must be in [1, %d]", ntaps, sdrk::OLS_MAX_TAPS);
     if (!taps_c64) return fail(SDRK_ERR_INVALID, "taps pointer is NULL");
-    // H = DFT_4096(taps zero-padded) in float64, rounded once: exact table angles, H[k] = sum_t h[t] W4096^((k t) mod 4096)
     constexpr int N = sdrk::OLS_N;
-    std::vector<double> wr(N), wi(N);
-    for (int m = 0; m < N; ++m) {
-        const double ang = -2.0 * 3.14159265358979323846 * (double)m / (double)N;
-        wr[m] = cos(ang);
-        wi[m] = sin(ang);
-    }
-    const float* h = static_cast<const float*>(taps_c64);
-    std::vector<float2> H(N);
-    for (int k = 0; k < N; ++k) {
-        double re = 0.0, im = 0.0;
-        for (int t = 0; t < ntaps; ++t) {
-            const int m = (k * t) & (N - 1);
-            const double hr = h[2 * t], hi = h[2 * t + 1];
-            re += hr * wr[m] - hi * wi[m];
-            im += hr * wi[m] + hi * wr[m];
-        }
-        H[k] = make_float2((float)re, (float)im);
-    }
+    const std::vector<float2> H = fir_responses(taps_c64, 1, ntaps);
     HIP_TRY(hipSetDevice(p->device));
     // not with work in flight, says the header; make it safe all the same for work on the plan's own stream
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -588,6 +687,80 @@ int sdrk_exec_host_downconvbank_iq8(sdrk_plan* p, const void* prefix_iq8, const 
                                     size_t* n_out) {
     if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
     return exec_host_ddc(iq8_format, true, p, prefix_iq8, iq_iq8, n, n_chan, freq_word, decim, sample0, out_c64, out_stride, n_out);
+}
+
+// ---- filter-and-sum beamformer ----
+int sdrk_plan_set_beam(sdrk_plan* p, int channels, int ntaps, const void* taps_c64) {
+    int st = check_fir_plan(p);
+    if (st != SDRK_OK) return st;
+    if (channels < 1 || channels > sdrk::BEAM_MAX_CHANNELS)
+        return fail(SDRK_ERR_INVALID, "channels=%d: must be in [1, %d]", channels, sdrk::BEAM_MAX_CHANNELS);
+    if (ntaps < 1 || ntaps > sdrk::OLS_MAX_TAPS) return fail(SDRK_ERR_INVALID, "ntaps=%d: must be in [1, %d]", ntaps, sdrk::OLS_MAX_TAPS);
+    if (!taps_c64) return fail(SDRK_ERR_INVALID, "taps pointer is NULL");
+    constexpr size_t N = sdrk::OLS_N;
+    const std::vector<float2> H = fir_responses(taps_c64, channels, ntaps);   // row c: the bits sdrk_plan_set_fir gives its taps
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));   // as sdrk_plan_set_fir: safe for work on the plan's own stream
+    p->beam_channels = 0;
+    if (!p->d_beam_h) HIP_TRY(hipMalloc((void**)&p->d_beam_h, sdrk::BEAM_MAX_CHANNELS * N * sizeof(float2)));
+    HIP_TRY(hipMemcpy(p->d_beam_h, H.data(), (size_t)channels * N * sizeof(float2), hipMemcpyHostToDevice));
+    p->beam_taps = ntaps;
+    p->beam_channels = channels;
+    return SDRK_OK;
+}
+
+int sdrk_plan_beam_channels(const sdrk_plan* p) { return p ? p->beam_channels : fail(SDRK_ERR_INVALID, "plan is NULL"); }
+int sdrk_plan_beam_taps(const sdrk_plan* p) {
+    if (!p) return fail(SDRK_ERR_INVALID, "plan is NULL");
+    return p->beam_channels ? p->beam_taps : 0;
+}
+
+int sdrk_exec_device_beam(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                          void* d_out_c64, void* stream) {
+    return exec_device_beam(sdrk::BEAM_IN_C64, p, d_in_c64, n_in, freq_word, decim, index0, d_out_c64, stream);
+}
+
+int sdrk_exec_device_beam_ci16(sdrk_plan* p, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                               void* d_out_c64, void* stream) {
+    return exec_device_beam(sdrk::BEAM_IN_S16, p, d_in_ci16, n_in, freq_word, decim, index0, d_out_c64, stream);
+}
+
+int sdrk_exec_device_beam_iq8(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word, int decim,
+                              uint64_t index0, void* d_out_c64, void* stream) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_beam(iq8_format, p, d_in_iq8, n_in, freq_word, decim, index0, d_out_c64, stream);
+}
+
+int sdrk_exec_device_beam_timed_each(sdrk_plan* p, const void* d_in_c64, size_t n_in, uint32_t freq_word, int decim, uint64_t index0,
+                                     void* d_out_c64, int launches, float* each_ms) {
+    return exec_device_beam_timed(sdrk::BEAM_IN_C64, p, d_in_c64, n_in, freq_word, decim, index0, d_out_c64, launches, each_ms);
+}
+
+int sdrk_exec_device_beam_ci16_timed_each(sdrk_plan* p, const void* d_in_ci16, size_t n_in, uint32_t freq_word, int decim,
+                                          uint64_t index0, void* d_out_c64, int launches, float* each_ms) {
+    return exec_device_beam_timed(sdrk::BEAM_IN_S16, p, d_in_ci16, n_in, freq_word, decim, index0, d_out_c64, launches, each_ms);
+}
+
+int sdrk_exec_device_beam_iq8_timed_each(sdrk_plan* p, const void* d_in_iq8, int iq8_format, size_t n_in, uint32_t freq_word,
+                                         int decim, uint64_t index0, void* d_out_c64, int launches, float* each_ms) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_device_beam_timed(iq8_format, p, d_in_iq8, n_in, freq_word, decim, index0, d_out_c64, launches, each_ms);
+}
+
+int sdrk_exec_host_beam(sdrk_plan* p, const void* prefix_c64, const void* iq_c64, size_t n, uint32_t freq_word, int decim,
+                        uint64_t sample0, void* out_c64, size_t* n_out) {
+    return exec_host_beam(sdrk::BEAM_IN_C64, p, prefix_c64, iq_c64, n, freq_word, decim, sample0, out_c64, n_out);
+}
+
+int sdrk_exec_host_beam_ci16(sdrk_plan* p, const void* prefix_ci16, const void* iq_ci16, size_t n, uint32_t freq_word, int decim,
+                             uint64_t sample0, void* out_c64, size_t* n_out) {
+    return exec_host_beam(sdrk::BEAM_IN_S16, p, prefix_ci16, iq_ci16, n, freq_word, decim, sample0, out_c64, n_out);
+}
+
+int sdrk_exec_host_beam_iq8(sdrk_plan* p, const void* prefix_iq8, const void* iq_iq8, int iq8_format, size_t n, uint32_t freq_word,
+                            int decim, uint64_t sample0, void* out_c64, size_t* n_out) {
+    if (int st = check_iq8_format(p, iq8_format); st != SDRK_OK) return st;
+    return exec_host_beam(iq8_format, p, prefix_iq8, iq_iq8, n, freq_word, decim, sample0, out_c64, n_out);
 }
 
 }  // extern "C"

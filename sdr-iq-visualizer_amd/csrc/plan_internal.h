@@ -134,6 +134,11 @@ struct sdrk_plan {
     float2* d_fir_h = nullptr;
     int fir_taps = 0;
     int fir_assign = 0;
+    // filter-and-sum beamformer (fir_api.hip): d_beam_h = beam_channels x 4096 complex64, channel-major, row c = what
+    // sdrk_plan_set_fir makes of channel c's taps (sdrk_plan_set_beam; 0 channels = none; allocated once, for 8 channels)
+    float2* d_beam_h = nullptr;
+    int beam_channels = 0;
+    int beam_taps = 0;
     // N = 4096, frames dealt by ticket (f4k_ticket.h, fft4096_ticket_kernel): f4k_order = SDRK_F4K_ORDER at creation;
     // d_f4k_heads = the eight heads, never reset; f4k_bases = where they stand behind every launch enqueued so far.  Two
     // ticketed launches of a plan must not overlap: f4k_ev follows the last one (on f4k_last), and a call on another stream

@@ -366,6 +366,7 @@ FIR_MAX_TAPS = 2049               # sdrk.h: taps of a FIR filter (overlap-save i
 FIR_MAX_DECIM = 256
 FIR_BLOCK = 4096
 FIR_BANK_MAX_CHANNELS = 64        # sdrk.h: channels of one channel-bank call
+BEAM_MAX_CHANNELS = 8             # sdrk.h: coherent channels of one beamformer call
 
 
 def channel_taps(decim: int, ntaps: Optional[int] = None, window: WindowArg = "hann") -> np.ndarray:
@@ -566,6 +567,8 @@ class SpectrumPlan:
         self._lock = threading.Lock()
         self.pfb_taps = 0                              # taps of the prototype filter set by set_pfb() (0: none)
         self.fir_taps = 0                              # taps of the FIR filter set by set_fir() (0: none)
+        self.beam_channels = 0                         # channels of the beam filters set by set_beam() (0: none)
+        self.beam_taps = 0                             # ... and their taps per channel
         self.last_placement: Optional[dict] = None     # report of the last tune_scratch() on this plan
         self._handle = c_void_p()
         wptr = warr.ctypes.data_as(c_void_p) if warr is not None else None
@@ -1588,6 +1591,136 @@ class SpectrumPlan:
         check(lib().sdrk_exec_device_chanbank_timed_each(self.handle, *args, int(launches), each))
         return list(each)
 
+    # -- filter-and-sum beamformer: C coherent channels in, one down-converted channel out ---------------------------------
+    def set_beam(self, taps) -> int:
+        """Set the beam filters: ``(C, M)`` complex taps, one row per channel, C in 1..8 and M in 1..2049 (``beam_taps`` makes
+        them from weights and a shared low-pass); returns C.  Row ``c`` becomes what ``set_fir`` makes of it.  May be called
+        again; leaves the FIR filter and a PFB prototype alone."""
+        self._float32_only("beamforming")
+        h = _as_c64(taps)
+        if h.ndim != 2 or not 1 <= h.shape[0] <= BEAM_MAX_CHANNELS or not 1 <= h.shape[1] <= FIR_MAX_TAPS:
+            raise ValueError(f"beam taps must have shape (C, M) with C in 1..{BEAM_MAX_CHANNELS} and M in 1..{FIR_MAX_TAPS}, "
+                             f"got shape {h.shape}")
+        with self._lock:
+            check(lib().sdrk_plan_set_beam(self.handle, int(h.shape[0]), int(h.shape[1]), h.ctypes.data_as(c_void_p)))
+            self.beam_channels, self.beam_taps = int(h.shape[0]), int(h.shape[1])
+        return self.beam_channels
+
+    def _beam_ready(self) -> int:
+        self._float32_only("beamforming")
+        if self.beam_channels < 1:
+            raise ValueError("no beam filters set: call set_beam(taps) first")
+        return self.beam_taps
+
+    def _beam_input(self, iq, prefix, kind: str):
+        """``iq`` and ``prefix`` as the arrays the C entry of ``kind`` ("", "_ci16", "_ci8") takes: ``(n, C)`` complex64 or
+        ``(n, C, 2)`` integers with the plan's C, checked and (integers) never converted."""
+        m, c = self._beam_ready(), self.beam_channels
+
+        def one(a, what):
+            if kind == "":
+                x = np.asarray(a)
+                if x.ndim != 2 or not np.issubdtype(x.dtype, np.complexfloating):
+                    raise ValueError(f"beam {what} must be a complex (n, C) array, got shape {x.shape} {x.dtype}")
+                x = _as_c64(x)
+            else:
+                dtypes, name = ((np.int16,), "int16") if kind == "_ci16" else ((np.int8, np.uint8), "int8 or uint8")
+                if not isinstance(a, np.ndarray) or a.dtype not in dtypes:
+                    raise ValueError(f"beam {what} must be a numpy {name} array, got {getattr(a, 'dtype', type(a).__name__)}")
+                if a.ndim != 3 or a.shape[2] != 2:
+                    raise ValueError(f"beam {what} must have shape (n, C, 2) (channel, then I, Q), got {a.shape}")
+                if not a.flags.c_contiguous:
+                    raise ValueError(f"beam {what} must be C-contiguous (I0 Q0 I1 Q1 ... per element)")
+                x = a
+            if x.shape[1] != c:
+                raise ValueError(f"beam {what} has {x.shape[1]} channels, the plan's beam filters have {c}")
+            return x
+
+        x = one(iq, "input")
+        pre = None
+        if prefix is not None and m > 1:
+            pre = one(prefix, "prefix")
+            if pre.dtype != x.dtype:
+                raise ValueError(f"beam prefix must have the dtype of iq ({x.dtype}), got {pre.dtype}")
+            if pre.shape[0] != m - 1:
+                raise ValueError(f"prefix must hold the {m - 1} elements before iq, got {pre.shape[0]}")
+        return x, pre
+
+    def beam(self, iq, freq_word: int = 0, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """Filter-and-sum beamformer on ``(n, C)`` complex64 elements (one sample of each of the plan's C channels): every
+        channel filtered by its own row of ``set_beam``'s taps, the sum tuned by ``freq_word`` and decimated by ``decim`` as
+        ``ddc`` does it, in one pass.  With C = 1 the bits of ``ddc`` with that row as the FIR filter."""
+        x, pre = self._beam_input(iq, prefix, "")
+        return self._host_ddc("sdrk_exec_host_beam", x, pre, freq_word, decim, sample0)
+
+    def beam_ci16(self, iq, freq_word: int = 0, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``beam`` on int16 elements of shape ``(n, C, 2)``: the bits of ``beam`` on the widened elements."""
+        x, pre = self._beam_input(iq, prefix, "_ci16")
+        return self._host_ddc("sdrk_exec_host_beam_ci16", x, pre, freq_word, decim, sample0)
+
+    def beam_ci8(self, iq, freq_word: int = 0, *, decim: int = 1, prefix=None, sample0: int = 0) -> np.ndarray:
+        """``beam`` on 8-bit elements of shape ``(n, C, 2)``, int8 (ci8) or uint8 (cu8) — the dtype is the format: the bits of
+        ``beam`` on ``iq8_to_c64(iq)``; without a prefix a uint8 stream starts from M - 1 elements of byte 128."""
+        x, pre = self._beam_input(iq, prefix, "_ci8")
+        return self._host_ddc("sdrk_exec_host_beam_iq8", x, pre, freq_word, decim, sample0, fmt=_iq8_format(x))
+
+    def beam_outputs(self, n_in: int, decim: int = 1, index0: int = 0) -> int:
+        """Samples ``exec_device_beam`` writes for ``n_in`` input elements (``sdrk_ddc_outputs`` with the beam's taps)."""
+        m = self._beam_ready()
+        if int(n_in) < m:
+            raise ValueError(f"n_in={n_in}: a valid convolution needs at least the {m} taps")
+        if int(index0) < 0:
+            raise ValueError("index0 must be >= 0")
+        return int(lib().sdrk_ddc_outputs(c_size_t(int(n_in)), m, _ddc_decim(decim), _ffi.c_uint64(int(index0))))
+
+    def _device_beam_args(self, d_in: int, n_in: int, freq_word: int, decim: int, index0: int, d_out: int, unsigned=None) -> list:
+        self.beam_outputs(n_in, decim, index0)
+        fmt = [] if unsigned is None else [c_int(IQ8_UNSIGNED if unsigned else IQ8_SIGNED)]
+        return [self.handle, c_void_p(d_in), *fmt, c_size_t(int(n_in)), _ffi.c_uint32(_ddc_word(freq_word)), _ddc_decim(decim),
+                _ffi.c_uint64(int(index0)), c_void_p(d_out)]
+
+    def exec_device_beam(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, *, decim: int = 1, index0: int = 0,
+                         stream: int = 0) -> None:
+        """Device pointers, "valid" form: ``n_in`` elements of C complex64 samples in, ``beam_outputs(n_in, decim, index0)``
+        complex64 out; asynchronous on ``stream`` (0: the plan's stream)."""
+        args = self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out)
+        check(lib().sdrk_exec_device_beam(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_beam_ci16(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, *, decim: int = 1, index0: int = 0,
+                              stream: int = 0) -> None:
+        """``exec_device_beam`` on int16 elements (4 bytes per sample)."""
+        args = self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out)
+        check(lib().sdrk_exec_device_beam_ci16(*args, c_void_p(stream) if stream else None))
+
+    def exec_device_beam_ci8(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, *, unsigned: bool = False, decim: int = 1,
+                             index0: int = 0, stream: int = 0) -> None:
+        """``exec_device_beam`` on 8-bit elements (2 bytes per sample; ``unsigned``: cu8, else ci8)."""
+        args = self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out, unsigned)
+        check(lib().sdrk_exec_device_beam_iq8(*args, c_void_p(stream) if stream else None))
+
+    def _beam_timed(self, sym: str, args: list, launches: int) -> list:
+        each = (c_float * max(int(launches), 1))()
+        check(getattr(lib(), sym)(*args, int(launches), each))
+        return list(each)
+
+    def exec_device_beam_timed_each(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, launches: int = 1, *,
+                                    decim: int = 1, index0: int = 0) -> list:
+        """``exec_device_beam`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._beam_timed("sdrk_exec_device_beam_timed_each",
+                                self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out), launches)
+
+    def exec_device_beam_ci16_timed_each(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, launches: int = 1, *,
+                                         decim: int = 1, index0: int = 0) -> list:
+        """``exec_device_beam_ci16`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._beam_timed("sdrk_exec_device_beam_ci16_timed_each",
+                                self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out), launches)
+
+    def exec_device_beam_ci8_timed_each(self, d_in: int, n_in: int, d_out: int, freq_word: int = 0, launches: int = 1, *,
+                                        unsigned: bool = False, decim: int = 1, index0: int = 0) -> list:
+        """``exec_device_beam_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        return self._beam_timed("sdrk_exec_device_beam_iq8_timed_each",
+                                self._device_beam_args(d_in, n_in, freq_word, decim, index0, d_out, unsigned), launches)
+
     # -- digital down-converter: the two calls above tuned by a 32-bit frequency word, decimated by any integer 1..256 ------
     def _ddc_input(self, iq, prefix, ci16: bool):
         m = self._fir_ready()
@@ -2514,9 +2647,13 @@ class _DdcStreamBase:
         self.out_rate = self.sample_rate / self.decim
         self._own = plan is None
         self.plan = SpectrumPlan(FIR_BLOCK, device=device) if plan is None else plan
-        self.ntaps = int(self.plan.set_fir(taps))
+        self.ntaps = int(self._set_filter(taps))
         self.sample_index = 0                              # stream index of the next input sample
         self._tail = None                                  # the last M - 1 input samples (None: none yet = zeros)
+
+    def _set_filter(self, taps) -> int:
+        """Hand the plan its filter; the taps per channel."""
+        return self.plan.set_fir(taps)
 
     def _piece(self, iq) -> np.ndarray:
         return _stream_piece(type(self).__name__, iq, self._tail)
@@ -2581,5 +2718,117 @@ class DdcBankStream(_DdcStreamBase):
         if x.shape[0] == 0:
             return np.empty((len(self.freq_words), 0), dtype=np.complex64)
         out = self._run(x, True)(x, self.freq_words, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
+        self._advance(x)
+        return out
+
+
+# -- filter-and-sum beamformer ---------------------------------------------------------------------------------------------
+def beam_taps(weights, taps) -> np.ndarray:
+    """The ``(C, M)`` beam filters of ``C`` complex weights and one shared filter ``taps``: row ``c`` is ``conj(w_c) * taps``,
+    the convention ``y = w^H x`` followed by the filter."""
+    w = np.asarray(weights, dtype=np.complex128).reshape(-1)
+    h = np.asarray(taps, dtype=np.complex128).reshape(-1)
+    if not 1 <= w.shape[0] <= BEAM_MAX_CHANNELS:
+        raise ValueError(f"weights must hold 1..{BEAM_MAX_CHANNELS} channels, got {w.shape[0]}")
+    if not 1 <= h.shape[0] <= FIR_MAX_TAPS:
+        raise ValueError(f"taps must hold 1..{FIR_MAX_TAPS} coefficients, got {h.shape[0]}")
+    return np.ascontiguousarray((np.conj(w)[:, None] * h[None, :]).astype(np.complex64))
+
+
+def mvdr_weights(R, steering, loading: float = 0.0) -> np.ndarray:
+    """Minimum-variance distortionless-response weights ``R^-1 a / (a^H R^-1 a)`` for one ``(C, C)`` covariance matrix ``R``
+    (a bin or a band average of ``CorrelationMatrix.matrix()``) and steering vector ``a``, with ``loading`` added to the
+    diagonal: ``w^H a = 1``.  Plain numpy, complex128."""
+    r = np.asarray(R, dtype=np.complex128)
+    a = np.asarray(steering, dtype=np.complex128).reshape(-1)
+    if r.ndim != 2 or r.shape[0] != r.shape[1] or r.shape[0] != a.shape[0]:
+        raise ValueError(f"R must be (C, C) and steering (C,), got {r.shape} and {a.shape}")
+    if float(loading) < 0:
+        raise ValueError("loading must be >= 0")
+    ria = np.linalg.solve(r + float(loading) * np.eye(r.shape[0]), a)
+    return ria / np.vdot(a, ria)
+
+
+def _beam_kind(iq) -> str:
+    if isinstance(iq, np.ndarray) and iq.dtype in _NARROW:
+        return "_ci16" if iq.dtype == np.int16 else "_ci8"
+    return ""
+
+
+def _beam_filters(weights_or_taps, decim: int, taps) -> np.ndarray:
+    """``(C, M)`` filters from ``(C, M)`` taps as they are, or from ``(C,)`` weights and ``taps`` (None: ``ddc_taps(decim)``)."""
+    w = np.asarray(weights_or_taps)
+    if w.ndim == 2:
+        if taps is not None:
+            raise ValueError("taps goes with (C,) weights; (C, M) filters already hold theirs")
+        return _as_c64(w)
+    return beam_taps(w, ddc_taps(decim) if taps is None else taps)
+
+
+def _cached_beam_plan(filters: np.ndarray, device: int) -> "SpectrumPlan":
+    key = (int(device), FIR_BLOCK, ("beam", filters.shape, hashlib.sha1(filters.tobytes()).digest()), 1e-12, True, "single")
+    plan = _plans.get(key)
+    if plan is None:
+        with _plans_lock:
+            plan = _plans.get(key)
+            if plan is None:
+                plan = SpectrumPlan(FIR_BLOCK, device=device)
+                plan.set_beam(filters)
+                _plans[key] = plan
+    return plan
+
+
+def beamform(x, weights_or_taps, offset_hz: float, sample_rate: float, decim: int = 1, *, taps=None, device: int = 0) -> np.ndarray:
+    """``SpectrumPlan.beam`` on a cached plan: ``x`` of shape ``(n, C)`` complex, or ``(n, C, 2)`` int16 / int8 / uint8, combined
+    with ``(C,)`` weights (``y = w^H x``, then ``taps``, by default ``ddc_taps(decim)``) or ``(C, M)`` per-channel taps, the band
+    around ``offset_hz`` moved to DC and decimated by ``decim``."""
+    _ddc_decim(decim)
+    word = freq_word(offset_hz, sample_rate)
+    plan = _cached_beam_plan(_beam_filters(weights_or_taps, decim, taps), device)
+    return getattr(plan, "beam" + _beam_kind(x))(x, word, decim=decim)
+
+
+class BeamStream(_DdcStreamBase):
+    """``DdcStream`` behind a filter-and-sum beamformer: pieces of ``(n, C)`` complex64 elements, or ``(n, C, 2)`` int16 / int8 /
+    uint8 (one kind throughout), in; the beam's output samples whose stream index is a multiple of ``decim`` out.  ``taps``:
+    the ``(C, M)`` beam filters (``beam_taps``).  The last ``M - 1`` elements and the stream index are kept between calls; a
+    uint8 stream starts from elements of byte 128."""
+
+    def __init__(self, plan, taps, decim: int, offset_hz: float, sample_rate: float, *, device: int = 0):
+        word = freq_word(offset_hz, sample_rate)
+        super().__init__(plan, taps, decim, sample_rate, device)
+        self.freq_word = word
+        self.tuned_hz = freq_word_hz(word, self.sample_rate)
+
+    def _set_filter(self, taps) -> int:
+        h = _as_c64(taps)
+        self.channels = int(self.plan.set_beam(h))
+        return int(h.shape[1])
+
+    def _piece(self, iq) -> np.ndarray:
+        x = np.ascontiguousarray(iq) if _beam_kind(iq) else _as_c64(iq)
+        if x.ndim != (3 if _beam_kind(iq) else 2) or x.shape[1] != self.channels:
+            raise ValueError(f"a BeamStream piece must have shape (n, {self.channels})" + (" + (2,)" if _beam_kind(iq) else "")
+                             + f", got {x.shape}")
+        if self._tail is not None and self._tail.dtype != x.dtype:
+            raise ValueError(f"a BeamStream takes complex, int16, int8 or uint8 pieces, not both: one kind throughout "
+                             f"(so far {self._tail.dtype}, now {x.dtype})")
+        return x
+
+    def _advance(self, x: np.ndarray) -> None:
+        keep = self.ntaps - 1
+        if keep:
+            tail = self._tail
+            if tail is None:
+                tail = np.full((keep,) + x.shape[1:], 128 if x.dtype == np.uint8 else 0, x.dtype)
+            self._tail = np.ascontiguousarray(np.concatenate((tail, x))[-keep:])
+        self.sample_index += int(x.shape[0])
+
+    def push(self, iq) -> np.ndarray:
+        x = self._piece(iq)
+        if x.shape[0] == 0:
+            return np.empty(0, dtype=np.complex64)
+        run = getattr(self.plan, "beam" + _beam_kind(x))
+        out = run(x, self.freq_word, decim=self.decim, prefix=self._tail, sample0=self.sample_index)
         self._advance(x)
         return out
