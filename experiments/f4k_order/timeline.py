@@ -67,7 +67,8 @@ def main():
     ap.add_argument("--short", type=int, default=65536)
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--orders", default="stride,ticket",
-                    help="comma-separated SDRK_F4K_ORDER values, each optionally with :<SDRK_F4K_TICKET_FORM> (ticket:rot4)")
+                    help="comma-separated SDRK_F4K_ORDER values, each optionally with :<SDRK_F4K_TICKET_FORM> (ticket:rot4) and, for a "
+                         "rot form, @<SDRK_F4K_ROT_AHEAD> (ticket:rot4@3)")
     a = ap.parse_args()
     lib = _ffi.lib()
     _ffi.require_device(0)
@@ -87,10 +88,12 @@ def main():
     with open(a.out, "a") as out:
         for order in [o for o in a.orders.split(",") if o]:
             os.environ["SDRK_F4K_ORDER"] = order.split(":")[0]
-            if ":" in order:
-                os.environ["SDRK_F4K_TICKET_FORM"] = order.split(":")[1]
-            else:
-                os.environ.pop("SDRK_F4K_TICKET_FORM", None)
+            form, _, ahead = order.partition(":")[2].partition("@")
+            for var, value in (("SDRK_F4K_TICKET_FORM", form), ("SDRK_F4K_ROT_AHEAD", ahead)):
+                if value:
+                    os.environ[var] = value
+                else:
+                    os.environ.pop(var, None)
             with SpectrumPlan(NFFT, window="hann", device=0) as plan:
                 warm_up_by_time(lambda: plan.exec_device_timed(d_in.value, a.frames, outs[0].value, 1))
                 for i, p in enumerate(outs):

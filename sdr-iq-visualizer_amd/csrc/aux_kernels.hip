@@ -196,7 +196,8 @@ hipError_t launch_copy_1to1(const void* d_in, void* d_out, size_t bytes, int num
 // The two probes with their frames dealt as the flagship kernel's are (f4k_deal.h): the same bytes per frame by the same
 // instructions, one barrier per frame for the dealer's slot.  A grid-stride probe under a ticketed kernel is no ceiling: its
 // workgroups drift apart as the kernel's did (profiles/f4k_ticket/SUMMARY.md §0).  The copy's "frame" is the 1024 vectors a
-// workgroup moves per turn.
+// workgroup moves per turn.  At look-ahead two (F4kRotDeal2) the one barrier stands at the top, between the slot's write and
+// its read, as in fft4096_rot2_kernel.
 template <class Deal>
 __global__ __launch_bounds__(256) void stream_mix_dealt_kernel(const v4f* __restrict__ in, v4f* __restrict__ out, size_t n_frames,
                                                                const sdrk_host::F4kDealArgs da) {
@@ -208,6 +209,10 @@ __global__ __launch_bounds__(256) void stream_mix_dealt_kernel(const v4f* __rest
     deal.begin();
     while (deal.more()) {
         deal.top(tid);
+        if constexpr (Deal::TWO_AHEAD) {
+            __syncthreads();
+            deal.read();
+        }
         const size_t f = deal.frame();
         if (f < n_frames) {
             const v4f* x = in + f * 2048;
@@ -218,7 +223,8 @@ __global__ __launch_bounds__(256) void stream_mix_dealt_kernel(const v4f* __rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[2 * j] + v[2 * j + 1], &o[tid + 256 * j]);
         }
-        __syncthreads();
+        if constexpr (Deal::TWO_AHEAD) deal.tail(tid);
+        else __syncthreads();
         deal.step();
     }
     deal.leave(tid);
@@ -236,6 +242,10 @@ __global__ __launch_bounds__(256) void copy_1to1_dealt_kernel(const v4f* __restr
     deal.begin();
     while (deal.more()) {
         deal.top(tid);
+        if constexpr (Deal::TWO_AHEAD) {
+            __syncthreads();
+            deal.read();
+        }
         const size_t u = deal.frame();
         if (u < n_units) {
             const size_t i = u * 1024 + tid;
@@ -247,21 +257,23 @@ __global__ __launch_bounds__(256) void copy_1to1_dealt_kernel(const v4f* __restr
             for (int j = 0; j < 4; ++j)
                 if (i + 256 * j < n_vec) __builtin_nontemporal_store(v[j], &out[i + 256 * j]);
         }
-        __syncthreads();
+        if constexpr (Deal::TWO_AHEAD) deal.tail(tid);
+        else __syncthreads();
         deal.step();
     }
     deal.leave(tid);
 }
 
 // One dealt launch of `n_units` units on a grid of at most `max_blocks`, or hipErrorNotSupported where the probe's choice
-// leaves the grid-stride loop in place (f4k_ticket_takes); the host's bases follow the launch.
+// leaves the grid-stride loop in place (f4k_ticket_takes); the host's bases follow the launch.  launch(grid, args, dealer):
+// 0 F4kTicketDeal, 1 F4kRotDeal, 2 F4kRotDeal2.
 template <class Launch>
 static hipError_t launch_dealt(sdrk_host::F4kProbeDeal& pd, size_t max_blocks, size_t n_units, Launch&& launch) {
     using namespace sdrk_host;
     if (!pd.d_heads || !f4k_ticket_takes(pd.choice.order, max_blocks, n_units, F4K_TICKET_DEFAULT)) return hipErrorNotSupported;
     const unsigned grid = f4k_ticket_grid(max_blocks, n_units);
     const F4kDealArgs da = {pd.d_heads, pd.bases, pd.choice.form, pd.choice.rot_heads};
-    launch(grid, da, pd.choice.rot_heads != 0);
+    launch(grid, da, !pd.choice.rot_heads ? 0 : (pd.choice.rot_ahead == F4K_AHEAD_2TOP ? 2 : 1));
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess && !pd.choice.rot_heads) f4k_ticket_advance(pd.choice.form, pd.bases, n_units, grid);
     return e;
@@ -272,8 +284,9 @@ hipError_t launch_stream_mix_dealt(const void* d_in, void* d_out, size_t n_frame
     if (n_frames4096 == 0) return hipSuccess;
     const v4f* in = static_cast<const v4f*>(d_in);
     v4f* out = static_cast<v4f*>(d_out);
-    const hipError_t e = launch_dealt(pd, (size_t)num_cus * 3, n_frames4096, [&](unsigned grid, const sdrk_host::F4kDealArgs& da, bool rot) {
-        if (rot) hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
+    const hipError_t e = launch_dealt(pd, (size_t)num_cus * 3, n_frames4096, [&](unsigned grid, const sdrk_host::F4kDealArgs& da, int rot) {
+        if (rot == 2) hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kRotDeal2>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
+        else if (rot) hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
         else hipLaunchKernelGGL(stream_mix_dealt_kernel<F4kTicketDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_frames4096, da);
     });
     return e == hipErrorNotSupported ? launch_stream_mix(d_in, d_out, n_frames4096, num_cus, stream) : e;
@@ -286,8 +299,9 @@ hipError_t launch_copy_1to1_dealt(const void* d_in, void* d_out, size_t bytes, i
     const v4f* in = static_cast<const v4f*>(d_in);
     v4f* out = static_cast<v4f*>(d_out);
     const hipError_t e = launch_dealt(pd, (size_t)num_cus * blocks_per_cu, (n_vec + 1023) / 1024,
-                                      [&](unsigned grid, const sdrk_host::F4kDealArgs& da, bool rot) {
-        if (rot) hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
+                                      [&](unsigned grid, const sdrk_host::F4kDealArgs& da, int rot) {
+        if (rot == 2) hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kRotDeal2>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
+        else if (rot) hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kRotDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
         else hipLaunchKernelGGL(copy_1to1_dealt_kernel<F4kTicketDeal>, dim3(grid), dim3(256), 0, stream, in, out, n_vec, da);
     });
     return e == hipErrorNotSupported ? launch_copy_1to1(d_in, d_out, bytes, num_cus, blocks_per_cu, stream) : e;

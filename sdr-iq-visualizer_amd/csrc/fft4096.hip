@@ -28,8 +28,9 @@
 // the next frame's 16 loads per thread are in flight while the current frame is
 // transformed, so each resident workgroup keeps 32 KiB of HBM reads outstanding.
 // fft4096_ticket_kernel is the same frame body under another order of the frames: a workgroup takes its next frame
-// from a counter in device memory (f4k_ticket.h) instead of stepping by the grid; fft4096_rot_kernel, what a full grid runs,
-// takes one frame per ticket from several such counters in rotation (f4k_rot.h).
+// from a counter in device memory (f4k_ticket.h) instead of stepping by the grid; fft4096_rot_kernel takes one frame per
+// ticket from several such counters in rotation (f4k_rot.h), three tickets ahead, and fft4096_rot2_kernel, what a full grid
+// runs, two.
 #include "f4k_deal.h"
 #include "fft4096_core.h"
 
@@ -264,6 +265,75 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_rot_kernel(
     deal.leave(tid);
 }
 
+// The rot order at look-ahead two (f4k_rot.h, F4kRotDeal2 of f4k_deal.h), what a full grid runs: the ticket that is in lane 0's
+// register at the top of an iteration names the prefetch of that same iteration, with the barriers the frame body has anyway.
+// The transform's first barrier — it only orders the previous frame's pass-3 LDS reads before this frame's exchange-1 writes —
+// stands at the top of the iteration, behind lane 0's slot write; every wave reads the slot there, and the prefetch goes out
+// where it does in fft4096_rot_kernel.  An iteration has the four barriers it had, a skipped frame has one.  The next draw
+// goes out behind the row stores; hipcc waits vmcnt(0) at the top of the loop (for the prefetched loads), which covers it.
+// The rows are fft4096_rot_kernel's bits: only the order of the frames differs.
+// (Built and dropped, profiles/f4k_ahead/SUMMARY.md: the barrier left where it was and the slot read, and the prefetch issued,
+// behind it, one radix-16 pass later — 92 VGPRs, 0.07 ms slower than look-ahead three; and the draw at the top of the
+// iteration, ahead of the prefetch loads — 0.16 ms slower than behind the stores.)
+template <bool HAS_WINDOW, int EPILOGUE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_rot2_kernel(
+    const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift, unsigned* __restrict__ heads, const unsigned n_heads) {
+    typedef F4kInC64 In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    __shared__ unsigned deal_slot[F4K_DEAL_SLOTS];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kRotDeal2 deal(heads, n_heads, n_frames, deal_slot, tid);
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    deal.publish(tid);
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+    F4K_TIMELINE_LOAD();
+
+    auto issue = [&](In::word (&x)[16], size_t fr) {
+        F4K_TIMELINE_MARK(fr);
+        if (fr >= n_frames) fr = 0;  // harmless re-read past the end
+        In::issue(x, iq + fr * frame_stride, tid);
+    };
+    In::word nxt[16];
+    deal.begin();
+    issue(nxt, deal.frame());   // the frame to transform has its loads in flight
+    while (deal.more()) {
+        deal.top(tid);
+        __syncthreads();        // the slot; and the previous frame's pass-3 reads are done
+        deal.read();            // deal.next() is the frame to prefetch
+        const size_t cur = deal.frame();
+        if (cur < n_frames) {
+            In::to_owners(nxt, lds, tid);
+            cf v[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = In::widen(nxt[j]);
+            issue(nxt, deal.next());
+            f4k_windowed_transform<HAS_WINDOW, false>(v, lds, tw256, tw1, lds_win, A, tid);
+            f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + cur * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                    voff_out, xor_k2, eps);
+        } else {
+            issue(nxt, deal.next());
+        }
+        deal.tail(tid);
+        deal.step();
+    }
+    deal.leave(tid);
+}
+
 unsigned f4k_max_blocks(int num_cus) { return f4k_grid(num_cus, F4K_WAVES, (size_t)-1); }
 
 hipError_t launch_fft4096(const LaunchArgs& a) {
@@ -312,6 +382,26 @@ hipError_t launch_fft4096_rot(const LaunchArgs& a, unsigned* d_heads, unsigned n
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
 #define SDRK_LAUNCH(W, E)                                                                            \
     hipLaunchKernelGGL((fft4096_rot_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,       \
+                       a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, n_heads)
+    if (a.epilogue == EPI_LOGPSD) {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
+    } else {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_COMPLEX); else SDRK_LAUNCH(false, EPI_COMPLEX);
+    }
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_fft4096_rot2(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (!d_heads || grid == 0 || grid % sdrk_host::F4K_TICKET_MAX_HEADS || !sdrk_host::f4k_rot_heads_ok(n_heads) ||
+        a.n_frames > sdrk_host::F4K_TICKET_MAX_FRAMES)
+        return hipErrorInvalidValue;
+    dim3 g(grid), b(F4K_THREADS);
+    const float2* iq = static_cast<const float2*>(a.d_iq);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(W, E)                                                                            \
+    hipLaunchKernelGGL((fft4096_rot2_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,      \
                        a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, n_heads)
     if (a.epilogue == EPI_LOGPSD) {
         if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);

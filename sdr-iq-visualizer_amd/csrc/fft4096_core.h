@@ -88,7 +88,9 @@ __device__ __forceinline__ void pow_tree(cf w1, cf (&w)[16]) {
 // Contains four workgroup barriers; the first one also protects the previous
 // call's exchange-2 reads, so calls may follow each other directly.
 // With WIN, v[j] is still to be multiplied by the window coefficient win[j] = w[tid + 256 j] (folded into pass 1, cplx.h).
-template <bool WIN = false>
+// ENTRY_BARRIER = false leaves the first barrier to the caller: a barrier of its own between the previous call's return and
+// this call does the same (fft4096_rot2_kernel).
+template <bool WIN = false, bool ENTRY_BARRIER = true>
 __device__ __forceinline__ void f4k_transform(cf (&v)[16], float2* __restrict__ lds,
                                               const float2* __restrict__ tw256,
                                               const float2* __restrict__ tw1, const F4kAddr& A,
@@ -102,7 +104,7 @@ __device__ __forceinline__ void f4k_transform(cf (&v)[16], float2* __restrict__ 
 #pragma unroll
         for (int k = 1; k < 16; ++k) v[rev16(k)] = cmul(v[rev16(k)], w[k]);
     }
-    __syncthreads();  // previous transform's pass-3 reads are done
+    if (ENTRY_BARRIER) __syncthreads();  // previous transform's pass-3 reads are done
 #pragma unroll
     for (int k = 0; k < 16; ++k)
         lds[((k & 1) ? A.x1w_odd : A.x1w_even) + 256 * k] = make_float2(v[rev16(k)].x, v[rev16(k)].y);
@@ -159,7 +161,7 @@ struct F4kInC64 {
 };
 
 // window (16 coefficients per thread from LDS) * v -> transform
-template <bool HAS_WINDOW>
+template <bool HAS_WINDOW, bool ENTRY_BARRIER = true>
 __device__ __forceinline__ void f4k_windowed_transform(cf (&v)[16], float2* __restrict__ lds, const float2* __restrict__ tw256,
                                                        const float2* __restrict__ tw1, const float* __restrict__ lds_win,
                                                        const F4kAddr& A, int tid) {
@@ -167,9 +169,9 @@ __device__ __forceinline__ void f4k_windowed_transform(cf (&v)[16], float2* __re
         float win[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) win[j] = lds_win[tid + 256 * j];
-        f4k_transform<true>(v, lds, tw256, tw1, A, tid, win);
+        f4k_transform<true, ENTRY_BARRIER>(v, lds, tw256, tw1, A, tid, win);
     } else {
-        f4k_transform(v, lds, tw256, tw1, A, tid);
+        f4k_transform<false, ENTRY_BARRIER>(v, lds, tw256, tw1, A, tid);
     }
 }
 

@@ -151,6 +151,8 @@ struct sdrk_plan {
     // d_f4k_rot = its heads and exit counter, zero between launches
     unsigned f4k_rot_heads = sdrk_host::F4K_ROT_DEFAULT_HEADS;
     unsigned* d_f4k_rot = nullptr;
+    // its look-ahead (SDRK_F4K_ROT_AHEAD at creation): F4K_AHEAD_*
+    int f4k_rot_ahead = sdrk_host::F4K_ROT_DEFAULT_AHEAD;
     hipEvent_t f4k_ev = nullptr;
     hipStream_t f4k_last = nullptr;
     bool f4k_recorded = false;

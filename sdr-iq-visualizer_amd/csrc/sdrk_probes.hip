@@ -123,7 +123,7 @@ struct ProbeHeads {
     F4kProbeDeal deal;
     int status = SDRK_OK;
     explicit ProbeHeads(int device) {
-        deal.choice = f4k_choice(getenv("SDRK_F4K_ORDER"), getenv("SDRK_F4K_TICKET_FORM"));
+        deal.choice = f4k_choice(getenv("SDRK_F4K_ORDER"), getenv("SDRK_F4K_TICKET_FORM"), getenv("SDRK_F4K_ROT_AHEAD"));
         if (deal.choice.order == F4K_ORDER_STRIDE) return;            // the grid-stride loops: no heads
         status = check_device(device);
         if (status != SDRK_OK) return;

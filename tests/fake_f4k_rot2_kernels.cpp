@@ -1,0 +1,12 @@
+// tests/fake_f4k_rot2_kernels.cpp — stand-in for the look-ahead-two launcher of csrc/fft4096.hip (kernels.h), for the host-only
+// sanitizer build of csrc/sdrk_plan.hip: the "rot H" stand-in of fake_f4k_rot_kernels.cpp — the real launcher's argument
+// checks, the heads found at zero, moved and left at zero — which the look-ahead does not change.
+#include "../sdr-iq-visualizer_amd/csrc/kernels.h"
+
+namespace sdrk {
+
+hipError_t launch_fft4096_rot2(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid) {
+    return launch_fft4096_rot(a, d_heads, n_heads, grid);
+}
+
+}  // namespace sdrk

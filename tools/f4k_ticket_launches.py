@@ -10,13 +10,17 @@ order is also timed as the product issues it ("product": one call, cut by f4k_sp
 
     python tools/f4k_ticket_launches.py --out profiles/f4k_ticket/launches.json
 
---paired FORM,FORM,... (profiles/f4k_window/SUMMARY.md) measures forms of the ticket order against the product's 1x2 instead:
-two plans in the process per comparison, 1x2 and the other form (SDRK_F4K_TICKET_FORM at creation), on the same pair; whole
-calls of 2^20 frames alternate between the two, each timed by events of its own, and each side is the median of `--reps`
-(after one uncounted launch each).  The first comparison on every pair is 1x2 against a second 1x2 plan: its largest
-difference over the pairs and processes is what alternation alone produces.
+A form is SDRK_F4K_TICKET_FORM's name, and a rot form may name its look-ahead behind an "@": rot4@3, rot4@2top
+(SDRK_F4K_ROT_AHEAD; csrc/f4k_rot.h).
 
-    python tools/f4k_ticket_launches.py --paired rot2,rot4,rot8 --out profiles/f4k_window/paired.json
+--paired FORM,FORM,... (profiles/f4k_window/SUMMARY.md, profiles/f4k_ahead/SUMMARY.md) measures forms of the ticket order
+against a control, `--control` (rot4 at look-ahead three, rot4@3), instead: two plans in the process per comparison, the control
+and the other form (named at creation), on the same pair; whole calls of 2^20 frames alternate between the two, each timed by
+events of its own, and each side is the median of `--reps` (after one uncounted launch each).  The first comparison on every
+pair is the control against a second control plan: its largest difference over the pairs and processes is what alternation
+alone produces.  (profiles/f4k_window/ was measured with 1x2 as the control: --control 1x2.)
+
+    python tools/f4k_ticket_launches.py --paired rot4@2top --out profiles/f4k_ahead/paired.json
 """
 import argparse
 import ctypes
@@ -37,12 +41,19 @@ NFFT = 4096
 PARTS = [1, 2, 4, 8, 16]
 
 
+def name_form(form):
+    """SDRK_F4K_TICKET_FORM and SDRK_F4K_ROT_AHEAD from "<form>[@<ahead>]"; None: the defaults."""
+    name, _, ahead = (form or "").partition("@")
+    for var, value in (("SDRK_F4K_TICKET_FORM", name), ("SDRK_F4K_ROT_AHEAD", ahead)):
+        if value:
+            os.environ[var] = value
+        else:
+            os.environ.pop(var, None)
+
+
 def plan_of(order, parts, form=None):
     os.environ["SDRK_F4K_ORDER"] = order
-    if form:
-        os.environ["SDRK_F4K_TICKET_FORM"] = form
-    else:
-        os.environ.pop("SDRK_F4K_TICKET_FORM", None)
+    name_form(form)
     if parts:
         os.environ["SDRK_F4K_PARTS"] = str(parts)
     else:
@@ -58,7 +69,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--label", default="")
     ap.add_argument("--probe", default="", help="comma-separated forms to time the no-arithmetic 2:1 probe under, beside stride and 1x2")
-    ap.add_argument("--paired", default="", help="comma-separated forms to time against 1x2, launches alternating")
+    ap.add_argument("--paired", default="", help="comma-separated forms to time against the control, launches alternating")
+    ap.add_argument("--control", default="rot4@3", help="the other side of --paired")
     a = ap.parse_args()
     lib = _ffi.lib()
     _ffi.require_device(0)
@@ -109,7 +121,7 @@ def main():
             row = {}
             for form in forms:
                 os.environ["SDRK_F4K_ORDER"] = "stride" if form == "stride" else "ticket"
-                os.environ["SDRK_F4K_TICKET_FORM"] = "1x2" if form == "stride" else form
+                name_form("1x2" if form == "stride" else form)
                 _ffi.check(lib.sdrk_stream_ceiling_probe(0, d_in, p, frames, a.reps, ms))
                 row[form] = round(statistics.median(ms), 4)
             rec["pairs"].append(row)
@@ -121,10 +133,10 @@ def main():
         return
 
     if a.paired:
-        forms = ["1x2"] + [f for f in a.paired.split(",") if f]
-        rec = {"kind": "f4k_ticket_paired", "frames": frames, "outputs": a.outputs, "reps": a.reps, "forms": forms,
+        forms = [a.control] + [f for f in a.paired.split(",") if f]
+        rec = {"kind": "f4k_ticket_paired", "frames": frames, "outputs": a.outputs, "reps": a.reps, "control": a.control, "forms": forms,
                "d_in": hex(d_in.value), "d_out": [hex(p.value) for p in outs], "label": a.label, "pid": os.getpid(), "pairs": []}
-        with plan_of("ticket", 1, "1x2") as base:
+        with plan_of("ticket", 1, a.control) as base:
             warm_up_by_time(lambda: base.exec_device_timed(d_in.value, frames, outs[0].value, 1))
             for p in outs:
                 row = {}
