@@ -68,7 +68,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--orders", default="stride,ticket",
                     help="comma-separated SDRK_F4K_ORDER values, each optionally with :<SDRK_F4K_TICKET_FORM> (ticket:rot4) and, for a "
-                         "rot form, @<SDRK_F4K_ROT_AHEAD> (ticket:rot4@3)")
+                         "rot form, @<SDRK_F4K_ROT_AHEAD>: 3, 2top or 2flow (ticket:rot4@3, ticket:rot4@2flow)")
     a = ap.parse_args()
     lib = _ffi.lib()
     _ffi.require_device(0)

@@ -266,14 +266,16 @@ __global__ __launch_bounds__(256) void copy_1to1_dealt_kernel(const v4f* __restr
 
 // One dealt launch of `n_units` units on a grid of at most `max_blocks`, or hipErrorNotSupported where the probe's choice
 // leaves the grid-stride loop in place (f4k_ticket_takes); the host's bases follow the launch.  launch(grid, args, dealer):
-// 0 F4kTicketDeal, 1 F4kRotDeal, 2 F4kRotDeal2.
+// 0 F4kTicketDeal, 1 F4kRotDeal, 2 F4kRotDeal2 (F4K_AHEAD_2TOP and F4K_AHEAD_2FLOW: the probes have one form at look-ahead two —
+// a software-pipelined 2:1 probe that leaves its stores in flight as fft4096_flow2_kernel does was built and measured 0.25 ms
+// SLOWER than this one on every pair, so this one is the truer ceiling; profiles/f4k_flow/SUMMARY.md (a)).
 template <class Launch>
 static hipError_t launch_dealt(sdrk_host::F4kProbeDeal& pd, size_t max_blocks, size_t n_units, Launch&& launch) {
     using namespace sdrk_host;
     if (!pd.d_heads || !f4k_ticket_takes(pd.choice.order, max_blocks, n_units, F4K_TICKET_DEFAULT)) return hipErrorNotSupported;
     const unsigned grid = f4k_ticket_grid(max_blocks, n_units);
     const F4kDealArgs da = {pd.d_heads, pd.bases, pd.choice.form, pd.choice.rot_heads};
-    launch(grid, da, !pd.choice.rot_heads ? 0 : (pd.choice.rot_ahead == F4K_AHEAD_2TOP ? 2 : 1));
+    launch(grid, da, !pd.choice.rot_heads ? 0 : (f4k_ahead_is_two(pd.choice.rot_ahead) ? 2 : 1));
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess && !pd.choice.rot_heads) f4k_ticket_advance(pd.choice.form, pd.bases, n_units, grid);
     return e;

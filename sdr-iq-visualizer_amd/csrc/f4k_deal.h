@@ -170,7 +170,8 @@ struct F4kRotDeal {
 //     deal.tail(tid);  deal.step();
 //
 // The next draw goes out in tail(), behind the iteration's stores (at the top, ahead of the prefetch loads, it measured 0.16 ms
-// slower on 2^20 frames, profiles/f4k_ahead/SUMMARY.md).  slot[0]: the prologue's frame; [2], [3]: the loop's, alternating (the
+// slower on 2^20 frames, profiles/f4k_ahead/SUMMARY.md); fft4096_flow2_kernel calls tail() behind the transform and ahead of
+// the stores, so that the stores are the youngest operations at the loop top (profiles/f4k_flow/SUMMARY.md).  slot[0]: the prologue's frame; [2], [3]: the loop's, alternating (the
 // one barrier between top() and read() also orders this iteration's read before the write of the iteration after the next).
 struct F4kRotDeal2 {
     static constexpr bool TWO_AHEAD = true;

@@ -13,7 +13,8 @@
 // covered it), goes into an LDS slot there as a frame number, is read by every wave behind the barriers of i + 1, names the
 // prefetch of i + 2 and is transformed in i + 3.  The first three tickets are drawn in the prologue.
 //
-// Look-ahead two (F4kRotDeal2, fft4096_rot2_kernel; the product's form, F4K_ROT_DEFAULT_AHEAD below, profiles/f4k_ahead/SUMMARY.md):
+// Look-ahead two (F4kRotDeal2; fft4096_rot2_kernel, profiles/f4k_ahead/SUMMARY.md, and fft4096_flow2_kernel, the product's form,
+// F4K_ROT_DEFAULT_AHEAD below, which sends the draw out AHEAD of the row stores and does not wait for them at the loop top):
 // the prologue draws two tickets, and the ticket that is in the register at the top of iteration i goes into the slot there, is
 // read by every wave behind a barrier the frame body has anyway (the transform's entry barrier, which stands at the top of the
 // iteration in that kernel) and names the prefetch of that same iteration i; it is transformed in i + 1.  The next draw goes out
@@ -100,13 +101,19 @@ constexpr unsigned F4K_ROT_DEFAULT_HEADS = 4;
 // alternating with a rot4 plan at look-ahead three on the same pair: two ahead with the draw at the top gains 0.08 ms on 8.03
 // (on every pair, 0.05 at the least), the draw behind the row stores another 0.16 (0.15 at the least), where a second plan of the
 // control differs by 0.005 and 0.024 (profiles/f4k_ahead/SUMMARY.md).
-enum { F4K_AHEAD_3 = 3, F4K_AHEAD_2TOP = 2 };
-constexpr int F4K_ROT_DEFAULT_AHEAD = F4K_AHEAD_2TOP;
+// "2flow" (fft4096_flow2_kernel) is 2top's dealer and order with the draw ahead of the row stores and a loop that does not wait
+// for those stores at its top (fft4096.hip); the enumerator's value is a name, not a count.  Launches alternating with a rot4 plan
+// at 2top on the same pair: 2flow gains 0.18 ms on 7.90-8.01 (on every pair of nine, 0.11 at the least), where a second plan of
+// the control differs by 0.014 at the most (profiles/f4k_flow/SUMMARY.md).
+enum { F4K_AHEAD_3 = 3, F4K_AHEAD_2TOP = 2, F4K_AHEAD_2FLOW = 4 };
+constexpr int F4K_ROT_DEFAULT_AHEAD = F4K_AHEAD_2FLOW;
+// the dealer of a look-ahead is F4kRotDeal2 (f4k_deal.h), not F4kRotDeal
+constexpr bool f4k_ahead_is_two(int ahead) { return ahead == F4K_AHEAD_2TOP || ahead == F4K_AHEAD_2FLOW; }
 
 // What the environment asks of the N = 4096 order (plans at creation, the no-arithmetic probes per call):
 // SDRK_F4K_ORDER = "stride" / "ticket" forces either loop wherever a ticketed grid exists (f4k_ticket_takes);
 // SDRK_F4K_TICKET_FORM = "<heads>x<frames per ticket>" (f4k_ticket.h) or "rot<heads>" names a form for A/B work.
-// SDRK_F4K_ROT_AHEAD = "3" | "2top" names the rot form's look-ahead (above); anything else leaves the default.
+// SDRK_F4K_ROT_AHEAD = "3" | "2top" | "2flow" names the rot form's look-ahead (above); anything else leaves the default.
 struct F4kChoice {
     int order = F4K_ORDER_AUTO;
     F4kTicketForm form = F4K_TICKET_FORM;
@@ -117,6 +124,7 @@ inline int f4k_rot_ahead_parse(const char* s) {
     if (!s) return -1;
     if (s[0] == '3' && s[1] == 0) return F4K_AHEAD_3;
     if (s[0] == '2' && s[1] == 't' && s[2] == 'o' && s[3] == 'p' && s[4] == 0) return F4K_AHEAD_2TOP;
+    if (s[0] == '2' && s[1] == 'f' && s[2] == 'l' && s[3] == 'o' && s[4] == 'w' && s[5] == 0) return F4K_AHEAD_2FLOW;
     return -1;
 }
 inline F4kChoice f4k_choice(const char* order_env, const char* form_env, const char* ahead_env = nullptr) {

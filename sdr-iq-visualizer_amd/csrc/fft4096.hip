@@ -29,8 +29,8 @@
 // transformed, so each resident workgroup keeps 32 KiB of HBM reads outstanding.
 // fft4096_ticket_kernel is the same frame body under another order of the frames: a workgroup takes its next frame
 // from a counter in device memory (f4k_ticket.h) instead of stepping by the grid; fft4096_rot_kernel takes one frame per
-// ticket from several such counters in rotation (f4k_rot.h), three tickets ahead, and fft4096_rot2_kernel, what a full grid
-// runs, two.
+// ticket from several such counters in rotation (f4k_rot.h), three tickets ahead, fft4096_rot2_kernel two, and
+// fft4096_flow2_kernel, what a full grid runs, two with the row stores left in flight across the turn.
 #include "f4k_deal.h"
 #include "fft4096_core.h"
 
@@ -60,8 +60,10 @@ __device__ uint4* f4k_timeline_buf = nullptr;
 // log epilogue (1.5 % slower), and sending the row through LDS once more so that it leaves as four 16-byte stores
 // per thread instead of sixteen 4-byte ones (1.0-1.5 % slower: two more barriers per frame cost more than the
 // narrower stores do); issuing the prefetch through inline asm with an exact `s_waitcnt vmcnt(16)` in front of its first
-// use — hipcc waits vmcnt(0) there, i.e. also for the previous frame's stores — changed nothing either: with three
-// workgroups per CU another wave always has work while one waits for its store acknowledgements.  The window coefficients
+// use — hipcc waits vmcnt(0) there, i.e. also for the previous frame's stores — changed nothing either ON THIS KERNEL, the
+// grid-stride order at 9.2 ms, which then ran faster than its no-arithmetic probe (0.95-0.98) and whose pace the disorder
+// among its workgroups set.  In the rot order at 7.7-7.9 ms the same wait costs 0.11-0.22 ms: fft4096_flow2_kernel below,
+// profiles/f4k_flow/SUMMARY.md.  This loop, and the other N = 4096 kernels', still drain their stores.  The window coefficients
 // in 16 VGPRs per thread instead of the 16 KiB LDS copy were a build switch, F4K_WINREG, that nothing set; it is gone.)
 template <bool HAS_WINDOW, int EPILOGUE>
 __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_kernel(
@@ -265,7 +267,8 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_rot_kernel(
     deal.leave(tid);
 }
 
-// The rot order at look-ahead two (f4k_rot.h, F4kRotDeal2 of f4k_deal.h), what a full grid runs: the ticket that is in lane 0's
+// The rot order at look-ahead two (f4k_rot.h, F4kRotDeal2 of f4k_deal.h), the product's form until fft4096_flow2_kernel below and
+// now its selectable control (SDRK_F4K_ROT_AHEAD=2top): the ticket that is in lane 0's
 // register at the top of an iteration names the prefetch of that same iteration, with the barriers the frame body has anyway.
 // The transform's first barrier — it only orders the previous frame's pass-3 LDS reads before this frame's exchange-1 writes —
 // stands at the top of the iteration, behind lane 0's slot write; every wave reads the slot there, and the prefetch goes out
@@ -330,6 +333,93 @@ __global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_rot2_kernel(
         }
         deal.tail(tid);
         deal.step();
+    }
+    deal.leave(tid);
+}
+
+// fft4096_rot2_kernel's order, dealer and frame body with the row stores left in flight across the turn ("2flow",
+// F4K_AHEAD_2FLOW of f4k_rot.h, what a full grid runs; profiles/f4k_flow/SUMMARY.md: 0.11-0.22 ms faster on every pair).
+// There every wave waits vmcnt(0) on its way back to the loop header — for the acknowledgement of the sixteen row stores it has just issued, and in wave 0 for the draw behind them —
+// before it may touch words that were loaded a whole turn earlier: the header is also reached from the prologue and from a
+// skipped frame, where no stores follow the loads, and hipcc takes the count of the worst path.  Here
+//   - the draw goes out behind the transform and AHEAD of the row stores, so that sixteen stores stand between the atomic
+//     and the loop top (the dealer's rule holds: a draw goes out only after the one before was taken in top());
+//   - the steady loop is entered and re-entered only behind a transformed frame, i.e. with "16 loads, the draw, 16 stores"
+//     outstanding: the first frame runs ahead of the loop, and a workgroup whose frame is at or past the end leaves for a
+//     drain loop of fft4096_rot2_kernel's shape (skipped frames, and the frame or two that may still follow one);
+// and hipcc counts by itself: no wait in the steady loop names fewer than 16 outstanding (tests/test_f4k_flow_code_objects.py).
+// The barriers are those of fft4096_rot2_kernel, four per transformed frame and one per skipped one, and the rows its bits.
+// What is left at the loop's latch is `s_waitcnt vmcnt(16)` — the loads and the draw, not the stores — in front of the sixteen
+// register copies from the prefetch registers.  (Built and dropped: the steady loop unrolled over two turns with two sets of
+// prefetch registers, which removes those copies, takes 152-154 VGPRs where the budget of the N = 4096 kernels is 128.)
+template <bool HAS_WINDOW, int EPILOGUE>
+__global__ __launch_bounds__(F4K_THREADS, F4K_WAVES) void fft4096_flow2_kernel(
+    const float2* __restrict__ iq, size_t frame_stride, void* __restrict__ out_raw,
+    size_t n_frames, const float* __restrict__ window, const float2* __restrict__ tw4096,
+    float eps, int shift, unsigned* __restrict__ heads, const unsigned n_heads) {
+    typedef F4kInC64 In;
+    __shared__ float2 lds[f4k_lds_elems(HAS_WINDOW)];
+    __shared__ unsigned deal_slot[F4K_DEAL_SLOTS];
+    float2* __restrict__ tw256 = lds + F4K_XCH_ELEMS;  // [k][n] = W256^(n k)
+    float2* __restrict__ tw1 = tw256 + 256;            // W4096^tid
+    float* __restrict__ lds_win = reinterpret_cast<float*>(tw1 + 256);
+
+    const int tid = threadIdx.x;
+    F4kRotDeal2 deal(heads, n_heads, n_frames, deal_slot, tid);
+    F4kAddr A = f4k_addr(tid);
+    f4k_init_tables(tw256, tw1, tw4096, tid);
+    if (HAS_WINDOW) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lds_win[tid + 256 * j] = window[tid + 256 * j];
+    }
+    deal.publish(tid);
+    __syncthreads();
+
+    const int xor_k2 = shift ? 8 : 0;
+    constexpr int OUT_ELEM = (EPILOGUE == EPI_LOGPSD ? 4 : 8);
+    const int voff_out = tid * OUT_ELEM;
+    F4K_TIMELINE_LOAD();
+
+    auto issue = [&](In::word (&x)[16], size_t fr) {
+        F4K_TIMELINE_MARK(fr);
+        if (fr >= n_frames) fr = 0;  // harmless re-read past the end
+        In::issue(x, iq + fr * frame_stride, tid);
+    };
+    In::word nxt[16];
+    // one turn on a frame below the end: slot, prefetch, transform, draw, row stores
+    auto turn = [&]() {
+        deal.top(tid);
+        __syncthreads();        // the slot; and the previous frame's pass-3 reads are done
+        deal.read();            // deal.next() is the frame to prefetch
+        const size_t cur = deal.frame();
+        In::to_owners(nxt, lds, tid);
+        cf v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = In::widen(nxt[j]);
+        issue(nxt, deal.next());
+        f4k_windowed_transform<HAS_WINDOW, false>(v, lds, tw256, tw1, lds_win, A, tid);
+        deal.tail(tid);
+        f4k_store_row<EPILOGUE>(v, frame_rsrc(static_cast<char*>(out_raw) + cur * (size_t)(F4K_N * OUT_ELEM), F4K_N * OUT_ELEM),
+                                voff_out, xor_k2, eps);
+        deal.step();
+    };
+    deal.begin();
+    issue(nxt, deal.frame());   // the frame to transform has its loads in flight
+    if (deal.frame() < n_frames) {
+        turn();                                    // the first frame: behind it the state is the steady loop's
+        while (deal.frame() < n_frames) turn();    // the steady loop
+    }
+    while (deal.more()) {                          // the drain: at most a few turns
+        if (deal.frame() < n_frames) {
+            turn();
+        } else {
+            deal.top(tid);
+            __syncthreads();
+            deal.read();
+            issue(nxt, deal.next());
+            deal.tail(tid);
+            deal.step();
+        }
     }
     deal.leave(tid);
 }
@@ -402,6 +492,26 @@ hipError_t launch_fft4096_rot2(const LaunchArgs& a, unsigned* d_heads, unsigned 
     const float2* tw = static_cast<const float2*>(a.d_twiddle);
 #define SDRK_LAUNCH(W, E)                                                                            \
     hipLaunchKernelGGL((fft4096_rot2_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,      \
+                       a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, n_heads)
+    if (a.epilogue == EPI_LOGPSD) {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);
+    } else {
+        if (a.d_window) SDRK_LAUNCH(true, EPI_COMPLEX); else SDRK_LAUNCH(false, EPI_COMPLEX);
+    }
+#undef SDRK_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_fft4096_flow2(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (!d_heads || grid == 0 || grid % sdrk_host::F4K_TICKET_MAX_HEADS || !sdrk_host::f4k_rot_heads_ok(n_heads) ||
+        a.n_frames > sdrk_host::F4K_TICKET_MAX_FRAMES)
+        return hipErrorInvalidValue;
+    dim3 g(grid), b(F4K_THREADS);
+    const float2* iq = static_cast<const float2*>(a.d_iq);
+    const float2* tw = static_cast<const float2*>(a.d_twiddle);
+#define SDRK_LAUNCH(W, E)                                                                            \
+    hipLaunchKernelGGL((fft4096_flow2_kernel<W, E>), g, b, 0, a.stream, iq, a.frame_stride, a.d_out,     \
                        a.n_frames, a.d_window, tw, a.eps, a.shift, d_heads, n_heads)
     if (a.epilogue == EPI_LOGPSD) {
         if (a.d_window) SDRK_LAUNCH(true, EPI_LOGPSD); else SDRK_LAUNCH(false, EPI_LOGPSD);

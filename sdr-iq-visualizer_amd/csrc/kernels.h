@@ -114,6 +114,8 @@ hipError_t launch_fft4096_ticket(const LaunchArgs& a, unsigned* d_heads, const s
 hipError_t launch_fft4096_rot(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid);
 // ... at look-ahead two (F4K_AHEAD_2TOP of f4k_rot.h): the same arguments, heads and rules
 hipError_t launch_fft4096_rot2(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid);
+// ... and with the row stores left in flight across the turn (F4K_AHEAD_2FLOW): the same again
+hipError_t launch_fft4096_flow2(const LaunchArgs& a, unsigned* d_heads, unsigned n_heads, unsigned grid);
 hipError_t launch_fft_small(const LaunchArgs& a);   // 2 <= nfft <= 2048: Stockham radix-2 in LDS (N = 2, 4, 8 and far-apart frames)
 bool fft_lds_supports(int nfft);                     // 16 .. 16384 except 4096: registers + LDS, one pass over HBM
 hipError_t launch_fft_lds(const LaunchArgs& a);

@@ -195,7 +195,9 @@ int plan_launch_impl(sdrk_plan* p, const void* d_iq, size_t n_frames, size_t fra
             a.n_frames = n_frames - f0 < per ? n_frames - f0 : per;
             if (ticket) {
                 const unsigned grid = f4k_ticket_grid(max_blocks, a.n_frames);
-                if (p->f4k_rot_heads && p->f4k_rot_ahead == F4K_AHEAD_2TOP) {
+                if (p->f4k_rot_heads && p->f4k_rot_ahead == F4K_AHEAD_2FLOW) {
+                    e = sdrk::launch_fft4096_flow2(a, p->d_f4k_rot, p->f4k_rot_heads, grid);
+                } else if (p->f4k_rot_heads && p->f4k_rot_ahead == F4K_AHEAD_2TOP) {
                     e = sdrk::launch_fft4096_rot2(a, p->d_f4k_rot, p->f4k_rot_heads, grid);
                 } else if (p->f4k_rot_heads) {
                     e = sdrk::launch_fft4096_rot(a, p->d_f4k_rot, p->f4k_rot_heads, grid);
@@ -428,7 +430,7 @@ int sdrk_plan_create_ex(int device, int nfft, size_t max_batch, int window_kind,
             // The heads of the ticket order, one 128-byte line each.  They start a few hundred tickets short of the 32-bit
             // wrap: every plan that lives for more than a launch or two crosses it, so the wrap is no rare path.
             // SDRK_F4K_ORDER: "stride" / "ticket", either loop at any size (f4k_ticket_takes); SDRK_F4K_TICKET_FORM:
-            // "<heads>x<frames per ticket>" or "rot<heads>" (f4k_rot.h), A/B work; SDRK_F4K_ROT_AHEAD: "3" / "2top", the rot
+            // "<heads>x<frames per ticket>" or "rot<heads>" (f4k_rot.h), A/B work; SDRK_F4K_ROT_AHEAD: "3" / "2top" / "2flow", the rot
             // form's look-ahead
             const F4kChoice choice = f4k_choice(getenv("SDRK_F4K_ORDER"), getenv("SDRK_F4K_TICKET_FORM"), getenv("SDRK_F4K_ROT_AHEAD"));
             p->f4k_order = choice.order;

@@ -10,7 +10,7 @@ order is also timed as the product issues it ("product": one call, cut by f4k_sp
 
     python tools/f4k_ticket_launches.py --out profiles/f4k_ticket/launches.json
 
-A form is SDRK_F4K_TICKET_FORM's name, and a rot form may name its look-ahead behind an "@": rot4@3, rot4@2top
+A form is SDRK_F4K_TICKET_FORM's name, and a rot form may name its look-ahead behind an "@": rot4@3, rot4@2top, rot4@2flow
 (SDRK_F4K_ROT_AHEAD; csrc/f4k_rot.h).
 
 --paired FORM,FORM,... (profiles/f4k_window/SUMMARY.md, profiles/f4k_ahead/SUMMARY.md) measures forms of the ticket order
@@ -21,6 +21,7 @@ pair is the control against a second control plan: its largest difference over t
 alone produces.  (profiles/f4k_window/ was measured with 1x2 as the control: --control 1x2.)
 
     python tools/f4k_ticket_launches.py --paired rot4@2top --out profiles/f4k_ahead/paired.json
+    python tools/f4k_ticket_launches.py --control rot4@2top --paired rot4@2flow --out profiles/f4k_flow/paired.json
 """
 import argparse
 import ctypes
