@@ -351,6 +351,43 @@ int sdrk_exec_device_integrated_ci8_timed_each(sdrk_plan* plan, const void* d_iq
 int sdrk_exec_host_integrated_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_format, size_t n_groups, size_t k_frames,
                                   size_t frame_stride, int detector, int out_form, float scale, float* out);
 
+/* ---- real-sampled input: SigMF rf32_le / ri16_le / ri8 / ru8 --------------------------
+ * One-sided spectra of real sample streams (a direct-sampling receiver, an ADC behind an IF, audio-rate baseband).  For a
+ * float32 plan of power-of-two length N = nfft, 16 <= N <= 2^20, a real frame has L = 2 N samples and a row N + 1 bins: bin k
+ * at k * fs / L, ascending from 0 to fs / 2, no fftshift, whatever the plan's `shift`.  The plan's own window (window_kind at
+ * creation) plays no part; the mode has a real window of L coefficients of its own, rectangular until one is set.
+ *     SDRK_REAL_F32 float32          SDRK_REAL_S16 int16 -> float32(v)
+ *     SDRK_REAL_S8  int8 -> float32(v)          SDRK_REAL_U8  uint8 -> float32(v) - 127.5f        (all exact)
+ * Arithmetic: y[n] = w[n] * x[n] (one float32 product; no window: none), z[m] = y[2m] + i y[2m+1], Z = the plan's rectangular
+ * transform of z, and for k = 0 ... N with Z[N] = Z[0]:
+ *     E = (Z[k] + conj Z[N-k]) / 2,   O = -(i/2) (Z[k] - conj Z[N-k]),   X[k] = E + exp(-i pi k / N) * O
+ * X[0] = Re Z[0] + Im Z[0] and X[N] = Re Z[0] - Im Z[0], both with imaginary part +0.0; exp(-i pi k / N) comes from a table
+ * computed in float64 and rounded once (at N = 4096 times a constant exp(-i pi k2 / 16)).  Rows are complex64 X[k]
+ * (SDRK_REAL_OUT_COMPLEX) or float32 20*log10(|X[k]| + eps) with the plan's eps (SDRK_REAL_OUT_DB).
+ * sdrk_plan_set_real_window: n must be 2 * nfft; the coefficients are copied; NULL / 0 returns to rectangular.  Not with work
+ * of the plan in flight.
+ * Calls: frame_stride counts REAL samples and must be even (frames may overlap or leave gaps); the input pointer must be
+ * aligned to a pair of samples (8 / 4 / 2 bytes); out_stride counts output elements between rows: 0 = packed (nfft + 1),
+ * otherwise >= nfft + 1, and what lies between rows is not written.  The host entries write packed rows and chunk as
+ * sdrk_exec_host does.  N = 4096 is one kernel on the caller's data; other lengths stage complex64 pairs in plan-owned memory
+ * (at most 2 x 64 MiB).
+ * Promised: the integer formats return the bits of the float32 call on the widened samples; a host entry returns the bits of
+ * the device entry however it is chunked; a frame's row does not depend on where in a call it stands.
+ * Refused, nothing launched: an f64 plan, an odd frame_stride, a misaligned pointer, a window of another length, an unknown
+ * real_format or out_form, out_stride in 1 ... nfft, NULL pointers (SDRK_ERR_INVALID); a chirp-z (non-power-of-two) plan and
+ * nfft < 16 or > 2^20 (SDRK_ERR_UNSUPPORTED); each with a message.  A plan that has refused still works.
+ * Not provided: integrated / filter-bank / kurtosis / cross forms and the FIR family on real input, double precision, odd
+ * hops, the inverse transform. */
+enum sdrk_real_format { SDRK_REAL_F32 = 0, SDRK_REAL_S16 = 1, SDRK_REAL_S8 = 2, SDRK_REAL_U8 = 3 };
+enum sdrk_real_out { SDRK_REAL_OUT_DB = 0, SDRK_REAL_OUT_COMPLEX = 1 };
+int sdrk_plan_set_real_window(sdrk_plan* plan, const float* w, size_t n);
+int sdrk_exec_device_real(sdrk_plan* plan, const void* d_x, int real_format, size_t n_frames, size_t frame_stride, int out_form,
+                          void* d_out, size_t out_stride, void* stream);
+int sdrk_exec_device_real_timed_each(sdrk_plan* plan, const void* d_x, int real_format, size_t n_frames, size_t frame_stride,
+                                     int out_form, void* d_out, size_t out_stride, int launches, float* each_ms);
+int sdrk_exec_host_real(sdrk_plan* plan, const void* x, int real_format, size_t n_frames, size_t frame_stride, float* out_db);
+int sdrk_exec_fft_host_real(sdrk_plan* plan, const void* x, int real_format, size_t n_frames, size_t frame_stride, void* out_c64);
+
 /* ---- polyphase filter bank spectra: a T-tap weighted fold in front of the transform ------
  * A plain windowed FFT gives every bin the window's response: a wide main lobe, side lobes that fall slowly.  A polyphase
  * filter bank (weighted overlap-add) applies a prototype filter h of T*nfft coefficients (typically a windowed sinc) to T*nfft

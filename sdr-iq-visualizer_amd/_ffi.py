@@ -281,7 +281,18 @@ SYMBOLS = [
     ("sdrk_exec_host_beam", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
     ("sdrk_exec_host_beam_ci16", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
     ("sdrk_exec_host_beam_iq8", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_uint32, c_int, c_uint64, c_void_p, POINTER(c_size_t)]),
+    # real-sampled input (SigMF rf32_le / ri16_le / ri8 / ru8): frames of 2 * nfft real samples, rows of nfft + 1 bins
+    ("sdrk_plan_set_real_window", c_int, [c_void_p, c_void_p, c_size_t]),
+    ("sdrk_exec_device_real", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    ("sdrk_exec_device_real_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_size_t, c_int,
+                                                 POINTER(c_float)]),
+    ("sdrk_exec_host_real", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    ("sdrk_exec_fft_host_real", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
 ]
+
+# sdrk_real_format / sdrk_real_out of include/sdrk.h
+REAL_F32, REAL_S16, REAL_S8, REAL_U8 = 0, 1, 2, 3
+REAL_OUT_DB, REAL_OUT_COMPLEX = 0, 1
 
 _lib = None
 _lib_lock = threading.Lock()

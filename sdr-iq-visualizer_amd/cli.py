@@ -134,12 +134,51 @@ def _extract_bank(args, sigmf_io, spectrum, samples, fs: float, fc: float) -> in
     return 0
 
 
+REAL_DATATYPES = ("rf32_le", "ri16_le", "ri8", "ru8")
+
+
+def _psd_real(args, sigmf_io, spectrum) -> int:
+    """psd on a real-sampled recording: one-sided dB rows of --nfft real samples each (even; default 8192) with their axis."""
+    for flag, on in (("--sk", args.sk), ("--cross", args.cross), ("--correlate", args.correlate), ("--pfb", args.pfb),
+                     ("--integrate", args.integrate)):
+        if on:
+            print(f"{flag} is not provided on a real-sampled recording: psd writes its one-sided rows (rows_db), which the "
+                  f"caller can reduce", file=sys.stderr)
+            return 2
+    nfft = 8192 if args.nfft is None else int(args.nfft)
+    if nfft < 32 or nfft & (nfft - 1):
+        print(f"--nfft {nfft}: on a real-sampled recording it is the real frame length, a power of two 32 ... 2^21",
+              file=sys.stderr)
+        return 2
+    samples, meta = sigmf_io.read_sigmf_real(args.path)
+    n_samples = int(samples.shape[0])
+    if n_samples < nfft:
+        print(f"recording has {n_samples} samples, need {nfft}", file=sys.stderr)
+        return 2
+    fs, fc = meta["sample_rate"], meta["center_freq"]
+    frames = n_samples // nfft
+    rows = spectrum.rspectrum_db(np.ascontiguousarray(samples[: frames * nfft]).reshape(frames, nfft), nfft, args.window,
+                                 device=args.device)
+    freqs = spectrum.rfreq_axis(nfft, fs, fc)
+    k = int(np.argmax(rows[0]))
+    report = {"samples": n_samples, "sample_rate": fs, "center_freq": fc, "nfft": nfft, "real": True,
+              "datatype": meta.get("global", {}).get("core:datatype"), "rows": frames, "bins": int(rows.shape[1]),
+              "peak_db": float(rows[0, k]), "peak_freq_hz": float(freqs[k]), "median_db": float(np.median(rows[0]))}
+    if args.out:
+        np.savez_compressed(args.out, power_db=rows[0], rows_db=rows, freqs=freqs)
+        report["out"] = args.out
+    print(json.dumps(report))
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="sdr_iq_visualizer_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     p = sub.add_parser("psd")
     p.add_argument("path")
-    p.add_argument("--nfft", type=int, default=4096)
+    p.add_argument("--nfft", type=int, default=None,
+                   help="frame length (default 4096); on a real-sampled recording (rf32_le, ri16_le, ri8, ru8) the real frame "
+                        "length, even (default 8192): psd then writes one-sided rows of nfft/2 + 1 bins")
     p.add_argument("--welch", type=int, default=0, help="also compute the averaged PSD with this NFFT (Hann)")
     p.add_argument("--integrate", type=_positive, default=0, metavar="K",
                    help="also write one dB row per K frames of --nfft samples (integrated_db)")
@@ -207,6 +246,10 @@ def main(argv=None) -> int:
     from . import spectrum
     if args.cmd == "extract":
         return _extract(args, sigmf_io, spectrum)
+    if not args.path.endswith(".zip") and sigmf_io.sigmf_datatype(args.path) in REAL_DATATYPES:
+        return _psd_real(args, sigmf_io, spectrum)
+    if args.nfft is None:
+        args.nfft = 4096
     # one read; an int16 recording stays int16 (the spectrum row and the --integrate / --pfb rows are computed from the int16 samples
     # themselves: the same bits from half the bytes) and is widened only if the Welch leg, which stays on complex64, is asked for.
     # A ci8 / cu8 recording stays 8-bit for the spectrum row and the --integrate, --pfb and --sk rows (2 bytes per sample over the

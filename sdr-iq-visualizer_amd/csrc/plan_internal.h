@@ -157,6 +157,13 @@ struct sdrk_plan {
     hipStream_t f4k_last = nullptr;
     bool f4k_recorded = false;
     size_t f4k_parts = 0;
+    // real-sampled input (sdrk_exec_*_real, ci16_api.hip): d_real_win = the mode's own window, 2 * nfft float32
+    // (sdrk_plan_set_real_window; nullptr = rectangular); d_real_tab = exp(-i pi k / nfft), k < nfft, built at the first call;
+    // real.buf[0] = the windowed complex64 pairs and real.buf[1] = their transform, of the lengths without a fused kernel,
+    // at most 64 MiB each
+    float* d_real_win = nullptr;
+    float2* d_real_tab = nullptr;
+    sdrk_host::Staging real;
 };
 
 namespace sdrk_host {
@@ -317,6 +324,8 @@ struct HostIo {
     int zero_copy_max_nfft = 0;    // longest frame whose kernel may read / write pinned host memory itself
     int zero_copy_min_nfft = 0;    // ... and the shortest
     size_t in_span = 0;            // input samples a frame reads from its start (0: nfft; pfb_api.hip: taps * nfft)
+    size_t out_bins = 0;           // output bins per frame (0: nfft; the real-input spectra: nfft + 1, and then neither the
+                                   // small mapped call nor the zero-copy branches are offered)
     LaunchFn launch = nullptr;
 };
 

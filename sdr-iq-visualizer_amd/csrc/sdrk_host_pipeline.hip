@@ -175,12 +175,13 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     HIP_TRY(hipSetDevice(p->device));
     const size_t nfft = (size_t)p->nfft;
     const size_t span = io.in_span ? io.in_span : nfft;   // samples a frame reads from its start
+    const size_t bins = io.out_bins ? io.out_bins : nfft;   // output bins of a frame's row
     const size_t in_samples = (n_frames - 1) * frame_stride + span;
     const size_t in_elem = io.in_elem, out_elem = io.out_elem;
     const int epilogue = io.epilogue;
     const size_t in_bytes = in_samples * in_elem;
-    const size_t out_bytes = n_frames * nfft * out_elem;
-    if (in_bytes <= SMALL_IN_BYTES && out_bytes <= SMALL_IN_BYTES && p->nfft <= 4096 && !p->blu_inner) {
+    const size_t out_bytes = n_frames * bins * out_elem;
+    if (in_bytes <= SMALL_IN_BYTES && out_bytes <= SMALL_IN_BYTES && p->nfft <= 4096 && !p->blu_inner && !io.out_bins) {
         if (!p->h_small_in) {
             HIP_TRY(hipHostMalloc(&p->h_small_in, SMALL_IN_BYTES, hipHostMallocMapped));
             HIP_TRY(hipHostMalloc(&p->h_small_out, SMALL_IN_BYTES, hipHostMallocMapped));
@@ -231,11 +232,11 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     size_t target = HOST_CHUNK_BYTES;
     if (in_bytes / 4 < target) target = in_bytes / 4 > ((size_t)1 << 20) ? in_bytes / 4 : ((size_t)1 << 20);
     size_t per = target / stride_bytes;
-    if (per > target / (nfft * out_elem)) per = target / (nfft * out_elem);   // heavily overlapped frames: bound the rows too
+    if (per > target / (bins * out_elem)) per = target / (bins * out_elem);   // heavily overlapped frames: bound the rows too
     if (per < 1) per = 1;
     if (per > n_frames) per = n_frames;
     const size_t chunk_in = ((per - 1) * frame_stride + span) * in_elem;   // (with the span's overlap into the next chunk)
-    const size_t chunk_out = per * nfft * out_elem;
+    const size_t chunk_out = per * bins * out_elem;
     sdrk::CopyPool& pool = sdrk::CopyPool::get();
     HostTrace tr;
     { const char* env = getenv("SDRK_HOST_TRACE"); tr.on = env && env[0] == '1'; }
@@ -247,7 +248,7 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     // Caller arrays in pinned memory (sdrk_host_alloc / sdrk_host_register) are not staged: the copy engines read
     // and write them directly.  Decided per side.
     const bool in_pinned = pinned_ranges().covers(iq, in_bytes), out_pinned = pinned_ranges().covers(out, out_bytes);
-    const bool zc_length = p->nfft <= io.zero_copy_max_nfft && p->nfft >= io.zero_copy_min_nfft;
+    const bool zc_length = p->nfft <= io.zero_copy_max_nfft && p->nfft >= io.zero_copy_min_nfft && !io.out_bins;
     const bool zero_copy = zc_length && !p->blu_inner && frame_stride >= nfft && in_bytes <= ZERO_COPY_MAX_BYTES &&
                            !in_pinned && !out_pinned;
     if (in_pinned && out_pinned && zc_length && !p->blu_inner && frame_stride >= nfft &&
@@ -270,7 +271,7 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
     for (size_t f0 = 0; f0 < n_frames; f0 += per) {
         const size_t nf = n_frames - f0 < per ? n_frames - f0 : per;
         const size_t cin = ((nf - 1) * frame_stride + span) * in_elem;
-        const size_t cout = nf * nfft * out_elem;
+        const size_t cout = nf * bins * out_elem;
         HostSlot* sp = nullptr;
         st = pipe.acquire(chunk_in, chunk_out, sp);
         if (st != SDRK_OK) return st;
@@ -278,7 +279,7 @@ int exec_host(sdrk_plan* p, const void* iq, size_t n_frames, size_t frame_stride
         const double t0 = tr.on ? HostTrace::now() : 0;
         const void* src = static_cast<const char*>(iq) + f0 * frame_stride * in_elem;
         src = chunk_pinned_src(s, src, cin, in_pinned);
-        void* user_rows = static_cast<char*>(out) + f0 * nfft * out_elem;
+        void* user_rows = static_cast<char*>(out) + f0 * bins * out_elem;
         if (tr.on) tr.t_in += HostTrace::now() - t0;
         if (zero_copy) {
             // the transform reads the pinned chunk and writes the pinned rows itself, over PCIe: no DMA-engine

@@ -573,6 +573,9 @@ int sdrk_plan_destroy(sdrk_plan* p) {
     p->pfb.release();
     if (p->d_fir_h) (void)hipFree(p->d_fir_h);
     if (p->d_beam_h) (void)hipFree(p->d_beam_h);
+    if (p->d_real_win) (void)hipFree(p->d_real_win);
+    if (p->d_real_tab) (void)hipFree(p->d_real_tab);
+    p->real.release();
     if (p->f4k_recorded) (void)hipEventSynchronize(p->f4k_ev);   // a ticketed launch on a caller's stream still draws from the heads
     if (p->d_f4k_heads) (void)hipFree(p->d_f4k_heads);
     if (p->d_f4k_rot) (void)hipFree(p->d_f4k_rot);

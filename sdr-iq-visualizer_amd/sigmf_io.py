@@ -17,6 +17,10 @@ Multi-channel recordings (``core:num_channels = C``, the channels' samples inter
 end delivers them): ``write_sigmf(..., num_channels=C)`` and ``read_sigmf_channels`` -> ``(n, C)`` (``(n, C, 2)`` for the
 integer formats, ci8 / cu8 included).  ``read_sigmf`` itself
 reads the data file as one stream whatever the channel count says.
+
+Real-sampled recordings (``rf32_le``, ``ri16_le``, ``ri8``, ``ru8``): ``write_sigmf(..., datatype=...)`` from a flat array of
+the matching dtype, ``read_sigmf_real`` -> the flat array in the file's own dtype, for the ``r*`` spectrum functions.
+``read_sigmf`` refuses them: it returns complex samples.
 """
 from __future__ import annotations
 
@@ -33,6 +37,8 @@ _DTYPES = {"cf32_le": np.dtype("<c8"), "cf64_le": np.dtype("<c16"),
            "ci16_le": np.dtype("<i2"), "ci8": np.dtype("i1"), "cu8": np.dtype("u1")}
 _CU8_MID = np.float32(127.5)          # mid-scale of 0 ... 255: cu8 decodes to (I - 127.5) + 1j*(Q - 127.5)
 _NATIVE = {"ci16_le": np.int16, "ci8": np.int8, "cu8": np.uint8}   # the (n, 2) dtype read_sigmf(native=...) gives back
+# real-sampled recordings: read_sigmf_real / write_sigmf only (read_sigmf refuses them); the flat array's dtype
+_REAL = {"rf32_le": np.dtype("<f4"), "ri16_le": np.dtype("<i2"), "ri8": np.dtype("i1"), "ru8": np.dtype("u1")}
 
 
 def make_metadata(sample_rate: float, center_freq: float, *, description: str = "IQ recording",
@@ -101,8 +107,19 @@ def write_sigmf(base_path: str, samples, sample_rate: float, center_freq: float,
     samples the format holds exactly) and ``<base>.sigmf-meta``; returns both paths.
     ``num_channels=C`` (> 1): ``samples`` is ``(n, C)`` complex (or ``(n, C, 2)`` int16; for ci8 / cu8 ``(n, C, 2)`` int8 /
     uint8, nothing else), stored with the channels interleaved per sample instant and ``core:num_channels = C`` in the metadata."""
+    if datatype in _REAL:
+        x = np.asarray(samples)
+        if x.dtype != _REAL[datatype].newbyteorder("=") or x.ndim != 1 or int(num_channels) != 1:
+            raise ValueError(f"datatype={datatype!r} takes a flat {_REAL[datatype].newbyteorder('=').name} array of one channel, got "
+                             f"{x.dtype} of shape {x.shape}")
+        data_path, meta_path = base_path + ".sigmf-data", base_path + ".sigmf-meta"
+        np.ascontiguousarray(x).astype(_REAL[datatype], copy=False).tofile(data_path)
+        with open(meta_path, "w") as fh:
+            json.dump(make_metadata(sample_rate, center_freq, datatype=datatype, **meta_kw), fh, indent=2)
+        return data_path, meta_path
     if datatype not in ("cf32_le", "ci16_le", "ci8", "cu8"):
-        raise ValueError(f"write_sigmf writes 'cf32_le', 'ci16_le', 'ci8' or 'cu8', not {datatype!r}")
+        raise ValueError(f"write_sigmf writes 'cf32_le', 'ci16_le', 'ci8', 'cu8' or the real 'rf32_le', 'ri16_le', 'ri8', 'ru8', "
+                         f"not {datatype!r}")
     num_channels = int(num_channels)
     if num_channels < 1:
         raise ValueError("num_channels must be >= 1")
@@ -192,6 +209,40 @@ def read_sigmf(path: str, max_samples: Optional[int] = None, native=False) -> Tu
         samples = _decode(raw, g.get("core:datatype", "cf32_le"))
     if max_samples is not None:
         samples = samples[: int(max_samples)]
+    caps = meta.get("captures") or [{}]
+    out = dict(meta)
+    out["sample_rate"] = float(g.get("core:sample_rate", 1.0))
+    out["center_freq"] = float(caps[0].get("core:frequency", 0.0))
+    return samples, out
+
+
+def sigmf_datatype(path: str) -> str:
+    """``core:datatype`` of a recording given its ``.sigmf-meta``, ``.sigmf-data`` or base name (default ``cf32_le``)."""
+    base = path
+    for ext in (".sigmf-meta", ".sigmf-data"):
+        if base.endswith(ext):
+            base = base[: -len(ext)]
+    with open(base + ".sigmf-meta") as fh:
+        return json.load(fh).get("global", {}).get("core:datatype", "cf32_le")
+
+
+def read_sigmf_real(path: str, max_samples: Optional[int] = None) -> Tuple[np.ndarray, dict]:
+    """Read a real-sampled recording (``rf32_le``, ``ri16_le``, ``ri8``, ``ru8``) given its ``.sigmf-meta``, ``.sigmf-data``
+    or base name: ``(samples, meta)`` with the samples flat and in the file's own dtype (float32, int16, int8, uint8) — what
+    ``rspectrum_db`` / ``rfft`` / ``SpectrumPlan.rstft_db`` take.  ``meta`` as from ``read_sigmf``.  Any other datatype is a
+    ValueError."""
+    base = path
+    for ext in (".sigmf-meta", ".sigmf-data"):
+        if base.endswith(ext):
+            base = base[: -len(ext)]
+    with open(base + ".sigmf-meta") as fh:
+        meta = json.load(fh)
+    g = meta.get("global", {})
+    datatype = g.get("core:datatype", "cf32_le")
+    if datatype not in _REAL:
+        raise ValueError(f"read_sigmf_real reads {sorted(_REAL)}, not {datatype!r} (read_sigmf reads the complex datatypes)")
+    a = np.fromfile(base + ".sigmf-data", dtype=_REAL[datatype], count=-1 if max_samples is None else int(max_samples))
+    samples = a.astype(_REAL[datatype].newbyteorder("="), copy=False)
     caps = meta.get("captures") or [{}]
     out = dict(meta)
     out["sample_rate"] = float(g.get("core:sample_rate", 1.0))

@@ -32,6 +32,11 @@ the same way — the array's dtype is the format — for per-frame rows / spectr
 (``pfb_*_ci8``) and spectral kurtosis (``spectral_kurtosis_ci8``, ``pfb_spectral_kurtosis_ci8``): the bits of the complex64
 call on ``iq8_to_c64(iq)``, from a quarter of the input bytes.
 
+``rspectrum_db`` / ``rfft`` / ``rfreq_axis`` (and ``SpectrumPlan.set_real_window`` / ``rspectrum_db`` / ``rfft`` / ``rstft_db`` /
+``exec_device_real``) take REAL sample streams — float32, int16, int8 or uint8 (``v - 127.5``), SigMF ``rf32_le`` / ``ri16_le`` /
+``ri8`` / ``ru8``; the dtype is the format, float64 is refused — in frames of ``2*nfft`` samples and return one-sided rows of
+``nfft + 1`` bins from 0 to fs/2 (``np.fft.rfft``'s order, never shifted), from a transform of half the frame length.
+
 ``pfb_*`` (``SpectrumPlan.set_pfb`` / ``pfb_db`` / ``pfb_fft`` / ``pfb_integrate`` and the module functions ``pfb_db`` and
 ``pfb_integrated_db``) put a polyphase filter bank front end before the transform: a prototype filter of ``T*nfft`` float32 coefficients (``pfb_prototype``: a windowed
 sinc) weights ``T*nfft`` consecutive samples, the ``T`` blocks are summed into ``nfft`` samples (float32, products and sums
@@ -156,6 +161,44 @@ def _as_ci8(a, nfft: Optional[int] = None, stream: bool = False) -> np.ndarray:
         want = "(N, 2) or (B, N, 2)" if nfft is None else f"({nfft}, 2) or (B, {nfft}, 2)"
         raise ValueError(f"8-bit I,Q frames must have shape {want}, got {a.shape}")
     return a
+
+
+_REAL_FORMATS = {np.dtype(np.float32): _ffi.REAL_F32, np.dtype(np.int16): _ffi.REAL_S16, np.dtype(np.int8): _ffi.REAL_S8,
+                 np.dtype(np.uint8): _ffi.REAL_U8}
+REAL_FORMAT_NAMES = {"f32": _ffi.REAL_F32, "s16": _ffi.REAL_S16, "s8": _ffi.REAL_S8, "u8": _ffi.REAL_U8}
+
+
+def _as_real(a, frame_len: int, stream: bool = False) -> np.ndarray:
+    """Check a real-sampled array (no copy, no conversion): C-contiguous float32, int16, int8 or uint8 — the dtype is the
+    format (SigMF rf32_le / ri16_le / ri8 / ru8); ``(frames, frame_len)`` or a flat stream.  float64 is refused, not
+    narrowed.  Anything else is a ValueError, before any device call."""
+    if not isinstance(a, np.ndarray) or a.dtype not in _REAL_FORMATS:
+        raise ValueError(f"real-sampled input must be a numpy float32, int16, int8 or uint8 array, got "
+                         f"{getattr(a, 'dtype', type(a).__name__)}")
+    if not a.flags.c_contiguous:
+        raise ValueError("real-sampled input must be C-contiguous")
+    if stream:
+        if a.ndim != 1:
+            raise ValueError(f"a real-sampled stream must have shape (n_samples,), got {a.shape}")
+    elif a.ndim == 1:
+        if a.shape[0] == 0 or a.shape[0] % frame_len:
+            raise ValueError(f"a flat real-sampled array must hold whole frames of {frame_len} samples, got {a.shape[0]}")
+    elif a.ndim != 2 or a.shape[1] != frame_len:
+        raise ValueError(f"real-sampled frames must have shape (frames, {frame_len}) or be flat, got {a.shape}")
+    return a
+
+
+def _real_format(a: np.ndarray) -> int:
+    """The C format code (SDRK_REAL_*) of a checked real-sampled array."""
+    return _REAL_FORMATS[a.dtype]
+
+
+def _real_window(window: WindowArg, frame_len: int) -> Optional[np.ndarray]:
+    """The real window of ``frame_len`` float32 coefficients a ``WindowArg`` names, None for rectangular."""
+    kind, w, _ = _window_spec(window, frame_len)
+    if kind == _ffi.WINDOW_HANN:
+        return np.hanning(frame_len).astype(np.float32)
+    return w
 
 
 def _iq8_format(a: np.ndarray) -> int:
@@ -859,6 +902,93 @@ class SpectrumPlan:
         """``exec_device_ci8`` ``launches`` times on the plan's stream; the milliseconds of each."""
         return self._exec_device_timed_each(_CI8, d_iq, n_frames, d_out, launches, frame_stride, what="8-bit I,Q input",
                                             fmt=IQ8_UNSIGNED if unsigned else IQ8_SIGNED)
+
+    # -- real-sampled input (SigMF rf32_le / ri16_le / ri8 / ru8): frames of 2 * nfft real samples, one-sided rows of
+    #    nfft + 1 bins from 0 to fs / 2 in ascending order; the array's dtype is the format; float32 power-of-two plans.  The
+    #    plan's own window and shift play no part: the mode has its window (set_real_window), rectangular until one is set --
+    def set_real_window(self, window: WindowArg) -> None:
+        """The real window of the ``r*`` calls: None / ``"rect"``, ``"hann"`` or ``2 * nfft`` coefficients (copied)."""
+        self._float32_only("real-sampled input")
+        w = _real_window(window, 2 * self.nfft)
+        with self._lock:
+            if w is None:
+                check(lib().sdrk_plan_set_real_window(self.handle, None, c_size_t(0)))
+            else:
+                check(lib().sdrk_plan_set_real_window(self.handle, w.ctypes.data_as(c_void_p), c_size_t(w.shape[0])))
+
+    def _frames_real(self, x):
+        self._float32_only("real-sampled input")
+        x = _as_real(x, 2 * self.nfft)
+        one = x.ndim == 1 and x.shape[0] == 2 * self.nfft
+        return x.reshape(-1, 2 * self.nfft), one
+
+    def _run_host_real(self, fn, x: np.ndarray, n_frames: int, stride: int, out: np.ndarray) -> None:
+        with self._lock:
+            check(fn(self.handle, x.ctypes.data_as(c_void_p), _real_format(x), c_size_t(n_frames), c_size_t(stride),
+                     out.ctypes.data_as(c_void_p)))
+
+    def rspectrum_db(self, x, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """float32 rows ``20*log10(|rfft(w*x)| + eps)`` of real frames ``(frames, 2*nfft)`` (or flat: one frame gives one
+        row), ``nfft + 1`` bins each.  float32, int16, int8 or uint8 (``v - 127.5``) samples."""
+        x, one = self._frames_real(x)
+        res = self._out_array(out, (self.nfft + 1,) if one else (x.shape[0], self.nfft + 1), np.float32)
+        self._run_host_real(lib().sdrk_exec_host_real, x, x.shape[0], 2 * self.nfft, res)
+        return res
+
+    def rfft(self, x) -> np.ndarray:
+        """complex64 ``np.fft.rfft(w*x, axis=-1)`` of real frames, shapes and dtypes as ``rspectrum_db``."""
+        x, one = self._frames_real(x)
+        res = np.empty((x.shape[0], self.nfft + 1), dtype=np.complex64)
+        self._run_host_real(lib().sdrk_exec_fft_host_real, x, x.shape[0], 2 * self.nfft, res)
+        return res[0] if one else res
+
+    def rstft_db(self, x, hop: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Spectrogram rows over one flat real-sampled stream: ``1 + (len - 2*nfft) // hop`` rows of ``nfft + 1`` bins;
+        ``hop`` in real samples, even (default ``2*nfft``)."""
+        self._float32_only("real-sampled input")
+        x = _as_real(x, 2 * self.nfft, stream=True)
+        length = 2 * self.nfft
+        hop = length if hop is None else int(hop)
+        if hop < 2 or hop % 2:
+            raise ValueError(f"hop must be a positive even number of real samples, got {hop}")
+        if x.shape[0] < length:
+            raise ValueError(f"the stream has {x.shape[0]} samples, fewer than one frame of {length}")
+        rows = 1 + (x.shape[0] - length) // hop
+        res = self._out_array(out, (rows, self.nfft + 1), np.float32)
+        self._run_host_real(lib().sdrk_exec_host_real, x, rows, hop, res)
+        return res
+
+    def _device_real_args(self, d_x: int, n_frames: int, d_out: int, fmt, out: str, frame_stride: Optional[int],
+                          out_stride: Optional[int]) -> list:
+        self._float32_only("real-sampled input")
+        if isinstance(fmt, str):
+            if fmt not in REAL_FORMAT_NAMES:
+                raise ValueError(f"fmt must be one of {sorted(REAL_FORMAT_NAMES)} or an SDRK_REAL_* code, got {fmt!r}")
+            fmt = REAL_FORMAT_NAMES[fmt]
+        if out not in ("db", "complex"):
+            raise ValueError(f"out must be 'db' or 'complex', got {out!r}")
+        stride = 2 * self.nfft if frame_stride is None else int(frame_stride)
+        return [c_void_p(d_x), int(fmt), c_size_t(int(n_frames)), c_size_t(stride),
+                _ffi.REAL_OUT_DB if out == "db" else _ffi.REAL_OUT_COMPLEX, c_void_p(d_out),
+                c_size_t(0 if out_stride is None else int(out_stride))]
+
+    def exec_device_real(self, d_x: int, n_frames: int, d_out: int, *, fmt, out: str = "db",
+                         frame_stride: Optional[int] = None, out_stride: Optional[int] = None, stream: int = 0) -> None:
+        """Device pointers: real samples in (``fmt``: ``"f32"``, ``"s16"``, ``"s8"``, ``"u8"``), rows of ``nfft + 1`` float32
+        dB values (``out="db"``) or complex64 (``"complex"``) out, asynchronous on ``stream`` (0: the plan's stream).
+        ``frame_stride`` in real samples (even; default ``2*nfft``), ``out_stride`` in output elements (default packed)."""
+        args = self._device_real_args(d_x, n_frames, d_out, fmt, out, frame_stride, out_stride)
+        with self._lock:
+            check(lib().sdrk_exec_device_real(self.handle, *args, c_void_p(stream) if stream else None))
+
+    def exec_device_real_timed_each(self, d_x: int, n_frames: int, d_out: int, launches: int = 1, *, fmt, out: str = "db",
+                                    frame_stride: Optional[int] = None, out_stride: Optional[int] = None) -> list:
+        """``exec_device_real`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_real_args(d_x, n_frames, d_out, fmt, out, frame_stride, out_stride)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_real_timed_each(self.handle, *args, int(launches), ms))
+        return [float(v) for v in ms]
 
     def welch_psd(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
         """Averaged periodogram of one contiguous stream, float32 ``(nfft,)``:
@@ -2050,9 +2180,10 @@ def _cached_plan(nfft: int, window: WindowArg, eps: float, shift: bool, device: 
 
 def clear_plan_cache() -> None:
     with _plans_lock:
-        for p in _plans.values():
+        for p in list(_plans.values()) + list(_real_plans.values()):
             p.close()
         _plans.clear()
+        _real_plans.clear()
 
 
 def _nfft_of(samples) -> int:
@@ -2168,6 +2299,56 @@ def fft_c128(samples, *, window: WindowArg = None, shift: bool = False, device: 
     dtype), optionally fftshifted; powers of two 2 ... 2^22."""
     nfft = _nfft_of(samples)
     return _cached_plan(nfft, window, 1e-12, shift, device, "double").fft(samples)
+
+
+_real_plans: dict = {}
+
+
+def _cached_real_plan(nfft_real: int, window: WindowArg, eps: float, device: int) -> SpectrumPlan:
+    """A plan of ``nfft_real // 2`` with the real window set: its own cache, since the real window is state of the plan."""
+    nfft_real = int(nfft_real)
+    if nfft_real < 32 or nfft_real & (nfft_real - 1):
+        raise ValueError(f"nfft_real={nfft_real}: real frames are powers of two 32 ... 2^21 samples long")
+    w = _real_window(window, nfft_real)
+    key = (int(device), nfft_real, None if w is None else w.tobytes(), float(eps))
+    with _plans_lock:
+        plan = _real_plans.get(key)
+        if plan is None:
+            plan = SpectrumPlan(nfft_real // 2, eps=eps, shift=False, device=device)
+            if w is not None:
+                plan.set_real_window(w)
+            if len(_real_plans) >= 8:
+                for p in _real_plans.values():
+                    p.close()
+                _real_plans.clear()
+            _real_plans[key] = plan
+        return plan
+
+
+def rspectrum_db(x, nfft_real: int, window: WindowArg = None, *, eps: float = 1e-12, device: int = 0,
+                 out: Optional[np.ndarray] = None) -> np.ndarray:
+    """One-sided power spectrum in dB of real-sampled frames ``(frames, nfft_real)`` (or flat): float32
+    ``20*log10(|np.fft.rfft(x*window, axis=-1)| + eps)``, ``nfft_real // 2 + 1`` bins from 0 to fs/2.  ``x`` is float32,
+    int16, int8 or uint8 (``v - 127.5``) — SigMF rf32_le / ri16_le / ri8 / ru8 — read as it is; ``window``: None, ``"hann"``
+    or ``nfft_real`` coefficients."""
+    x = _as_real(x, int(nfft_real))
+    return _cached_real_plan(nfft_real, window, eps, device).rspectrum_db(x, out=out)
+
+
+def rfft(x, nfft_real: int, window: WindowArg = None, *, device: int = 0) -> np.ndarray:
+    """complex64 ``np.fft.rfft(x*window, axis=-1)`` of real-sampled frames; shapes and dtypes as ``rspectrum_db``."""
+    x = _as_real(x, int(nfft_real))
+    return _cached_real_plan(nfft_real, window, 1e-12, device).rfft(x)
+
+
+def rfreq_axis(nfft_real: int, sample_rate: float, center_freq: float = 0.0) -> np.ndarray:
+    """float64 frequency axis in Hz of the one-sided rows: bin k of ``nfft_real // 2 + 1`` at ``k * sample_rate / nfft_real
+    + center_freq`` — ``np.fft.rfftfreq(nfft_real, 1/sample_rate) + center_freq`` with the same float operations."""
+    n = int(nfft_real)
+    if n < 2 or n % 2:
+        raise ValueError("nfft_real must be even and >= 2")
+    val = 1.0 / (n * (1 / sample_rate))
+    return np.arange(0, n // 2 + 1, dtype=int) * val + center_freq
 
 
 def freq_axis(n: int, sample_rate: float, center_freq: float = 0.0) -> np.ndarray:
