@@ -376,8 +376,21 @@ int sdrk_exec_host_integrated_ci8(sdrk_plan* plan, const void* iq_ci8, int iq8_f
  * Refused, nothing launched: an f64 plan, an odd frame_stride, a misaligned pointer, a window of another length, an unknown
  * real_format or out_form, out_stride in 1 ... nfft, NULL pointers (SDRK_ERR_INVALID); a chirp-z (non-power-of-two) plan and
  * nfft < 16 or > 2^20 (SDRK_ERR_UNSUPPORTED); each with a message.  A plan that has refused still works.
- * Not provided: integrated / filter-bank / kurtosis / cross forms and the FIR family on real input, double precision, odd
- * hops, the inverse transform. */
+ * Integrated form (sdrk_exec_*_real_integrated): ONE row of nfft + 1 float32 per group of k_frames consecutive frames, group g
+ * the frames [g * k_frames, (g + 1) * k_frames); rows packed, n_groups x (nfft + 1), ascending from 0 to fs/2, never shifted.
+ * The frame, format, window, alignment and stride rules are those above.  With X_f[k] the complex64 row of frame f as
+ * SDRK_REAL_OUT_COMPLEX returns it and p_f[k] = fmaf(re, re, im * im), the row is the reduction of p_f[k] over the group's
+ * frames by `detector` (SDRK_DET_MEAN: compensated sum times float32(1 / k_frames); SDRK_DET_MAX; SDRK_DET_MIN), given as
+ * 20*log10(sqrt(R) + eps) (SDRK_INT_OUT_DB) or scale * R (SDRK_INT_OUT_POWER) — the detectors, forms and splitting of few
+ * long groups are those of sdrk_exec_device_integrated.  N = 4096 reduces inside the transform's kernel on the caller's data;
+ * other lengths run the per-frame route into at most 64 MiB more of plan-owned staging and reduce down its columns.
+ * Promised: an unsplit group's row carries the bits of that reduction applied to the per-frame complex rows; k_frames = 1 in
+ * dB is the per-frame SDRK_REAL_OUT_DB row bit for bit; the integer formats give the bits of the float32 call on the widened
+ * samples; the host entry gives the device entry's bits however it is chunked; a group's row does not depend on its place
+ * in a call.  Refused, nothing launched: everything the per-frame entries refuse, and an unknown detector or out_form,
+ * n_groups or k_frames of 0, a frame_stride of 0 (SDRK_ERR_INVALID).
+ * Not provided: filter-bank / kurtosis / cross forms and the FIR family on real input, double precision, odd hops, the
+ * inverse transform. */
 enum sdrk_real_format { SDRK_REAL_F32 = 0, SDRK_REAL_S16 = 1, SDRK_REAL_S8 = 2, SDRK_REAL_U8 = 3 };
 enum sdrk_real_out { SDRK_REAL_OUT_DB = 0, SDRK_REAL_OUT_COMPLEX = 1 };
 int sdrk_plan_set_real_window(sdrk_plan* plan, const float* w, size_t n);
@@ -387,6 +400,13 @@ int sdrk_exec_device_real_timed_each(sdrk_plan* plan, const void* d_x, int real_
                                      int out_form, void* d_out, size_t out_stride, int launches, float* each_ms);
 int sdrk_exec_host_real(sdrk_plan* plan, const void* x, int real_format, size_t n_frames, size_t frame_stride, float* out_db);
 int sdrk_exec_fft_host_real(sdrk_plan* plan, const void* x, int real_format, size_t n_frames, size_t frame_stride, void* out_c64);
+int sdrk_exec_device_real_integrated(sdrk_plan* plan, const void* d_x, int real_format, size_t n_groups, size_t k_frames,
+                                     size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream);
+int sdrk_exec_device_real_integrated_timed_each(sdrk_plan* plan, const void* d_x, int real_format, size_t n_groups,
+                                                size_t k_frames, size_t frame_stride, int detector, int out_form, float scale,
+                                                float* d_out, int launches, float* each_ms);
+int sdrk_exec_host_real_integrated(sdrk_plan* plan, const void* x, int real_format, size_t n_groups, size_t k_frames,
+                                   size_t frame_stride, int detector, int out_form, float scale, float* out);
 
 /* ---- polyphase filter bank spectra: a T-tap weighted fold in front of the transform ------
  * A plain windowed FFT gives every bin the window's response: a wide main lobe, side lobes that fall slowly.  A polyphase

@@ -288,6 +288,13 @@ SYMBOLS = [
                                                  POINTER(c_float)]),
     ("sdrk_exec_host_real", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     ("sdrk_exec_fft_host_real", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
+    # ... integrated: one row of nfft + 1 bins per k frames (format, groups, k, stride, detector, out form, scale)
+    ("sdrk_exec_device_real_integrated", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                                 c_void_p, c_void_p]),
+    ("sdrk_exec_device_real_integrated_timed_each", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int,
+                                                            c_float, c_void_p, c_int, POINTER(c_float)]),
+    ("sdrk_exec_host_real_integrated", c_int, [c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float,
+                                               c_void_p]),
 ]
 
 # sdrk_real_format / sdrk_real_out of include/sdrk.h

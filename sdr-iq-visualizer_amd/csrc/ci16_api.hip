@@ -14,7 +14,9 @@
 //
 // The real-input entry points (sdrk_plan_set_real_window, sdrk_exec_*_real: SigMF rf32_le / ri16_le / ri8 / ru8) live here as
 // well: a frame of 2 * nfft real samples is a frame of nfft pairs in the complex format of the same width, so the pointers,
-// strides and staging are these (kernels_real.h has the arithmetic, rspec4096.hip and real_kernels.hip the kernels).
+// strides and staging are these (kernels_real.h has the arithmetic, rspec4096.hip and real_kernels.hip the kernels).  Their
+// integrated forms (sdrk_exec_*_real_integrated) are integrate_call.h's call with rows of nfft + 1 bins: rspec4096_groups.hip
+// reduces inside the transform at N = 4096, every other length runs launch_real into staging and integrate_rows.hip over it.
 // Host code only (g++ builds it against tests/fake_hip for the sanitizer legs).
 #include "../../include/sdrk.h"
 
@@ -25,6 +27,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "integrate_call.h"
 #include "kernels_ci16.h"
 #include "kernels_ci8.h"
 #include "kernels_real.h"
@@ -291,15 +294,41 @@ int launch_real_bound(sdrk_plan* p, const void* d_in, size_t n_frames, size_t st
     return launch_real(p, d_in, FMT, n_frames, stride, d_out, (size_t)p->nfft + 1, epilogue, stream);
 }
 
+LaunchFn real_launch_fn(int fmt) {
+    return fmt == SDRK_REAL_F32   ? launch_real_bound<SDRK_REAL_F32>
+           : fmt == SDRK_REAL_S16 ? launch_real_bound<SDRK_REAL_S16>
+           : fmt == SDRK_REAL_S8  ? launch_real_bound<SDRK_REAL_S8>
+                                  : launch_real_bound<SDRK_REAL_U8>;
+}
+
 // pairs in (8 / 4 / 2 bytes, the stride in pairs); float32 rows or complex64 of nfft + 1 bins out; through the copy engines
 HostIo real_io(const sdrk_plan* p, int fmt, int epilogue) {
-    const LaunchFn fn = fmt == SDRK_REAL_F32   ? launch_real_bound<SDRK_REAL_F32>
-                        : fmt == SDRK_REAL_S16 ? launch_real_bound<SDRK_REAL_S16>
-                        : fmt == SDRK_REAL_S8  ? launch_real_bound<SDRK_REAL_S8>
-                                               : launch_real_bound<SDRK_REAL_U8>;
-    HostIo io = frames_io(sdrk::real_pair_bytes(fmt), 0, fn, epilogue);
+    HostIo io = frames_io(sdrk::real_pair_bytes(fmt), 0, real_launch_fn(fmt), epilogue);
     io.out_bins = (size_t)p->nfft + 1;
     return io;
+}
+
+// ---- integrated real input: one row of nfft + 1 bins per k frames ----
+
+// pairs in, the stride in pairs; N = 4096: the kernel that reduces behind the split; every other length: packed complex64 rows
+// of nfft + 1 bins from launch_real (its two stagings) into the call's own staging, reduced down the columns
+IntIo real_int_io(const sdrk_plan* p, int fmt) {
+    IntIo io;
+    io.in_elem = sdrk::real_pair_bytes(fmt);
+    io.fused = sdrk::launch_rspec4096_groups;
+    io.transform = real_launch_fn(fmt);
+    io.bins = (size_t)p->nfft + 1;
+    io.real_fmt = fmt;
+    return io;
+}
+
+// What the integrated real entries refuse: what a per-frame real entry does (check_real_exec), then what an integrated entry
+// does (check_int_args); frame_stride in REAL samples.
+int check_real_integrated(const sdrk_plan* p, const void* x, int fmt, size_t n_groups, size_t k, size_t frame_stride, int detector,
+                          int out_form, const float* out) {
+    int st = check_real_exec(p, x, fmt, 1, frame_stride, SDRK_REAL_OUT_DB, out, 0);
+    if (st != SDRK_OK) return st;
+    return check_int_args(p, x, n_groups, k, frame_stride, detector, out_form, out);
 }
 
 }  // namespace
@@ -402,6 +431,41 @@ int sdrk_exec_fft_host_real(sdrk_plan* p, const void* x, int real_format, size_t
     int st = check_real_exec(p, x, real_format, n_frames, frame_stride, SDRK_REAL_OUT_COMPLEX, out_c64, 0);
     if (st != SDRK_OK) return st;
     return exec_host(p, x, n_frames, frame_stride / 2, out_c64, real_io(p, real_format, sdrk::EPI_COMPLEX));
+}
+
+int sdrk_exec_device_real_integrated(sdrk_plan* p, const void* d_x, int real_format, size_t n_groups, size_t k_frames,
+                                     size_t frame_stride, int detector, int out_form, float scale, float* d_out, void* stream) {
+    int st = check_real_integrated(p, d_x, real_format, n_groups, k_frames, frame_stride, detector, out_form, d_out);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    st = ensure_real_tab(p);
+    if (st != SDRK_OK) return st;
+    return exec_device_integrated(real_int_io(p, real_format), p, d_x, n_groups, k_frames, frame_stride / 2, detector, out_form,
+                                  scale, d_out, stream);
+}
+
+int sdrk_exec_device_real_integrated_timed_each(sdrk_plan* p, const void* d_x, int real_format, size_t n_groups, size_t k_frames,
+                                                size_t frame_stride, int detector, int out_form, float scale, float* d_out,
+                                                int launches, float* each_ms) {
+    if (!each_ms || launches < 1 || launches > 4096) return fail(SDRK_ERR_INVALID, "bad launches/each_ms");
+    int st = check_real_integrated(p, d_x, real_format, n_groups, k_frames, frame_stride, detector, out_form, d_out);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    st = ensure_real_tab(p);
+    if (st != SDRK_OK) return st;
+    return exec_device_integrated_timed_each(real_int_io(p, real_format), p, d_x, n_groups, k_frames, frame_stride / 2, detector,
+                                             out_form, scale, d_out, launches, each_ms);
+}
+
+int sdrk_exec_host_real_integrated(sdrk_plan* p, const void* x, int real_format, size_t n_groups, size_t k_frames,
+                                   size_t frame_stride, int detector, int out_form, float scale, float* out) {
+    int st = check_real_integrated(p, x, real_format, n_groups, k_frames, frame_stride, detector, out_form, out);
+    if (st != SDRK_OK) return st;
+    HIP_TRY(hipSetDevice(p->device));
+    st = ensure_real_tab(p);
+    if (st != SDRK_OK) return st;
+    return exec_host_integrated(real_int_io(p, real_format), p, x, n_groups, k_frames, frame_stride / 2, detector, out_form, scale,
+                                out);
 }
 
 int sdrk_synth_fill_ci16(int device, uint32_t seed, uint64_t first_frame, size_t n_frames, int nfft, void* d_iq_ci16,

@@ -57,6 +57,11 @@ struct IntIo {
     // launch_corrmat_finalize stand where rows / rows2 / finalize do, which are not used
     int channels = 0;
     int fmt = 0;
+    // elements of a row, a state row and a staged spectrum (0: nfft).  Real-sampled input (ci16_api.hip): nfft + 1 bins from 0 to
+    // fs/2; in_elem is then a pair of samples, `transform` writes packed complex64 rows of `bins`, and real_fmt (a
+    // sdrk::REAL_* value) tells the fused launcher what the pairs are
+    size_t bins = 0;
+    int real_fmt = 0;
 };
 
 constexpr size_t INT_STAGE_BYTES = (size_t)64 << 20;   // complex64 spectra of the generic route, per plan
@@ -70,7 +75,8 @@ struct IntCall {
     sdrk::IntSplit sp{1, 1};
     bool fused = false;          // the N = 4096 kernel of io.fused
     bool direct = false;         // io.channels at N = 4096: the spectra kernel that reads the element stream itself
-    size_t group_floats = 0;     // float32 per output group: io.planes * nfft
+    size_t bins = 0;             // elements of a row: io.bins, or nfft
+    size_t group_floats = 0;     // float32 per output group: io.planes * bins
     size_t stage_frames = 0;     // generic route: frames per staging chunk
     unsigned launches = 0;       // reduction launches so far: picks the carry rows
     hipStream_t stream = nullptr;
@@ -125,13 +131,15 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
                (route && std::strcmp(route, "split") == 0    ? false
                 : route && std::strcmp(route, "direct") == 0 ? true
                                                              : sdrk::cm4k_reads_directly(io.fmt, io.channels));
-    c.group_floats = io.planes * nfft;
+    c.bins = io.bins ? io.bins : nfft;
+    const size_t bins = c.bins;
+    c.group_floats = io.planes * bins;
     // the generic route has nfft / 256 workgroups per unit to spread: it splits later than the fused kernel.  The C-channel
     // calls make the two-channel call's cut at every length, so that a pair's planes are that call's bits.
     const size_t ways = c.fused || (f4k && io.channels) ? 1 : (nfft + 255) / 256;
     c.sp = n_groups > (~(size_t)0) / ways ? sdrk::IntSplit{1, k} : sdrk::integrate_split(n_groups * ways, k, p->num_cus);
-    const size_t row = nfft * sizeof(float2);              // a staged spectrum
-    const size_t state_row = nfft * io.state * sizeof(float);
+    const size_t row = bins * sizeof(float2);              // a staged spectrum
+    const size_t state_row = bins * io.state * sizeof(float);
     const size_t n_partials = c.sp.slices > 1 ? n_groups * c.sp.slices : 0;
     Staging& sg = p->integ;   // buf[0]: carry and partial rows; buf[1]: spectra of the generic route
     int st = sg.reserve(0, (2 + n_partials) * state_row);
@@ -147,10 +155,10 @@ inline int call_begin(IntCall& c, const IntIo& io, sdrk_plan* p, size_t n_groups
         if (st != SDRK_OK) return st;
     }
     c.carry[0] = static_cast<float2*>(sg.buf[0].d);
-    // (rows of nfft * state floats: counted in floats, an odd nfft times an odd state is no whole number of float2)
+    // (rows of bins * state floats: counted in floats, an odd length times an odd state is no whole number of float2)
     float* const rows = static_cast<float*>(sg.buf[0].d);
-    c.carry[1] = reinterpret_cast<float2*>(rows + nfft * io.state);
-    c.partials = reinterpret_cast<float2*>(rows + 2 * nfft * io.state);
+    c.carry[1] = reinterpret_cast<float2*>(rows + bins * io.state);
+    c.partials = reinterpret_cast<float2*>(rows + 2 * bins * io.state);
     return sg.enter(stream);   // one state and one staging per plan: a call on another stream waits for the last one's work
 }
 
@@ -169,7 +177,7 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
     a.d_out = d_out;
     a.out_row0 = out_row0;
     a.d_partials = c.partials;
-    a.nfft = p->nfft;
+    a.nfft = (int)c.bins;
     a.d_window = p->d_window;
     a.d_twiddle = p->d_twiddle;
     a.shift = p->shift;
@@ -177,6 +185,9 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
     a.stream = c.stream;
     a.d_pfb_h = p->d_pfb_h;   // (read by the polyphase-filter-bank launcher alone)
     a.pfb_taps = p->pfb_taps;
+    a.d_real_window = p->d_real_win;   // (read by the real-input launcher alone)
+    a.d_real_tab = p->d_real_tab;
+    a.real_fmt = c.io.real_fmt;
     const size_t step = c.fused ? f1 - f0 : c.stage_frames;
     for (size_t s0 = f0; s0 < f1; s0 += step) {
         const size_t s1 = f1 - s0 < step ? f1 : s0 + step;
@@ -228,7 +239,7 @@ inline int call_range(IntCall& c, const void* d_in, size_t f0, size_t f1, float*
             int st = c.io.transform(p, src, s1 - s0, c.stride, d_stage, sdrk::EPI_COMPLEX, c.stream);
             if (st != SDRK_OK) return st;
             a.d_in = d_stage;
-            a.in_stride = (size_t)p->nfft;
+            a.in_stride = c.bins;
             e = c.io.rows(a);
         }
         if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate kernel launch failed: %s", hipGetErrorString(e));
@@ -242,7 +253,7 @@ inline int call_finalize(IntCall& c, float* d_out) {
     const hipError_t e =
         c.io.channels ? sdrk::launch_corrmat_finalize(reinterpret_cast<const float*>(c.partials), c.io.channels, c.n_groups, c.k,
                                                       c.sp.slices, c.p->nfft, c.scale, d_out, c.p->num_cus, c.stream)
-                      : c.io.finalize(c.partials, c.n_groups, c.k, c.sp.slices, c.p->nfft, c.detector, c.out_form, c.scale,
+                      : c.io.finalize(c.partials, c.n_groups, c.k, c.sp.slices, (int)c.bins, c.detector, c.out_form, c.scale,
                                       c.p->eps, d_out, c.p->num_cus, c.stream);
     if (e != hipSuccess) return fail(SDRK_ERR_HIP, "integrate finalize launch failed: %s", hipGetErrorString(e));
     return SDRK_OK;

@@ -37,6 +37,12 @@ struct IntegrateArgs {
     // stream and a frame covers pfb_taps * nfft samples from its start
     const float* d_pfb_h = nullptr;
     int pfb_taps = 0;
+    // real-sampled input (rspec4096_groups.hip): d_in is then the stream of pairs in format real_fmt (a REAL_* value of
+    // kernels_real.h), in_stride counts pairs, nfft is the row length 4097, and the rows are not shifted; the mode's own window
+    // (2 * 4096 floats or nullptr) and the split's table exp(-i pi k / 4096)
+    const float* d_real_window = nullptr;
+    const float2* d_real_tab = nullptr;
+    int real_fmt = 0;
 };
 
 hipError_t launch_fft4096_integrate(const IntegrateArgs& a);

@@ -9,6 +9,7 @@
 // Nothing here is exported.
 #pragma once
 #include "kernels.h"
+#include "kernels_integrate.h"
 
 namespace sdrk {
 
@@ -39,5 +40,8 @@ hipError_t launch_rspec4096(const RealArgs& a);
 hipError_t launch_real_pairs(const RealArgs& a, void* d_pairs);
 // ... and, behind the plan's own transform of those (natural order, complex64: d_z, packed), X and the epilogue into the rows
 hipError_t launch_real_split(const RealArgs& a, const void* d_z);
+// rspec4096_groups.hip (built into the companion library): N = 4096 with the reduction over K frames behind the split, in the
+// transform's registers — one row of 4097 float32 per group; the real-input fields of IntegrateArgs say what the samples are
+hipError_t launch_rspec4096_groups(const IntegrateArgs& a);
 
 }  // namespace sdrk

@@ -33,7 +33,8 @@ the same way — the array's dtype is the format — for per-frame rows / spectr
 call on ``iq8_to_c64(iq)``, from a quarter of the input bytes.
 
 ``rspectrum_db`` / ``rfft`` / ``rfreq_axis`` (and ``SpectrumPlan.set_real_window`` / ``rspectrum_db`` / ``rfft`` / ``rstft_db`` /
-``exec_device_real``) take REAL sample streams — float32, int16, int8 or uint8 (``v - 127.5``), SigMF ``rf32_le`` / ``ri16_le`` /
+``exec_device_real``; integrated over k frames: ``rintegrated_db`` / ``rwelch_psd``, ``SpectrumPlan.rintegrate`` /
+``exec_device_real_integrated``) take REAL sample streams — float32, int16, int8 or uint8 (``v - 127.5``), SigMF ``rf32_le`` / ``ri16_le`` /
 ``ri8`` / ``ru8``; the dtype is the format, float64 is refused — in frames of ``2*nfft`` samples and return one-sided rows of
 ``nfft + 1`` bins from 0 to fs/2 (``np.fft.rfft``'s order, never shifted), from a transform of half the frame length.
 
@@ -199,6 +200,14 @@ def _real_window(window: WindowArg, frame_len: int) -> Optional[np.ndarray]:
     if kind == _ffi.WINDOW_HANN:
         return np.hanning(frame_len).astype(np.float32)
     return w
+
+
+def _real_hop(hop: Optional[int], frame_len: int) -> int:
+    """The hop of an integrated real-input call in real samples: even and positive, by default the frame length."""
+    hop = int(frame_len) if hop is None else int(hop)
+    if hop < 2 or hop % 2:
+        raise ValueError(f"hop must be a positive even number of real samples, got {hop}")
+    return hop
 
 
 def _iq8_format(a: np.ndarray) -> int:
@@ -988,6 +997,69 @@ class SpectrumPlan:
         ms = (c_float * int(launches))()
         with self._lock:
             check(lib().sdrk_exec_device_real_timed_each(self.handle, *args, int(launches), ms))
+        return [float(v) for v in ms]
+
+    # ... integrated: one row of nfft + 1 bins per k consecutive real frames, the reduction inside the transform
+    def _real_hop(self, hop: Optional[int]) -> int:
+        return _real_hop(hop, 2 * self.nfft)
+
+    def rintegrated_groups(self, n_samples: int, k: int, hop: Optional[int] = None) -> int:
+        """Rows ``rintegrate`` returns for a real-sampled stream of ``n_samples``: the ``1 + (n - 2*nfft)//hop`` full frames
+        in whole groups of ``k``; trailing frames that do not fill a group are dropped."""
+        return self._n_groups(2 * self.nfft, n_samples, k, self._real_hop(hop))
+
+    def rintegrate(self, x, k: int, hop: Optional[int] = None, detector: str = "mean", out: str = "db",
+                   scale: float = 1.0) -> np.ndarray:
+        """One float32 row per ``k`` consecutive frames of one flat real-sampled stream, ``(groups, nfft + 1)``: per bin
+        from 0 to fs/2 the mean (``detector="mean"``), maximum or minimum over the group's frames of ``|rfft(w*x_f)|^2``,
+        returned as ``20*log10(sqrt(R) + eps)`` (``out="db"``) or ``scale * R`` (``out="power"``).  Frame f covers samples
+        ``[f*hop, f*hop + 2*nfft)``; ``hop`` in real samples, even (default ``2*nfft``).  float32, int16, int8 or uint8
+        (``v - 127.5``) samples; the reduction runs inside the transform on the GPU, the stream goes through in chunks."""
+        self._float32_only("real-sampled input")
+        x = _as_real(x, 2 * self.nfft, stream=True)
+        hop = self._real_hop(hop)
+        codes = self._int_codes(detector, out)
+        groups = self._n_groups(2 * self.nfft, x.shape[0], k, hop)
+        if groups < 1:
+            raise ValueError(f"the stream has {x.shape[0]} samples, fewer than one group of {int(k)} frames of {2 * self.nfft}")
+        res = np.empty((groups, self.nfft + 1), dtype=np.float32)
+        with self._lock:
+            check(lib().sdrk_exec_host_real_integrated(self.handle, x.ctypes.data_as(c_void_p), _real_format(x), c_size_t(groups),
+                                                       c_size_t(int(k)), c_size_t(hop), *codes, c_float(float(scale)),
+                                                       res.ctypes.data_as(c_void_p)))
+        return res
+
+    def _device_real_integrated_args(self, d_x: int, n_groups: int, k: int, d_out: int, fmt, frame_stride: Optional[int],
+                                     detector: str, out: str, scale: float) -> list:
+        self._float32_only("real-sampled input")
+        if isinstance(fmt, str):
+            if fmt not in REAL_FORMAT_NAMES:
+                raise ValueError(f"fmt must be one of {sorted(REAL_FORMAT_NAMES)} or an SDRK_REAL_* code, got {fmt!r}")
+            fmt = REAL_FORMAT_NAMES[fmt]
+        codes = self._int_codes(detector, out)
+        if int(k) < 1 or int(n_groups) < 1:
+            raise ValueError("n_groups and k must be >= 1")
+        return [c_void_p(d_x), int(fmt), c_size_t(int(n_groups)), c_size_t(int(k)), c_size_t(self._real_hop(frame_stride)), *codes,
+                c_float(float(scale)), c_void_p(d_out)]
+
+    def exec_device_real_integrated(self, d_x: int, n_groups: int, k: int, d_out: int, *, fmt,
+                                    frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                    scale: float = 1.0, stream: int = 0) -> None:
+        """Device pointers: real samples in (``fmt``: ``"f32"``, ``"s16"``, ``"s8"``, ``"u8"``), ``n_groups`` packed float32
+        rows of ``nfft + 1`` bins out (one per ``k`` frames), asynchronous on ``stream`` (0: the plan's stream).
+        ``frame_stride`` in real samples (even; default ``2*nfft``)."""
+        args = self._device_real_integrated_args(d_x, n_groups, k, d_out, fmt, frame_stride, detector, out, scale)
+        with self._lock:
+            check(lib().sdrk_exec_device_real_integrated(self.handle, *args, c_void_p(stream) if stream else None))
+
+    def exec_device_real_integrated_timed_each(self, d_x: int, n_groups: int, k: int, d_out: int, launches: int = 1, *, fmt,
+                                               frame_stride: Optional[int] = None, detector: str = "mean", out: str = "db",
+                                               scale: float = 1.0) -> list:
+        """``exec_device_real_integrated`` ``launches`` times on the plan's stream; the milliseconds of each."""
+        args = self._device_real_integrated_args(d_x, n_groups, k, d_out, fmt, frame_stride, detector, out, scale)
+        ms = (c_float * int(launches))()
+        with self._lock:
+            check(lib().sdrk_exec_device_real_integrated_timed_each(self.handle, *args, int(launches), ms))
         return [float(v) for v in ms]
 
     def welch_psd(self, iq, sample_rate: float, hop: Optional[int] = None) -> np.ndarray:
@@ -2339,6 +2411,37 @@ def rfft(x, nfft_real: int, window: WindowArg = None, *, device: int = 0) -> np.
     """complex64 ``np.fft.rfft(x*window, axis=-1)`` of real-sampled frames; shapes and dtypes as ``rspectrum_db``."""
     x = _as_real(x, int(nfft_real))
     return _cached_real_plan(nfft_real, window, 1e-12, device).rfft(x)
+
+
+def rintegrated_db(x, nfft_real: int, k: int, hop: Optional[int] = None, detector: str = "mean", window: WindowArg = None,
+                   eps: float = 1e-12, device: int = 0) -> np.ndarray:
+    """dB rows of a one-sided spectrogram whose time axis is reduced on the device: one row of ``nfft_real // 2 + 1`` bins per
+    ``k`` frames of the flat real-sampled stream ``x``, the mean / max / min power per bin (``SpectrumPlan.rintegrate``)."""
+    x = _as_real(x, int(nfft_real), stream=True)
+    hop = _real_hop(hop, int(nfft_real))
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    return _cached_real_plan(nfft_real, window, eps, device).rintegrate(x, k, hop, detector, "db")
+
+
+def rwelch_psd(x, nfft_real: int, sample_rate: float, hop: Optional[int] = None, window: WindowArg = "hann", *,
+               device: int = 0) -> np.ndarray:
+    """Linear one-sided PSD (power per Hz) of one flat real-sampled stream as ``matplotlib.mlab.psd`` computes it for real
+    input (no detrend): float32 ``(nfft_real // 2 + 1,)``, the mean over all ``1 + (len - nfft_real)//hop`` full segments of
+    ``|rfft(w*x_r)|^2 / (sample_rate * sum(w^2))`` with the interior bins ``1 ... nfft_real/2 - 1`` doubled.  Transforms and
+    averaging run inside one kernel pass on the device; the doubling is done here on the returned row."""
+    n = int(nfft_real)
+    x = _as_real(x, n, stream=True)
+    hop = _real_hop(hop, n)
+    plan = _cached_real_plan(n, window, 1e-12, device)
+    rows = plan.rintegrated_groups(x.shape[0], 1, hop)
+    if rows < 1:
+        raise ValueError(f"stream of {x.shape[0]} samples is shorter than one {n}-sample segment")
+    w = _real_window(window, n)
+    wss = float(n) if w is None else float(np.sum(w.astype(np.float64) ** 2))
+    row = plan.rintegrate(x, rows, hop, "mean", "power", 1.0 / (float(sample_rate) * wss))[0]
+    row[1:n // 2] *= np.float32(2.0)
+    return row
 
 
 def rfreq_axis(nfft_real: int, sample_rate: float, center_freq: float = 0.0) -> np.ndarray:
